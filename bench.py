@@ -14,11 +14,16 @@ One "step" = one full pass of the hot path over one batch.  `--config` picks the
   3 configs[3]: aloha sim_transfer_cube -- raw 64x64 wrist frames -> StableVAE encode -> DDPM-100 planner -> DDPM-100 IDM
     through LDPAgent.sample, 512 frames per GPU (`--gpus 4` = the 2048-frame configuration BASELINE.json names);
   4 configs[4]: rm_can best-of-N candidates -- 50-step DDIM planner, 1024 candidates per GPU (`--gpus 8` = 8192), timed
-    once with N independent observations and once with ONE observation broadcast to all candidates (SURVEY 8d asks for both).
+    once with N independent observations and (with --full) once with ONE observation broadcast to all candidates.
 Weak scaling in every case: each rank samples its own rows (independent Philox rows keyed by the global plan index) and the
 sampled trajectories (+ actions) are all-gathered over RCCL inside the timed region -- a synchronous collective on the launch
 stream: it orders the ranks by itself, there is no barrier inside the timed region (the two fences bracket it).  Inputs are
 resident in HBM before the timed region starts.
+
+A plain run sets up, warms up, times the `--steps` steps and prints the line; `--full` adds the CPU-baseline leg
+(`cpu_baseline`, rank 0 at N = 1, unless `--no-cpu-baseline`) and, for `--config 4`, the broadcast-observation timing.
+`--dump-outputs DIR` writes what the timed path returned in its last timed step (the gathered rows at N > 1) as
+DIR/<name>.npy (float32, float64 kept) after the timed region.
 
 `--dry-run` exercises only the launcher and the collective plumbing on CPU (backend gloo, no
 GPU work, the line is marked INVALID): it is what the CPU test-suite runs.
@@ -53,6 +58,11 @@ def parse_args(argv=None):
     ap.add_argument("--n-steps", type=int, default=None, help="denoising steps per plan")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements the headline figure does not need (off without --full): the CPU-baseline leg; "
+                         "for --config 4, the same steps again with one observation broadcast to every candidate")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32 or float64; same arguments, same inputs)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="ldp_set_option before the run (tools/: work-split switches, timing ablations)")
     ap.add_argument("--lib", default=None, metavar="PATH",
@@ -72,6 +82,8 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher/collective check on CPU (gloo); no GPU work, the line is INVALID")
     a = ap.parse_args(argv)
+    if a.dump_outputs and (a.train or a.configs0 or a.dry_run):
+        ap.error("--dump-outputs writes what the sampling line's last timed step returned: --train, --configs0 and --dry-run have no such step")
     dflt = {1: (256, "ddim", 100), 2: (1024, "ddpm", 100), 3: (512, "ddpm", 100), 4: (1024, "ddim", 50)}[a.config]
     a.batch = dflt[0] if a.batch is None else a.batch
     a.sampler = dflt[1] if a.sampler is None else a.sampler
@@ -241,6 +253,25 @@ def pmc_call_traffic(config, args, default_batch, default_steps, default_sampler
             return round(json.load(f)["fabric_bytes_per_call"]), "profiles/" + name + " (separate rocprofv3 --pmc passes of this command, bytes per call; not re-measured in this run)"
     except Exception:
         return None, None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def host_outputs(names, tensors):
+    """{name: host copy, float32 (float64 kept)} of what a step returned.  Above DUMP_LIMIT_BYTES in all, every array keeps the same fixed,
+    seeded sample of its leading-dimension rows (in order), enough rows to fit."""
+    import numpy as np
+    import torch
+    outs = {n: (t.detach() if t.dtype in (torch.float32, torch.float64) else t.detach().float()).to("cpu", copy=True).numpy()
+            for n, t in zip(names, tensors)}
+    total = sum(a.nbytes for a in outs.values())
+    if total > DUMP_LIMIT_BYTES:
+        for n, a in outs.items():
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES / total))
+            rows = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.shape[0], keep, replace=False))
+            outs[n] = np.ascontiguousarray(a[rows])
+    return outs
 
 
 def train_line(args, rank=0, world=1, local=0):
@@ -454,7 +485,9 @@ def main():
             one_step(i)
         fence()
         dt_max, ev_ms, last = timed(args.steps, args.warmup)
-        extra = wl.extra_timed(timed, args) if hasattr(wl, "extra_timed") else {}
+        # host copies before anything else runs: the engine's output buffers are reused by the next call
+        dumped = host_outputs(wl.out_names, last) if args.dump_outputs and rank == 0 else None
+        extra = wl.extra_timed(timed, args) if args.full and hasattr(wl, "extra_timed") else {}
     assert all(bool(torch.isfinite(t).all()) for t in last)
     eng.check_fault()                 # a fault of either kind (exchange time-out, fp16-plane range) would show here
     conv_launches, all_launches = eng.launch_counts()
@@ -491,8 +524,12 @@ def main():
                        **info.get("config", {}), **extra},
             "roofline": info["roofline"],
         }
-        if not args.no_cpu_baseline and world == 1:          # CPU leg: rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:          # CPU leg: --full, rank 0 at N=1 only
             line["cpu_baseline"] = wl.cpu_baseline(args)
+        if dumped is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
         print(json.dumps(line), flush=True)
     wl.close()
     if world > 1:
@@ -512,6 +549,7 @@ class PlannerWorkload:
     """configs[1]: the rm_lift planner loop alone (the driver's line).  Exact-fp32 MFMA at <= 256 plans."""
     D, A, T, ah = 25, 7, 8, 4
     name = "rm_lift"
+    out_names = ("plans",)                                                  # what step() returns, in order
 
     def __init__(self, args, rank, world, dev):
         import numpy as np
@@ -578,7 +616,7 @@ class PlannerWorkload:
 class CandidatesWorkload(PlannerWorkload):
     """configs[4]: rm_can best-of-N candidate generation -- the planner loop, 50-step DDIM, 1024 candidates per GPU.  The reference has no
     scoring step: the configuration is "generate N candidates + gather" (SURVEY 8d).  `value` is timed with N independent observations;
-    the same steps with ONE observation broadcast to every candidate are timed right behind (config.shared_cond_*)."""
+    with --full the same steps with ONE observation broadcast to every candidate are timed right behind (config.shared_cond_*)."""
     name = "rm_can"
 
     def extra_timed(self, timed, args):
@@ -597,6 +635,7 @@ class CandidatesWorkload(PlannerWorkload):
 class JointT16Workload:
     """configs[2]: rm_square, pred_horizon 16 (the literal 15 of the yaml is ill-formed for the reference's U-Net: SURVEY 8d), planner + plan assembly +
     IDM as ONE captured graph (ldp_agent_sample), DDPM-100, 1024 plans per GPU, device-resident observation embeddings."""
+    out_names = ("plans", "actions")
 
     def __init__(self, args, rank, world, dev):
         import numpy as np
@@ -673,6 +712,7 @@ class JointT16Workload:
 class AlohaWorkload:
     """configs[3]: aloha sim_transfer_cube through LDPAgent.sample -- raw 64x64 wrist frames [0, 255] -> normalise -> StableVAE encode ->
     latent normalise -> DDPM-100 planner -> plan assembly -> DDPM-100 IDM -> action un-normalisation, device-resident inputs, 512 frames per GPU."""
+    out_names = ("plans", "actions")
 
     def __init__(self, args, rank, world, dev):
         import numpy as np

@@ -3,10 +3,12 @@ tests/golden/*.npz (run `python tests/golden/make_golden.py`).  The GPU parity t
 stored inputs through the HIP path and compare with the stored outputs, so the expensive
 float64 loops are not recomputed on the GPU box.  Weights are regenerated from their seeds
 (weights.init_*_params), they are too large to store."""
+import contextlib
 import os
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from tests import cfgs
 from tests.util import idm_params, idm_params_heavy, planner_params, planner_params_heavy, rng
@@ -20,22 +22,92 @@ def _t64(a):
 
 # The oracle is imported only where a golden is COMPUTED (tests/golden/make_golden.py): loading a case
 # (load_case: what the -m gpu tests and tools/parity_margin.py do) never executes anything under oracle/.
-def planner_fn(params, obs_cond, x_init, step_noise, n_train, n_steps, sampler, dtype=torch.float64):
+class _FixedOrderF:
+    """torch.nn.functional with linear / conv1d / conv_transpose1d computed without BLAS: broadcast products summed over the
+    reduced dimension by torch's own reduction, in chunks of 256 added in order, on one thread.  The order of every sum is then
+    fixed by this code and torch's CPU kernels (the same on every host of one ATen CPU capability), not by the host's BLAS:
+    MKL takes other GEMM kernels on other CPUs (and under other MKL_CBWR / thread settings), and the 100-step loops carry that
+    float64 round-off up to a few 1e-7 -- enough to break a bit-for-bit check."""
+    CHUNK = 256
+
+    def __getattr__(self, name):
+        return getattr(F, name)
+
+    def _mm(self, a, b):                                              # (M, K) @ (K, N)
+        out = None
+        for k0 in range(0, a.shape[1], self.CHUNK):
+            part = (a[:, k0:k0 + self.CHUNK, None] * b[None, k0:k0 + self.CHUNK, :]).sum(1)
+            out = part if out is None else out + part
+        return out
+
+    def linear(self, x, w, b=None):
+        y = self._mm(x.reshape(-1, x.shape[-1]), w.t()).reshape(*x.shape[:-1], w.shape[0])
+        return y if b is None else y + b
+
+    def conv1d(self, x, w, b=None, stride=1, padding=0):
+        B, cin, _ = x.shape
+        cout, _, k = w.shape
+        cols = F.pad(x, (padding, padding)).unfold(2, k, stride)           # (B, Cin, Tout, K)
+        t_out = cols.shape[2]
+        y = self._mm(cols.permute(0, 2, 1, 3).reshape(B * t_out, cin * k), w.reshape(cout, cin * k).t())
+        y = y.reshape(B, t_out, cout).permute(0, 2, 1)
+        return y if b is None else y + b[None, :, None]
+
+    def conv_transpose1d(self, x, w, b=None, stride=1, padding=0):
+        # = a stride-1 convolution of the input spread `stride` apart (zeros between), padded K - 1 - padding, kernel flipped
+        B, cin, T = x.shape
+        k = w.shape[2]
+        xd = x.new_zeros((B, cin, (T - 1) * stride + 1))
+        xd[:, :, ::stride] = x
+        return self.conv1d(xd, w.flip(2).permute(1, 0, 2), b, 1, k - 1 - padding)
+
+
+def _rounded(fn):
+    """fn evaluated in float64 by NumPy and rounded to the tensor's dtype: for the float32 sqrt of the schedule coefficients
+    and the float32 sin / cos of the timestep features, the correctly rounded value.  torch computes them with MKL's vector
+    math, whose last bit depends on the CPU and on MKL_CBWR (1 ulp in a DDPM coefficient is ~1e-7 at the end of the loop)."""
+    def f(t, *args, **kw):
+        return torch.from_numpy(np.asarray(fn(t.detach().double().numpy()))).to(t.dtype)
+    return f
+
+
+class _fixed_order:
+    """Within the block (single-threaded), oracle/torch32.py's GEMMs run through _FixedOrderF and its float32 sqrt / sin / cos
+    are correctly rounded: the results are the same on every x86 host."""
+
+    def __enter__(self):
+        from oracle import torch32
+        self.mod, self.saved, self.threads = torch32, torch32.F, torch.get_num_threads()
+        self.fns = (torch.Tensor.sqrt, torch.sin, torch.cos)
+        torch32.F = _FixedOrderF()
+        torch.Tensor.sqrt, torch.sin, torch.cos = _rounded(np.sqrt), _rounded(np.sin), _rounded(np.cos)
+        torch.set_num_threads(1)
+
+    def __exit__(self, *exc):
+        self.mod.F = self.saved
+        torch.Tensor.sqrt, torch.sin, torch.cos = self.fns
+        torch.set_num_threads(self.threads)
+
+
+def planner_fn(params, obs_cond, x_init, step_noise, n_train, n_steps, sampler, dtype=torch.float64, fixed_order=False):
     """float64 torch restatement of the planner loop (any pred_horizon: T comes with x_init).  dtype=torch.float32: the same code in
-    the reference's own precision (what `ref32_err` of the trained-like cases is measured with)."""
+    the reference's own precision (what `ref32_err` of the trained-like cases is measured with).  fixed_order: the GEMMs without
+    BLAS (_FixedOrderF), so that every host reproduces the result bit for bit."""
     from oracle import torch32
     P = torch32.TorchParams(params, dtype=dtype)
     t = lambda a: None if a is None else torch.tensor(np.asarray(a), dtype=dtype)      # noqa: E731
-    return torch32.planner_sample(P, t(obs_cond), t(x_init), t(step_noise),
+    with (_fixed_order() if fixed_order else contextlib.nullcontext()):
+        return torch32.planner_sample(P, t(obs_cond), t(x_init), t(step_noise),
+                                      n_train=n_train, n_steps=n_steps, sampler=sampler).double().numpy()
+
+
+def idm_fn(params, trans, a_init, step_noise, n_train, n_steps, sampler, dtype=torch.float64, fixed_order=False):
+    from oracle import torch32
+    P = torch32.TorchParams(params, dtype=dtype)
+    t = lambda a: None if a is None else torch.tensor(np.asarray(a), dtype=dtype)      # noqa: E731
+    with (_fixed_order() if fixed_order else contextlib.nullcontext()):
+        return torch32.idm_sample(P, t(trans), t(a_init), t(step_noise),
                                   n_train=n_train, n_steps=n_steps, sampler=sampler).double().numpy()
-
-
-def idm_fn(params, trans, a_init, step_noise, n_train, n_steps, sampler, dtype=torch.float64):
-    from oracle import torch32
-    P = torch32.TorchParams(params, dtype=dtype)
-    t = lambda a: None if a is None else torch.tensor(np.asarray(a), dtype=dtype)      # noqa: E731
-    return torch32.idm_sample(P, t(trans), t(a_init), t(step_noise),
-                              n_train=n_train, n_steps=n_steps, sampler=sampler).double().numpy()
 
 
 DIMS = {"rm": (25, 7, cfgs.RM_LIFT), "aloha": (30, 14, cfgs.ALOHA_CUBE),
@@ -49,7 +121,7 @@ def planner_loop(sampler, n_steps, B=3, T=8, D=25):
                nz=g.standard_normal((n_steps, B, T, D)))
 
     def compute():
-        return dict(plan=planner_fn(planner_params(D=D), inp["cond"], inp["x0"], inp["nz"], 100, n_steps, sampler))
+        return dict(plan=planner_fn(planner_params(D=D), inp["cond"], inp["x0"], inp["nz"], 100, n_steps, sampler, fixed_order=True))
     return inp, compute
 
 
@@ -103,7 +175,7 @@ def idm_loop(cfg, sampler, n_steps, R=12):
     inp = dict(tr=g.uniform(-1, 1, (R, 2 * D)), a0=g.standard_normal((R, A)), nz=g.standard_normal((n_steps, R, A)))
 
     def compute():
-        return dict(act=idm_fn(idm_params(D=D, A=A), inp["tr"], inp["a0"], inp["nz"], 100, n_steps, sampler))
+        return dict(act=idm_fn(idm_params(D=D, A=A), inp["tr"], inp["a0"], inp["nz"], 100, n_steps, sampler, fixed_order=True))
     return inp, compute
 
 

@@ -172,7 +172,7 @@ def test_bench_multi_rank_path_on_one_gpu(config, batch):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--same-gpu", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--batch", str(batch), "--config", str(config)], cwd=root, capture_output=True, text=True,
+                        "--no-cpu-baseline", "--full", "--batch", str(batch), "--config", str(config)], cwd=root, capture_output=True, text=True,
                        timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])

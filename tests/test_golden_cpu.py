@@ -16,6 +16,8 @@ def test_fixture_loads_and_inputs_match_seed(name):
 
 @pytest.mark.parametrize("name", ["idm_loop_rm_ddpm100", "idm_loop_aloha_ddim50", "planner_loop_ddim50"])
 def test_oracle_reproduces_fixture(name):
+    """Bit for bit on every host: the loop fixtures are evaluated with the GEMMs in a fixed order, without BLAS, and with
+    correctly rounded float32 sqrt / sin / cos (tests/cases.py _fixed_order)."""
     fn, args = CASES[name]
     inp, compute = fn(*args)
     for k in inp:                                   # the fixture was generated from float32-rounded inputs

@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
 # 1. the driver's bench line
-python $R/bench.py > $OUT/bench.json 2> $OUT/bench.err
+python $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 # 2. per-kernel time of the same command (short run)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks_bench -o k -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/ks_bench.log 2>&1
 # 3. PMC passes of the same command (separate passes) + summary

@@ -8,7 +8,7 @@ for round in 1 2 3; do
   for cfg in 4 3; do
     for lib in default noguard; do
       extra=""; [ $lib = noguard ] && extra="--lib $NG"
-      line=$(python bench.py --config $cfg --steps 20 --warmup 3 --no-cpu-baseline $extra 2>/dev/null | tail -1)
+      line=$(python bench.py --config $cfg --steps 20 --warmup 3 --no-cpu-baseline --full $extra 2>/dev/null | tail -1)
       echo "round $round config $cfg $lib: $(echo "$line" | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], "plans/s", d["ms_per_step"], "ms/step", "shared-cond", d["config"].get("shared_cond_plans_per_s"))')"
     done
   done

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/prof_r06
 rm -rf $OUT; mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-python $R/bench.py > $OUT/bench.json 2> $OUT/bench.err
+python $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks_bench -o k -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/ks_bench.log 2>&1
 f=$(find $OUT/ks_bench -name "*kernel_trace.csv" | head -1)
 [ -n "$f" ] && python $R/tools/layer_times.py $f 30 256 > $OUT/layer_times_b256.txt 2>&1
@@ -15,7 +15,7 @@ bash $R/tools/pmc_passes.sh $OUT/pmc > $OUT/pmc.log 2>&1
 python $R/tools/pmc_summary.py $OUT/pmc $OUT/pmc_summary.json > $OUT/pmc_summary.txt 2>&1
 rm -rf $OUT/pmc
 for c in 2 3 4; do
-  python $R/bench.py --config $c --steps 20 --warmup 3 > $OUT/bench_config$c.json 2> $OUT/bench_config$c.err
+  python $R/bench.py --config $c --steps 20 --warmup 3 --full > $OUT/bench_config$c.json 2> $OUT/bench_config$c.err
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks_config$c -o k -- python $R/bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline > $OUT/ks_config$c.log 2>&1
 done
 python $R/bench.py --train > $OUT/bench_train.json 2> $OUT/bench_train.err
