@@ -149,6 +149,20 @@ LDP_API int ldp_agent_sample(ldp_handle* h, const float* obs_emb, int32_t obs_fr
                      float* action_out, const float* act_lo, const float* act_hi, int32_t act_dim,
                      int32_t act_mode, int32_t B, int32_t use_graph, void* stream);
 
+/* DPVAEAgent.sample_step (agent/dp_repr_agent.py:169-201) as ONE call and, with use_graph != 0, ONE captured hipGraph per (B bucket,
+ * n_steps, sampler, noise mode) -- the handle's planner module is the action U-Net (obs_dim = action_dim = A, global_cond_dim = obs_horizon * E):
+ *   cond   = get_obs_cond: [img_0 .. img_{oh-1}, low_0 .. low_{oh-1}]  (:76-85; NOT the per-frame interleave of ldp_agent_sample)
+ *   x      = the U-Net loop of ldp_plan_sample on (B, T, A) from x_init / N(0,I)  (:185-197)
+ *   action = unnormalize(x[:, :action_horizon]) (act_mode 0) or clip (act_mode 2); act_dim 0 = leave it normalised  (:199-200)
+ * obs_emb (B, obs_frames, E) per-frame [image latent (img_width floats) | low-dim (E - img_width)], only the first obs_horizon frames
+ * are read; the gather into the condition layout is the call's first kernel (the captured loop is ldp_plan_sample's, under its key).
+ * x_init (B,T,A) / x_noise (n_steps,B,T,A): explicit-noise parity inputs or NULL for the Philox streams keyed by (seed, row_offset + row).
+ * action_out (B, action_horizon, A). */
+LDP_API int ldp_policy_sample(ldp_handle* h, const float* obs_emb, int32_t obs_frames, int32_t obs_horizon, int32_t img_width,
+                      const float* x_init, const float* x_noise, uint64_t seed, int64_t row_offset, int32_t sampler,
+                      int32_t n_steps, float* action_out, const float* act_lo, const float* act_hi, int32_t act_dim,
+                      int32_t act_mode, int32_t B, int32_t use_graph, void* stream);
+
 /* -- StableVAE ----------------------------------------------------------------------------
  * FlaxAutoencoderKL.encode(x).latent_dist.mean   (call site agent/ldp_agent.py:55-60)
  * img (N, S, S, 3) NHWC already normalised to [-1,1] -> mean (N, S/32, S/32, latent_channels)
@@ -193,7 +207,8 @@ LDP_API int ldp_reduce_stats(const float* x, int64_t n, float* out4, void* strea
  * MFMA (csrc/train.hip).  Timesteps and noise are inputs (the reference draws them from its JAX key inside the traced step); the caller
  * evaluates the learning-rate schedule (optax evaluates it on the host-visible step count too).
  *
- * ldp_train_init: TrainStateEMA.create(params = the leaves last given with ldp_set_weight, tx = adam) -- moments zero, step 0.
+ * ldp_train_init: TrainStateEMA.create(params = the leaves last given with ldp_set_weight, tx = adam) -- moments zero, step 0; a module
+ *                 whose EMA is enabled (ldp_train_ema) has it re-seeded from the parameters.
  *                 Synchronises the device.  Call again after ldp_set_weight to restart from other parameters.
  * Streams: ldp_train_planner_grad and ldp_train_idm_grad write disjoint state (one workspace lane per module) and may be enqueued on two
  * different streams so that the two tapes overlap; each also forks its weight-gradient GEMMs to an internal side stream and joins it before
@@ -221,11 +236,18 @@ LDP_API int ldp_train_grad_norm(ldp_handle* h, int32_t modules, float* out, void
  * lr = schedule(count before the increment), evaluated by the caller. */
 LDP_API int ldp_train_apply(ldp_handle* h, int32_t module, float lr, float b1, float b2, float eps, void* stream);
 
+/* TrainStateEMA(ema_decay = decay, ema_params = params) (agent/dp_repr_agent.py:290-296): allocates the module's EMA arena and copies the
+ * current parameters into it.  From then on every ldp_train_apply of the module also writes
+ *   ema = ema * decay + p_new * (1 - decay)        (TrainStateEMA.apply_ema, utils/flax_utils.py:22-27; :155)
+ * in the same launch, and ldp_train_init re-seeds it from the parameters.  Synchronises `stream`. */
+LDP_API int ldp_train_ema(ldp_handle* h, int32_t module, float decay, void* stream);
+
 /* TrainState.step of a module: *out = the count (number of ldp_train_apply calls since init); set_to >= 0 overwrites it first (checkpoint
  * restore). */
 LDP_API int ldp_train_step_count(ldp_handle* h, int32_t module, int64_t set_to, int64_t* out);
 
-/* One leaf of a module's state, Flax layout, host float32: which = 0 parameters, 1 gradients, 2 Adam mu, 3 Adam nu.  `path` is the Flax path
+/* One leaf of a module's state, Flax layout, host float32: which = 0 parameters, 1 gradients, 2 Adam mu, 3 Adam nu, 4 EMA of the
+ * parameters (after ldp_train_ema).  `path` is the Flax path
  * inside the module ("ConditionalResidualBlock1D_3/Conv1dBlock_0/Conv_0/kernel").  Both synchronise `stream`.
  * replaces: reading / restoring planner_state / idm_state (params, opt_state) in train_bc.py:203-240. */
 LDP_API int ldp_train_read(ldp_handle* h, int32_t module, int32_t which, const char* path, float* host_out, int64_t numel, void* stream);
@@ -243,6 +265,8 @@ LDP_API int ldp_train_arena(ldp_handle* h, int32_t module, int32_t which, float*
 /* Make the sampling path use the trained parameters: master parameters -> the handle's weight store -> ldp_finalize of the listed
  * modules (what train_bc.py:143-155 relies on when it evaluates the agent it is training).  Synchronises `stream`. */
 LDP_API int ldp_train_publish(ldp_handle* h, int32_t modules, void* stream);
+/* The same with the EMA arena (use_ema: agent/dp_repr_agent.py:176-179).  Synchronises `stream`. */
+LDP_API int ldp_train_publish_ema(ldp_handle* h, int32_t modules, void* stream);
 
 /* -- unit-testable primitives (one Conv1dBlock / sampling conv of the U-Net) ----------------
  * y = [FiLM](Mish(GroupNorm8(Conv1d_k5_pad2(x) + b)))  with kernel in Flax layout on the host.

@@ -82,6 +82,8 @@ int assemble_plan_launch(const float* state, const float* obs_last, float* plan,
                          int B, int T, int D, int DP, int ah, hipStream_t s);
 int gather_obs_launch(const float* obs_emb, float* cond, float* obs_last, int B, int H, int D, int oh,
                       hipStream_t s);
+int gather_dp_cond_launch(const float* obs_emb, float* cond, int B, int H, int E, int oh, int w, hipStream_t s);
+int head_rows_launch(const float* src, float* dst, int B, int T, int rows, int d, int dp, hipStream_t s);
 int mean_sq_diff_launch(const float* a, const float* b, int64_t n, float* out, hipStream_t s);
 int reduce_stats_launch(const float* x, int64_t n, float* out4, hipStream_t s);      // out4 = {min, max, mean, population std}
 struct AbarTable { float v[256]; };                                               // float32 cumprod of (1 - beta), passed by value

@@ -213,6 +213,41 @@ int gather_obs_launch(const float* obs_emb, float* cond, float* obs_last, int B,
   return LDP_OK;
 }
 
+// DPVAEAgent.get_obs_cond (agent/dp_repr_agent.py:76-85): obs_emb (B, H, E) per-frame [image latent (w) | low-dim (E - w)] ->
+// cond (B, oh*E) = [img_0 .. img_{oh-1}, low_0 .. low_{oh-1}] (image features of every frame first, then the low-dim vectors)
+__global__ void gather_dp_cond_kernel(const float* __restrict__ obs_emb, float* __restrict__ cond, int B, int H, int E, int oh, int w) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * oh * E) return;
+  const int b = (int)(i / (oh * E)), j = (int)(i % (oh * E));
+  const int lw = E - w;
+  int f, c;
+  if (j < oh * w) { f = j / w; c = j - f * w; }
+  else { const int k = j - oh * w; f = k / lw; c = w + (k - f * lw); }
+  cond[i] = obs_emb[((size_t)b * H + f) * E + c];
+}
+int gather_dp_cond_launch(const float* obs_emb, float* cond, int B, int H, int E, int oh, int w, hipStream_t s) {
+  const int64_t n = (int64_t)B * oh * E;
+  hipLaunchKernelGGL(gather_dp_cond_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, obs_emb, cond, B, H, E, oh, w);
+  LDP_HIP(hipGetLastError());
+  return LDP_OK;
+}
+
+// dst (B, rows, d) <- the first `rows` of every sample's T rows of the padded loop state src (B, T, dp)
+__global__ void head_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, int B, int T, int rows, int d, int dp) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * rows * d) return;
+  const int64_t r = i / d;
+  const int c = (int)(i - r * d);
+  const int b = (int)(r / rows), t = (int)(r - (int64_t)b * rows);
+  dst[i] = src[((size_t)b * T + t) * dp + c];
+}
+int head_rows_launch(const float* src, float* dst, int B, int T, int rows, int d, int dp, hipStream_t s) {
+  const int64_t n = (int64_t)B * rows * d;
+  hipLaunchKernelGGL(head_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, B, T, rows, d, dp);
+  LDP_HIP(hipGetLastError());
+  return LDP_OK;
+}
+
 int set_seed_launch(uint64_t* seed_dev, uint64_t seed, int64_t row_offset, uint64_t epoch, hipStream_t s) {
   hipLaunchKernelGGL(set_seed_kernel, dim3(1), dim3(1), 0, s, seed_dev, seed, (uint64_t)row_offset, epoch);
   LDP_HIP(hipGetLastError());

@@ -1005,8 +1005,12 @@ __global__ __launch_bounds__(256) void colsum_jobs2_kernel(const ColJobs js, con
 //   p += -lr * (mu / bc1) / (sqrt(nu / bc2) + eps),  bc = 1 - b^count   (oracle/train.py adam_apply)
 // One work-group per 1024-element stripe (sumsq1_kernel's stripes and reduction order): besides the update it leaves the stripe's sum of squared
 // gradients in part[block], so that the global norm of the step (a metric: agent/ldp_agent.py:253, nothing is clipped) costs no second pass over the arena.
+// kEma (a module with ldp_train_ema): TrainStateEMA.apply_ema (utils/flax_utils.py:22-27) in the same pass, e = e * d + p_new * (1 - d); the
+// kEma = false instantiation is the code every other caller has always run (same P / M / V / part[] bits).
+template <bool kEma>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ mu, float* __restrict__ nu, long long n, float lr,
-                                                   float b1, float b2, float eps, float bc1, float bc2, float* __restrict__ part) {
+                                                   float b1, float b2, float eps, float bc1, float bc2, float* __restrict__ part,
+                                                   float* __restrict__ ema, float ema_d, float ema_1md) {
   __shared__ float red[4];
   const long long i0 = (long long)blockIdx.x * 1024 + threadIdx.x;
   float s = 0.0f;
@@ -1020,7 +1024,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
       const float v = (1.0f - b2) * (gi * gi) + b2 * nu[i];
       mu[i] = m;
       nu[i] = v;
-      p[i] = p[i] + (-lr) * ((m / bc1) / (sqrtf(v / bc2) + eps));
+      const float pn = p[i] + (-lr) * ((m / bc1) / (sqrtf(v / bc2) + eps));
+      p[i] = pn;
+      if constexpr (kEma) ema[i] = ema[i] * ema_d + pn * ema_1md;
     }
   }
   s = wsum(s);
@@ -1076,6 +1082,9 @@ struct Module {
   std::map<std::string, int> index;
   size_t total = 0;               // floats (each leaf padded to a multiple of 64)
   DevBuf P, G, M, V, gpart;       // params, grads, Adam moments, sum-of-squares partials
+  DevBuf E;                       // EMA of the parameters (ldp_train_ema), same layout as P
+  bool ema_on = false;
+  float ema_decay = 0.0f;
   bool gpart_fresh = false;       // gpart holds the stripes' sums of squares of the CURRENT gradients (left by ldp_train_apply)
   long long step = 0;
   bool ready = false;
@@ -2156,6 +2165,10 @@ int ldp_train_init(ldp_handle* h, int32_t modules, void* stream) {
     LDP_HIP(hipMemset(m->G.p, 0, m->total * 4));
     LDP_HIP(hipMemset(m->M.p, 0, m->total * 4));
     LDP_HIP(hipMemset(m->V.p, 0, m->total * 4));
+    if (m->ema_on) {                                                     // TrainStateEMA.create(..., ema_params=params)
+      LDP_TRY(m->E.alloc(m->total * 4));
+      LDP_HIP(hipMemcpy(m->E.p, m->P.p, m->total * 4, hipMemcpyDeviceToDevice));
+    }
     m->step = 0;
     m->gpart_fresh = false;
     m->ready = true;
@@ -2209,8 +2222,15 @@ int ldp_train_apply(ldp_handle* h, int32_t module, float lr, float b1, float b2,
   LDP_TRY(need_module(h, module, &m));
   const long long count = m->step + 1;
   const float bc1 = (float)(1.0 - std::pow((double)b1, (double)count)), bc2 = (float)(1.0 - std::pow((double)b2, (double)count));
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((m->total + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, m->P.f(), m->G.f(), m->M.f(), m->V.f(),
-                     (long long)m->total, lr, b1, b2, eps, bc1, bc2, m->gpart.f());
+  const dim3 grid((unsigned)((m->total + 1023) / 1024));
+  if (m->ema_on) {
+    const float d = m->ema_decay, omd = (float)(1.0 - (double)m->ema_decay);
+    hipLaunchKernelGGL(adam_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, m->P.f(), m->G.f(), m->M.f(), m->V.f(),
+                       (long long)m->total, lr, b1, b2, eps, bc1, bc2, m->gpart.f(), m->E.f(), d, omd);
+  } else {
+    hipLaunchKernelGGL(adam_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, m->P.f(), m->G.f(), m->M.f(), m->V.f(),
+                       (long long)m->total, lr, b1, b2, eps, bc1, bc2, m->gpart.f(), nullptr, 0.0f, 0.0f);
+  }
   LDP_HIP(hipGetLastError());
   m->gpart_fresh = true;
   m->step = count;
@@ -2225,16 +2245,25 @@ int ldp_train_step_count(ldp_handle* h, int32_t module, int64_t set_to, int64_t*
   return LDP_OK;
 }
 
+// which: 0 params, 1 grads, 2 Adam mu, 3 Adam nu, 4 EMA of the params (a module with ldp_train_ema only)
+static int state_buf(Module* m, int32_t module, int32_t which, DevBuf** out) {
+  if (which < 0 || which > 4) return fail(LDP_EINVAL, "which must be 0 (params), 1 (grads), 2 (mu), 3 (nu) or 4 (EMA)");
+  if (which == 4 && !m->ema_on) return fail(LDP_ESTATE, "module %d keeps no EMA (ldp_train_ema was not called)", module);
+  *out = which == 0 ? &m->P : which == 1 ? &m->G : which == 2 ? &m->M : which == 3 ? &m->V : &m->E;
+  return LDP_OK;
+}
+
 static int leaf_io(ldp_handle* h, int32_t module, int32_t which, const char* path, float* host, int64_t numel, bool write, void* stream) {
   Module* m = nullptr;
   LDP_TRY(need_module(h, module, &m));
   if (!path || !host) return fail(LDP_EINVAL, "bad argument");
-  if (which < 0 || which > 3) return fail(LDP_EINVAL, "which must be 0 (params), 1 (grads), 2 (mu) or 3 (nu)");
+  DevBuf* bp = nullptr;
+  LDP_TRY(state_buf(m, module, which, &bp));
   auto it = m->index.find(path);
   if (it == m->index.end()) return fail(LDP_EKEY, "module %d has no leaf '%s'", module, path);
   const Leaf& l = m->leaves[it->second];
   if (numel != (int64_t)l.taps * l.rows * l.cols) return fail(LDP_EINVAL, "leaf '%s' has %lld elements, caller passed %lld", path, (long long)l.taps * l.rows * l.cols, (long long)numel);
-  DevBuf& buf = which == 0 ? m->P : which == 1 ? m->G : which == 2 ? m->M : m->V;
+  DevBuf& buf = *bp;
   LDP_HIP(hipStreamSynchronize((hipStream_t)stream));
   std::vector<float> img(l.size_p(), 0.0f);
   if (write) {
@@ -2260,15 +2289,17 @@ int ldp_train_arena(ldp_handle* h, int32_t module, int32_t which, float** dev_ou
   Module* m = nullptr;
   LDP_TRY(need_module(h, module, &m));
   if (!dev_out || !numel_out) return fail(LDP_EINVAL, "bad argument");
-  if (which < 0 || which > 3) return fail(LDP_EINVAL, "which must be 0 (params), 1 (grads), 2 (mu) or 3 (nu)");
-  DevBuf& buf = which == 0 ? m->P : which == 1 ? m->G : which == 2 ? m->M : m->V;
+  DevBuf* bp = nullptr;
+  LDP_TRY(state_buf(m, module, which, &bp));
+  DevBuf& buf = *bp;
   if (which == 1) m->gpart_fresh = false;                    // (the caller may write the gradients: the all-reduce of a data-parallel step)
   *dev_out = buf.f();
   *numel_out = (int64_t)m->total;
   return LDP_OK;
 }
 
-int ldp_train_publish(ldp_handle* h, int32_t modules, void* stream) {
+// master parameters (or their EMA) -> the handle's weight store -> finalize of the listed modules
+static int publish(ldp_handle* h, int32_t modules, bool ema, void* stream) {
   if (!h) return fail(LDP_EINVAL, "null handle");
   if (!(modules & 3) || (modules & ~3)) return fail(LDP_EINVAL, "modules must be a mask of 1 (planner) and 2 (idm)");
   hipStream_t s = (hipStream_t)stream;
@@ -2278,9 +2309,10 @@ int ldp_train_publish(ldp_handle* h, int32_t modules, void* stream) {
     if (!(modules & bit)) continue;
     Module* m = nullptr;
     LDP_TRY(need_module(h, bit, &m));
+    if (ema && !m->ema_on) return fail(LDP_ESTATE, "module %d keeps no EMA (ldp_train_ema was not called)", bit);
     const char* prefix = bit == 1 ? "planner/" : "idm/";
     std::vector<float> img(m->total);
-    LDP_HIP(hipMemcpy(img.data(), m->P.p, m->total * 4, hipMemcpyDeviceToHost));
+    LDP_HIP(hipMemcpy(img.data(), ema ? m->E.p : m->P.p, m->total * 4, hipMemcpyDeviceToHost));
     for (const Leaf& l : m->leaves) {
       HostTensor t;
       t.shape = l.shape;
@@ -2293,6 +2325,24 @@ int ldp_train_publish(ldp_handle* h, int32_t modules, void* stream) {
   if (modules & 1) LDP_TRY(planner_finalize(h, s));
   if (modules & 2) LDP_TRY(idm_finalize(h, s));
   LDP_HIP(hipStreamSynchronize(s));
+  return LDP_OK;
+}
+
+int ldp_train_publish(ldp_handle* h, int32_t modules, void* stream) { return publish(h, modules, false, stream); }
+
+int ldp_train_publish_ema(ldp_handle* h, int32_t modules, void* stream) { return publish(h, modules, true, stream); }
+
+int ldp_train_ema(ldp_handle* h, int32_t module, float decay, void* stream) {
+  Module* m = nullptr;
+  LDP_TRY(need_module(h, module, &m));
+  if (!(decay >= 0.0f && decay <= 1.0f)) return fail(LDP_EINVAL, "ema decay must lie in [0, 1], got %g", (double)decay);
+  hipStream_t s = (hipStream_t)stream;
+  LDP_HIP(hipSetDevice(h->cfg.device));
+  LDP_TRY(m->E.alloc(m->total * 4));
+  LDP_HIP(hipMemcpyAsync(m->E.p, m->P.p, m->total * 4, hipMemcpyDeviceToDevice, s));
+  LDP_HIP(hipStreamSynchronize(s));
+  m->ema_on = true;
+  m->ema_decay = decay;
   return LDP_OK;
 }
 

@@ -1,0 +1,384 @@
+"""DPVAEAgent -- the reference's baseline (agent/dp_repr_agent.py, hydra target agent.dp_vae_agent.DPVAEAgent) on the HIP engine.
+
+A diffusion policy over ACTIONS conditioned on frozen StableVAE latents: one ConditionalUnet1D (input_dim = action_dim) denoises a
+(B, pred_horizon, A) action chunk given the observation condition of `get_obs_cond`.  Everything heavy runs in libldp_hip.so: the
+StableVAE encoder (ldp_vae_encode), the sampling loop with its condition gather and action un-normalisation as one call / one captured
+graph (ldp_policy_sample), the exact-fp32 training tape of the U-Net (ldp_train_planner_grad) and Adam with the parameter EMA fused into the
+same launch (ldp_train_ema / ldp_train_apply).
+
+Same names, argument meaning and return structure as the reference class: `create`, `.config`, `.replace`, `.planner_state` (`.params`,
+`.ema_params`, `.step`, `.replace(params=, ema_params=)`), `vae_encode`, `vae_decode`, `get_obs_cond`, `sample`, `update`, `get_metrics`,
+`get_params`.  rng / noise conventions are LDPAgent's (int seed, uint32[2] key or torch.Generator; explicit noise for parity runs).
+
+Like LDPAgent, only the NEWEST trained state's parameters and EMA can be read back (both stay in the engine's arenas until fetched): keep
+`agent = agent.update(...)[0]` as train_bc.py:107 does.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import weights as W
+from .agent import (LATENT_SHAPES, LDPAgent, ParamState, _Elem, _HostScalar, _as_flat, _get, _norm_entry, _philox_normal, _seed_of,
+                    _versions, load_pretrained_vae)
+from .arrays import DeviceArray
+from .engine import HipEngine
+
+
+class DPState(ParamState):
+    """flax_utils.TrainStateEMA (utils/flax_utils.py:18-27) as DPVAEAgent's callers see it: ParamState plus an EMA tree with a version
+    token of its own (`ema_version`), so the engine's single sampling slot always knows which of the two weight sets it holds.  The EMA
+    of a trained state lives in the engine's EMA arena and is fetched on first access, like its parameters."""
+
+    def __init__(self, params=None, ema_params=None, step: int = 0, version: Optional[int] = None, opt_state=None, _fetch=None,
+                 ema_version: Optional[int] = None, _ema_fetch=None, ema_is_params: bool = False):
+        self._ema = None
+        super().__init__(params, ema_params, step, version, opt_state, _fetch)
+        self.ema_version = next(_versions) if ema_version is None else ema_version
+        self._ema_fetch = _ema_fetch
+        # the EMA equals the parameters (TrainStateEMA.create, load_snapshot): restoring the state re-seeds the engine's EMA arena from them
+        self.ema_is_params = bool(ema_is_params)
+
+    @property
+    def ema_params(self):
+        if self._ema is None and self._ema_fetch is not None:
+            self._ema = self._ema_fetch()
+        if self._ema is None and self.ema_is_params:
+            return self.params
+        return self._ema
+
+    @ema_params.setter
+    def ema_params(self, value):
+        self._ema = value
+
+    def replace(self, **kw):
+        new = DPState(self._params, None, self.step, self.version, self._opt_state, self._fetch, self.ema_version, self._ema_fetch,
+                      self.ema_is_params)
+        new._ema = self._ema
+        same = "params" in kw and "ema_params" in kw and kw["ema_params"] is kw["params"]
+        if "params" in kw and "ema_params" not in kw and self.ema_is_params:
+            new._ema = self.params                      # the EMA stays what it was: the OLD parameters
+        if "params" in kw:
+            new.version = kw.pop("version", next(_versions))
+            new._params = _as_flat(kw.pop("params"))
+            new._fetch = None
+            new._opt_state = None if "opt_state" not in kw else new._opt_state
+            new.ema_is_params = False
+        if "ema_params" in kw:
+            e = kw.pop("ema_params")
+            new.ema_version = kw.pop("ema_version", next(_versions))
+            new._ema_fetch = None
+            new._ema = None if same or e is None else _as_flat(e)
+            new.ema_is_params = same
+        if "opt_state" in kw:
+            o = kw.pop("opt_state")
+            new._opt_state = None if o is None else dict(mu=_as_flat(o["mu"]), nu=_as_flat(o["nu"]), count=int(o.get("count", new.step)))
+            new.version = next(_versions) if new._fetch is None else new.version
+        for k in ("step", "version", "ema_version"):
+            if k in kw:
+                setattr(new, k, int(kw.pop(k)) if k == "step" else kw.pop(k))
+        if kw:
+            raise AttributeError(f"DPState has no field(s) {sorted(kw)}")
+        return new
+
+
+def dp_obs_cond(frame_emb: torch.Tensor, obs_horizon: int, img_width: int) -> torch.Tensor:
+    """get_obs_cond (agent/dp_repr_agent.py:76-85) from per-frame [image latent | low-dim] rows (B, H, E): the image features of frames
+    0..oh-1 first, then their low-dim vectors -> (B, oh * E)."""
+    x = frame_emb[:, :obs_horizon]
+    B = x.shape[0]
+    return torch.cat([x[..., :img_width].reshape(B, -1), x[..., img_width:].reshape(B, -1)], dim=-1).contiguous()
+
+
+class DPVAEAgent(LDPAgent):
+    """The fault protocol (_record / _guarded), pre/post-processing and the VAE calls are LDPAgent's; the planner slot of the engine holds
+    the action U-Net."""
+
+    def __init__(self, planner_state, vae_params, obs_normalization, config, engine: Optional[HipEngine], planner_spec, vae_spec, device,
+                 lr_schedule=None):
+        super().__init__(planner_state, None, vae_params, obs_normalization, True, False, 1, 0, config, engine, planner_spec, None,
+                         vae_spec, device, lr_schedules={"planner": lr_schedule} if lr_schedule is not None else None)
+
+    # ---------------------------------------------------------------------------------------------
+    @classmethod
+    def create(cls, rng, batch, shape_meta,
+               # Hydra config (agent/dp_repr_agent.yaml)
+               name, planner, lowdim_obs, rgb_obs, obs_normalization,
+               obs_horizon, pred_horizon, action_horizon, n_diffusion_steps,
+               lr, end_lr, warmup_steps, decay_steps,
+               random_shift, use_ema, planner_ema_decay,
+               vae_pretrain_path, vae_feature_dim,
+               device=None, vae_params=None, exclusive_gpu=True):
+        """agent/dp_repr_agent.py:225-307.  `batch` is accepted for signature parity (the reference traces shapes from it)."""
+        lowdim_obs, rgb_obs = list(lowdim_obs), list(rgb_obs)
+        if len(rgb_obs) != 1:
+            raise NotImplementedError(f"rgb_obs={rgb_obs}: the DP condition is built for exactly one camera (multi-camera "
+                                      "conditioning is not built)")
+        if vae_feature_dim is None or int(vae_feature_dim) not in LATENT_SHAPES:
+            raise NotImplementedError(f"vae_feature_dim={vae_feature_dim}: the latent shapes of agent/dp_repr_agent.py:56-69 are "
+                                      f"{sorted(LATENT_SHAPES)} (2x2x4, 2x2x8, 3x3x4, 4x4x4)")
+        side, latent_ch = LATENT_SHAPES[int(vae_feature_dim)]
+        image_size = 32 * side
+        lowdim_dim = sum(int(np.prod(shape_meta["all_shapes"][k])) for k in lowdim_obs)
+        obs_dim = lowdim_dim + int(vae_feature_dim) * len(rgb_obs)         # per frame (:236-239)
+        action_dim = int(shape_meta["ac_dim"])
+        if action_dim > 128:
+            raise NotImplementedError(f"action_dim={action_dim}: the U-Net's first conv is packed for inputs of at most 128 features")
+        down_dims = tuple(int(d) for d in _get(planner, "down_dims", (256, 512, 1024)))
+        pspec = W.PlannerSpec(input_dim=action_dim, global_cond_dim=int(obs_horizon) * obs_dim,   # Dense infers the width it is fed
+                              diffusion_step_embed_dim=int(_get(planner, "diffusion_step_embed_dim", 256)),
+                              down_dims=down_dims, kernel_size=int(_get(planner, "kernel_size", 5)),
+                              n_groups=int(_get(planner, "n_groups", 8)), downsample=bool(_get(planner, "downsample", True)))
+        if not pspec.downsample:
+            raise NotImplementedError("downsample=False U-Nets are not built")
+        if any(d < 256 or d % 128 for d in down_dims) or pspec.kernel_size != 5 or pspec.n_groups != 8:
+            raise NotImplementedError(f"planner down_dims={down_dims} kernel_size={pspec.kernel_size} n_groups="
+                                      f"{pspec.n_groups}: the MFMA conv tiles are built for kernel_size 5, 8 groups and "
+                                      "levels that are multiples of 128 channels and at least 256 wide")
+        T = int(pred_horizon)
+        if T % (1 << (len(down_dims) - 1)) != 0:
+            raise ValueError(f"pred_horizon {T}: the {len(down_dims)}-level ConditionalUnet1D needs a multiple of {1 << (len(down_dims) - 1)}")
+        if not 1 <= int(action_horizon) <= T:
+            raise ValueError(f"action_horizon {action_horizon} must lie in 1..pred_horizon {T}")
+        decay = float(planner_ema_decay)
+        if not 0.0 <= decay <= 1.0:
+            raise ValueError(f"planner_ema_decay={decay} must lie in [0, 1]")
+        seed = _seed_of(rng)
+        params = W.init_planner_params(pspec, seed=seed * 3 + 1, perturb=False)
+        planner_state = DPState(params, None, ema_is_params=True)           # TrainStateEMA.create(..., ema_params=params)
+        if vae_params is None and vae_pretrain_path is not None:
+            vae_params = load_pretrained_vae(str(vae_pretrain_path))
+        vae_params = _as_flat(vae_params) if vae_params is not None else None
+        config = dict(n_diffusion_steps=int(n_diffusion_steps), lowdim_obs=lowdim_obs, rgb_obs=rgb_obs, obs_horizon=int(obs_horizon),
+                      name=name, action_dim=action_dim, pred_horizon=T, action_horizon=int(action_horizon),
+                      random_shift=random_shift, use_ema=bool(use_ema), vae_feature_dim=int(vae_feature_dim),
+                      obs_dim=obs_dim, planner_ema_decay=decay)
+        norm = {"obs": {k: _norm_entry(v) for k, v in dict(obs_normalization["obs"]).items()}}
+        if "actions" in obs_normalization:
+            norm["actions"] = _norm_entry(obs_normalization["actions"])
+        if not torch.cuda.is_available():
+            from ._lib import LDPHipUnavailable
+            raise LDPHipUnavailable("no HIP device visible: DPVAEAgent has no CPU fallback")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        engine = HipEngine(obs_dim=action_dim, action_dim=action_dim, global_cond_dim=pspec.global_cond_dim, pred_horizon=T,
+                           action_horizon=int(action_horizon), down_dims=down_dims, kernel_size=pspec.kernel_size, n_groups=pspec.n_groups,
+                           step_embed_dim=pspec.diffusion_step_embed_dim, planner_train_steps=int(n_diffusion_steps),
+                           idm_train_steps=int(n_diffusion_steps), image_size=image_size, vae_latent_channels=latent_ch, device=dev)
+        if not exclusive_gpu:
+            engine.set_option("safe_mode", 1)
+        from .schedule import warmup_cosine_decay_schedule
+        sched = None
+        if lr is not None and warmup_steps is not None and decay_steps is not None:
+            sched = warmup_cosine_decay_schedule(float(end_lr), float(lr), int(warmup_steps), int(decay_steps), float(end_lr))
+        return cls(planner_state, vae_params, norm, config, engine, pspec, W.VAESpec(latent_channels=latent_ch), dev, lr_schedule=sched)
+
+    # ---------------------------------------------------------------------------------------------
+    def get_params(self):
+        """agent/dp_repr_agent.py:220-223."""
+        return dict(planner_params=self.planner_state.params, planner_ema_params=self.planner_state.ema_params)
+
+    def _sync_weights(self, need_vae=False, use_ema=None):
+        """The sampling slot must hold THIS agent's parameters -- or their EMA when use_ema (:176-179): each set has its own token."""
+        eng, st = self._engine, self.planner_state
+        use_ema = bool(self.config["use_ema"]) if use_ema is None else use_ema
+        want = st.ema_version if use_ema else st.version
+        up, ver = {}, {}
+        if eng.loaded["planner"] != want:
+            if not use_ema and eng.train_token.get("planner") == st.version:
+                eng.train_publish(["planner"], versions={"planner": want})
+            elif use_ema and eng.train_ema_token.get("planner") == st.ema_version:
+                eng.train_publish_ema(["planner"], versions={"planner": want})
+            else:
+                tree = st.ema_params if use_ema else st.params
+                W.check_params(tree, self._planner_shapes())
+                up["planner"], ver["planner"] = tree, want
+        if need_vae and eng.loaded["vae"] != self._vae_version:
+            if self.vae_params is None:
+                raise ValueError("raw image observations need VAE weights (vae_pretrain_path / vae_params)")
+            up["vae"], ver["vae"] = self.vae_params, self._vae_version
+        if up:
+            eng.load_params(**up, versions=ver)
+
+    # ---- agent/dp_repr_agent.py:76-85 ---------------------------------------------------------------
+    def _frame_emb(self, obs) -> torch.Tensor:
+        """Per-frame [image latent | low-dim] rows (B, H, E): what LDPAgent.get_obs_cond builds for one camera."""
+        return LDPAgent.get_obs_cond(self, obs).contiguous()
+
+    def get_obs_cond(self, batch):
+        """(B, obs_horizon * E) in the DP layout: the image latents of frames 0..oh-1, then their low-dim vectors."""
+        return dp_obs_cond(self._frame_emb(batch), self.config["obs_horizon"], self.config["vae_feature_dim"])
+
+    # ---- agent/dp_repr_agent.py:160-201 -------------------------------------------------------------
+    def sample(self, batch, eval_rng, noise=None, row_offset=0, sampler="ddpm", n_steps=None):
+        """-> (action (B, action_horizon, A) un-normalised, {}).  noise: optional dict(x_init (B, T, A), x_noise (S, B, T, A)) for
+        explicit-noise parity runs; row_offset: global index of the first row (the Philox stream of a row does not depend on sharding)."""
+        seed = _seed_of(eval_rng)
+        cfg = self.config
+        nz = noise or {}
+
+        def run():
+            self._sync_weights()
+            nb = self._postprocess(batch)
+            obs = self._vae_encode_t(nb["obs"])
+            lo, hi, mode = self._action_bounds()
+            return [self._engine.policy_sample(self._frame_emb(obs), cfg["obs_horizon"], cfg["vae_feature_dim"], x_init=nz.get("x_init"),
+                                               x_noise=nz.get("x_noise"), seed=seed, row_offset=row_offset, sampler=sampler,
+                                               n_steps=n_steps, action_bounds=(lo, hi), action_mode=mode)]
+        rec = self._record(run)
+        res = self._guarded(run)
+        rec.seqs = self._seqs()
+        return DeviceArray(res[0], record=rec), {}
+
+    def get_action(self, batch, eval_rng, **kw):
+        return self.sample(batch, eval_rng, **kw)[0]
+
+    # the LDP-only surface does not exist on the reference's DP class
+    def sample_viz(self, *a, **k):
+        raise NotImplementedError("DPVAEAgent has no sample_viz (agent/dp_repr_agent.py samples actions only)")
+
+    def sample_action(self, *a, **k):
+        raise NotImplementedError("DPVAEAgent has no sample_action (eval_bc.py:129-131 calls sample for dp agents)")
+
+    def sample_action_from_plan(self, *a, **k):
+        raise NotImplementedError("DPVAEAgent has no sample_action_from_plan")
+
+    def update_mixed(self, *a, **k):
+        raise NotImplementedError("DPVAEAgent has no update_mixed")
+
+    # ---- agent/dp_repr_agent.py:101-158: the training step ------------------------------------------------------------------------------
+    def _gates(self, step):
+        """update() trains the U-Net on every step (no gating, :135-144): (use_planner, use_idm) for dist.update_sharded."""
+        return True, False
+
+    def update(self, batch, rng, step, noise=None):
+        """-> (new agent, metrics): jax.grad(loss), one optax.adam step, then the EMA (:146-158) -- csrc/train.hip, one fused launch for
+        Adam and the EMA.  rng: seed of the timesteps (host PCG64) and of the noise (device Philox); noise: optional explicit
+        dict(t (B,), noise (B, T, A)) for parity runs."""
+        if self.config.get("random_shift", 0) and float(self.config["random_shift"]) > 0:
+            raise NotImplementedError("random_shift > 0 shifts the rgb keys as raw (B, T, H, W, C) images (agent/dp_repr_agent.py:135-144); "
+                                      "a latent training batch holds none")
+        return self._update_step(batch, None, rng, True, False, noise)
+
+    def _train_sync(self, name, state, shapes, eng=None):
+        """The engine's arenas must hold THIS state: parameters, Adam moments and the EMA (enabled with the agent's decay; a (re)load
+        re-seeds it from the parameters, then a distinct EMA tree is written over it)."""
+        eng = self._engine if eng is None else eng
+        if eng.train_token.get(name) == state.version and eng.train_ema_token.get(name) == state.ema_version:
+            return
+        W.check_params(state.params, shapes)
+        ema = None if state.ema_is_params else state.ema_params          # (read before the arenas are overwritten)
+        o = state.opt_state
+        eng.train_load(name, state.params, mu=None if o is None else o["mu"], nu=None if o is None else o["nu"], step=state.step,
+                       token=state.version)
+        decay = self.config["planner_ema_decay"]
+        if eng.ema_decay.get(name) != decay:
+            eng.train_ema(name, decay)
+        if ema is not None:
+            W.check_params(ema, shapes)
+            eng.train_write(name, eng.TRAIN_EMA, ema)
+        eng.train_ema_token[name] = state.ema_version
+
+    def _trained_state(self, name, old, shapes, eng=None):
+        eng = self._engine if eng is None else eng
+        token, etoken = next(_versions), next(_versions)
+        eng.train_token[name] = token
+        eng.train_ema_token[name] = etoken
+        which = {"params": eng.TRAIN_PARAMS, "mu": eng.TRAIN_MU, "nu": eng.TRAIN_NU, "ema": eng.TRAIN_EMA}
+
+        def fetch(what):
+            if eng.train_token.get(name) != token or (what == "ema" and eng.train_ema_token.get(name) != etoken):
+                raise RuntimeError(f"this {name} state was superseded by a later update(): its buffers were donated to the next step "
+                                   "(keep the agent that update() returned, as train_bc.py:107 does)")
+            return eng.train_read(name, which[what], shapes)
+        return DPState(None, None, old.step + 1, token, None, fetch, etoken, lambda: fetch("ema"))
+
+    def _update_step(self, batch, mixed_batch, rng, use_planner, use_idm, noise, shard=None):
+        """shard (dist.update_sharded): dict(group, rows=(lo, n)) -- `batch` holds rows [lo, lo + B) of a global batch of n: global-row
+        timesteps and noise, a B / n weighted loss, ONE all-reduce of the gradient arena, Adam and the EMA replicated."""
+        if mixed_batch is not None or use_idm:
+            raise NotImplementedError("DPVAEAgent trains one network on one batch")
+        if self._lr_schedules.get("planner") is None:
+            raise ValueError("update() needs the optimiser settings of DPVAEAgent.create (lr, end_lr, warmup_steps, decay_steps)")
+        cfg, eng = self.config, self._engine
+        seed = _seed_of(rng)
+        nz = noise or {}
+        nb = self._postprocess(batch)
+        if "actions" not in nb:
+            raise KeyError("update needs batch['actions'] (utils/data_utils.py:73)")
+        cond = self.get_obs_cond(nb["obs"])
+        action = nb["actions"].contiguous()
+        B, T, A = action.shape
+        if T != cfg["pred_horizon"] or A != cfg["action_dim"]:
+            raise ValueError(f"batch['actions'] has shape {tuple(action.shape)}: the U-Net denoises (B, pred_horizon={cfg['pred_horizon']}, "
+                             f"action_dim={cfg['action_dim']}) chunks (agent/dp_repr_agent.py:102-110)")
+        lo, n = (0, B) if shard is None else shard["rows"]
+        w = np.float32(B) / np.float32(n)
+        st = self.planner_state
+        self._train_sync("planner", st, self._planner_shapes())
+        stats = [eng.reduce_stats(cond), eng.reduce_stats(action)] + [eng.reduce_stats(nb["obs"][k]) for k in nb["obs"]]
+        hg = np.random.Generator(np.random.PCG64(seed & (2**63 - 1)))
+        t = nz.get("t")
+        t = np.asarray(hg.integers(0, int(cfg["n_diffusion_steps"]), size=n) if t is None else t).reshape(-1)
+        if len(t) == n and n != B:
+            t = t[lo:lo + B]
+        eps = nz.get("noise")
+        if eps is not None:
+            eps = self._t(eps[lo:lo + B] if len(eps) == n and n != B else eps)
+        else:
+            eps = _philox_normal(seed, lo * T * A, 0, 7, action.numel(), self._device).reshape(action.shape)
+        loss = eng.train_planner_grad(action, eps, t, cond, float(w))
+        if shard is not None:
+            import torch.distributed as tdist
+            tdist.all_reduce(eng.train_arena("planner", eng.TRAIN_GRADS), group=shard.get("group"))
+            loss = loss.reshape(1).clone()
+            tdist.all_reduce(loss, group=shard.get("group"))
+            loss = loss.reshape(())
+        sched = self._lr_schedules["planner"]
+        eng.train_apply("planner", float(np.float32(sched(st.step))))            # Adam + EMA, one launch
+        new_state = self._trained_state("planner", st, self._planner_shapes())
+        arrs = [DeviceArray(loss)] + [DeviceArray(x) for x in stats]
+        m = dict(loss=_HostScalar(lambda: arrs[0].numpy()))
+        m["obs_min"], m["obs_max"], m["obs_mean"], m["obs_std"] = (_Elem(arrs[1], i) for i in range(4))
+        m["action_min"], m["action_max"] = _Elem(arrs[2], 0), _Elem(arrs[2], 1)
+        for j, k in enumerate(nb["obs"]):
+            m[f"{k}_min"], m[f"{k}_max"], m[f"{k}_mean"], m[f"{k}_std"] = (_Elem(arrs[3 + j], i) for i in range(4))
+        m["planner_lr"], m["planner_step"] = np.float32(sched(st.step)), st.step       # the OLD state's step (:156-157)
+        return self.replace(planner_state=new_state), m
+
+    # ---- agent/dp_repr_agent.py:203-218 -------------------------------------------------------------
+    def get_metrics(self, batch, rng, noise=None):
+        """The loss, forward only, with the parameters or (use_ema) their EMA, and the statistics scalars of `loss` (:101-133).
+        noise: optional dict(t (B,), noise (B, T, A))."""
+        cfg, eng = self.config, self._engine
+        seed = _seed_of(rng)
+        nz = noise or {}
+
+        def run():
+            self._sync_weights()
+            nb = self._postprocess(batch)
+            if "actions" not in nb:
+                raise KeyError("get_metrics needs batch['actions'] (utils/data_utils.py:73)")
+            cond = self.get_obs_cond(nb["obs"])
+            action = nb["actions"].contiguous()
+            B = action.shape[0]
+            hg = np.random.Generator(np.random.PCG64(seed & (2**63 - 1)))
+            npl = int(cfg["n_diffusion_steps"])
+            t = nz.get("t")
+            t = torch.as_tensor(hg.integers(0, npl, size=B) if t is None else np.asarray(t)).to(self._device)
+            eps = nz.get("noise")
+            eps = self._t(eps) if eps is not None else _philox_normal(seed, 0, 0, 7, action.numel(), self._device).reshape(action.shape)
+            pred = eng.unet_forward(eng.add_noise(action, eps, t, npl), t, cond)
+            out = [eng.mean_sq_diff(pred, eps), eng.reduce_stats(cond), eng.reduce_stats(action)]
+            return out + [eng.reduce_stats(nb["obs"][k]) for k in nb["obs"]]
+        rec = self._record(run)
+        res = self._guarded(run)
+        rec.seqs = self._seqs()
+        arrs = [DeviceArray(x, record=rec) for x in res]
+        m = dict(loss=_HostScalar(lambda: arrs[0].numpy()))
+        m["obs_min"], m["obs_max"], m["obs_mean"], m["obs_std"] = (_Elem(arrs[1], i) for i in range(4))
+        m["action_min"], m["action_max"] = _Elem(arrs[2], 0), _Elem(arrs[2], 1)
+        for j, k in enumerate(batch["obs"].keys()):
+            m[f"{k}_min"], m[f"{k}_max"], m[f"{k}_mean"], m[f"{k}_std"] = (_Elem(arrs[3 + j], i) for i in range(4))
+        return m

@@ -69,6 +69,9 @@ class HipEngine:
         self.loaded = {"planner": None, "idm": None, "vae": None}
         # likewise for the training arenas (ldp_train_*): the token of the ParamState they currently represent
         self.train_token = {"planner": None, "idm": None}
+        # and of the EMA arenas (ldp_train_ema): the token of the EMA tree they hold
+        self.train_ema_token = {"planner": None, "idm": None}
+        self.ema_decay = {}                           # module -> decay of its EMA arena (train_ema)
         # fault bookkeeping for callers that keep results on the device: every sampling call gets a sequence
         # number; a detected fault marks every call enqueued so far as suspect (calls are asynchronous: the word
         # may have been set by any of them)
@@ -281,6 +284,36 @@ class HipEngine:
         self.call_seq += 1
         return x, plan, act
 
+    # -- DP policy: condition gather + U-Net loop + action rows as one call / one captured graph ---------------------
+    def policy_sample(self, obs_emb: torch.Tensor, obs_horizon: int, img_width: int, *, x_init=None, x_noise=None, seed: int = 0,
+                      row_offset: int = 0, sampler: str = "ddpm", n_steps: Optional[int] = None, action_bounds=None,
+                      action_mode: int = 0, use_graph: bool = True) -> torch.Tensor:
+        """DPVAEAgent.sample_step (agent/dp_repr_agent.py:169-201) on this handle's planner module (the action U-Net: D = A):
+        obs_emb (B, frames, E) per-frame [image latent (img_width) | low-dim] -> actions (B, action_horizon, A).  action_bounds /
+        action_mode as in agent_sample."""
+        ob = _f32(obs_emb, self.device)
+        B, H = ob.shape[0], ob.shape[1]
+        E = self.G // int(obs_horizon)
+        _want("obs_emb", ob, (B, H, E))
+        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
+        xi = None if x_init is None else _f32(x_init, self.device)
+        xn = None if x_noise is None else _f32(x_noise, self.device)
+        _want("x_init", xi, (B, self.T, self.D))
+        _want("x_noise", xn, (n_steps, B, self.T, self.D))
+        lo = hi = None
+        adim = 0
+        if action_bounds is not None:
+            lo, hi = self._bounds(*action_bounds)
+            adim = lo.numel()
+            if adim not in (1, self.D) or hi.numel() != adim:
+                raise ValueError(f"action bounds must have length 1 or {self.D}")
+        act = torch.empty((B, self.ah, self.D), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_policy_sample(self._h, _ptr(ob), H, int(obs_horizon), int(img_width), _ptr(xi), _ptr(xn),
+                                         C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _SAMPLERS[sampler], n_steps, _ptr(act),
+                                         _ptr(lo), _ptr(hi), adim, int(action_mode), B, 1 if use_graph else 0, self._stream()))
+        self.call_seq += 1
+        return act
+
     # -- VAE ------------------------------------------------------------------------------------
     def vae_encode(self, img_nhwc: torch.Tensor) -> torch.Tensor:
         img = _f32(img_nhwc, self.device)
@@ -441,7 +474,14 @@ class HipEngine:
         check(self.lib.ldp_train_step_count(self._h, self._MODS[module], C.c_int64(-1 if set_to is None else int(set_to)), C.byref(v)))
         return int(v.value)
 
-    TRAIN_PARAMS, TRAIN_GRADS, TRAIN_MU, TRAIN_NU = 0, 1, 2, 3
+    TRAIN_PARAMS, TRAIN_GRADS, TRAIN_MU, TRAIN_NU, TRAIN_EMA = 0, 1, 2, 3, 4
+
+    def train_ema(self, module: str, decay: float) -> None:
+        """TrainStateEMA(ema_decay=decay, ema_params=params): the module's EMA arena starts as a copy of its parameters; every later
+        train_apply updates it in the same launch, every train_init / train_load re-seeds it from the parameters."""
+        with torch.cuda.device(self.device):
+            check(self.lib.ldp_train_ema(self._h, self._MODS[module], C.c_float(decay), self._stream()))
+        self.ema_decay[module] = float(decay)
 
     def train_read(self, module: str, which: int, shapes) -> Dict[str, np.ndarray]:
         """{flax path: array} of the module's parameters / gradients / Adam moments; `shapes` = {path: shape} (weights.planner_shapes / idm_shapes)."""
@@ -468,6 +508,13 @@ class HipEngine:
         """The sampling path takes over the trained parameters (packed layouts and tables are rebuilt)."""
         with torch.cuda.device(self.device):
             check(self.lib.ldp_train_publish(self._h, self._mask(modules), self._stream()))
+        for name in ([modules] if isinstance(modules, str) else modules):
+            self.loaded[name] = (versions or {}).get(name, object())
+
+    def train_publish_ema(self, modules, versions: Optional[dict] = None) -> None:
+        """The sampling path takes over the EMA of the trained parameters (use_ema)."""
+        with torch.cuda.device(self.device):
+            check(self.lib.ldp_train_publish_ema(self._h, self._mask(modules), self._stream()))
         for name in ([modules] if isinstance(modules, str) else modules):
             self.loaded[name] = (versions or {}).get(name, object())
 

@@ -317,6 +317,13 @@ def eval_loss_metrics(policy, batch: dict, rng) -> dict:
     cfg = getattr(policy, "config", None)
     if cfg is not None and cfg.get("name") == "ldp_hier_agent":          # eval_bc.py:107-109: `return dict(), eval_rng`
         return {}
+    if cfg is not None and str(cfg.get("name", "")).startswith("dp"):   # eval_bc.py:129-131: the loss, then the sampled chunk only
+        actions = np.asarray(batch["actions"], dtype=np.float32)
+        metrics = {k: float(v) for k, v in policy.get_metrics(batch, rng).items()}
+        pred_action_full = np.array(policy.sample(batch, rng)[0])
+        H = pred_action_full.shape[1]
+        metrics["full_action_mse"] = float(np.mean(np.square(actions[:, :H, :] - pred_action_full)))
+        return metrics
     use_planner = bool(getattr(policy, "use_planner", True))
     actions = np.asarray(batch["actions"], dtype=np.float32)
     metrics = {}
