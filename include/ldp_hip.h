@@ -45,6 +45,30 @@ extern "C" {
 
 #define LDP_MAX_LEVELS 4
 
+/* Stream ids of the Philox4x32-10 noise source (counter word 3; "noise source primitives" below).  A draw is keyed by
+ * (seed, global element index, step, stream id); no two kinds of draw share a stream id. */
+#define LDP_PHILOX_STREAM_STEP 0u      /* scheduler noise of executed step i (planner / IDM / policy loops)          */
+#define LDP_PHILOX_STREAM_INIT 1u      /* the initial state x_T / a_T of a loop                                      */
+#define LDP_PHILOX_STREAM_LOSS_PLAN 7u /* add_noise of the planner / policy loss (get_metrics, update)               */
+#define LDP_PHILOX_STREAM_LOSS_IDM 8u  /* add_noise of the IDM loss                                                  */
+#define LDP_PHILOX_STREAM_VAE_EPS 9u   /* eps of the StableVAE posterior draw z = mean + std * eps (ldp_vae_posterior) */
+#define LDP_PHILOX_STREAM_VAE_SAMPLE 10u /* the latents StableVAEModel.sample decodes (drawn through ldp_philox_normal)  */
+
+/* Index of each scalar in the 11-float result of ldp_vae_metrics: the keys of StableVAEModel.loss
+ * (model/stable_vae_model.py:42-53), in the reference's order. */
+#define LDP_VAE_METRIC_IMG_MIN 0
+#define LDP_VAE_METRIC_IMG_MAX 1
+#define LDP_VAE_METRIC_IMG_MEAN 2
+#define LDP_VAE_METRIC_IMG_STD 3
+#define LDP_VAE_METRIC_LOSS 4
+#define LDP_VAE_METRIC_LOSS_MSE 5
+#define LDP_VAE_METRIC_LOSS_KL 6
+#define LDP_VAE_METRIC_Z_MIN 7
+#define LDP_VAE_METRIC_Z_MAX 8
+#define LDP_VAE_METRIC_Z_MEAN 9
+#define LDP_VAE_METRIC_Z_STD 10
+#define LDP_VAE_N_METRICS 11
+
 typedef struct ldp_handle ldp_handle;
 
 /* Hyper-parameters fixed at construction (agent/ldp_agent.yaml:7-34,47-51 + the dims
@@ -174,6 +198,36 @@ LDP_API int ldp_vae_encode(ldp_handle* h, const float* img_nhwc, float* mean_out
  * z (N, S/32, S/32, latent_channels) NHWC, already un-normalised -> image (N, 3, S, S) NCHW.
  * Needs the decoder weights (vae/post_quant_conv, vae/decoder/...) to have been finalized. */
 LDP_API int ldp_vae_decode(ldp_handle* h, const float* z_nhwc, float* img_nchw_out, int32_t N, void* stream);
+
+/* FlaxAutoencoderKL.encode(x).latent_dist.parameters   (model/stable_vae_model.py:29; diffusers
+ * FlaxDiagonalGaussianDistribution.__init__: `mean, logvar = jnp.split(parameters, 2, axis=-1)`)
+ * The encoder exactly as ldp_vae_encode runs it, keeping every quant_conv channel:
+ * moments_out (N, S/32, S/32, 2 * latent_channels) NHWC, channels [0, LC) the mean -- bitwise what ldp_vae_encode
+ * returns -- and [LC, 2 LC) the (unclamped) log-variance. */
+LDP_API int ldp_vae_moments(ldp_handle* h, const float* img_nhwc, float* moments_out, int32_t N, void* stream);
+
+/* FlaxDiagonalGaussianDistribution.sample / .kl on N images' moments (model/stable_vae_model.py:31,38), one fused kernel:
+ *   logvar <- clip(logvar, -30, 20);  std = exp(0.5 logvar);  var = exp(logvar)
+ *   z_out (N, hl, hl, LC) = mean + std * eps;   kl_out[n] = 0.5 * sum_{h,w,c}(mean^2 + var - 1 - logvar)
+ *   stats_out[0..3] = min, max, mean, population std of z (may be NULL);  std_out as z_out (may be NULL)
+ * eps (N, hl, hl, LC): explicit noise, or NULL for the Philox stream LDP_PHILOX_STREAM_VAE_EPS keyed by
+ * (seed, element (row_offset + n) * hl * hl * LC + e, step 0): a shard draws what the unsharded batch draws, and an eps buffer
+ * filled by ldp_philox_normal with the same key gives the same bits.  hl = image_size / 32 and LC come from the handle's config;
+ * no weights are needed.  Every reduction has a fixed order (no atomics): two runs give the same bits. */
+LDP_API int ldp_vae_posterior(ldp_handle* h, const float* moments, const float* eps, uint64_t seed, int64_t row_offset,
+                      float* z_out, float* std_out, float* kl_out, float* stats_out, int32_t N, void* stream);
+
+/* StableVAEModel.loss, forward only (model/stable_vae_model.py:25-55; get_metrics_step :78-87 after postprocess_batch):
+ *   moments -> posterior draw -> decode -> mse = mean((img - pred_img)^2), kl = mean_n kl[n] (exactly 0 when use_kl == 0),
+ *   loss = mse + beta * kl (== mse when use_kl == 0), and min / max / mean / population std of img and of z.
+ * img (N, S, S, 3) NHWC normalised to [-1, 1]; metrics_out: LDP_VAE_N_METRICS device floats in LDP_VAE_METRIC_* order, valid in
+ * stream order (the caller reads them once).  eps / seed / row_offset as ldp_vae_posterior.  z_out (N, hl, hl, LC) NHWC and
+ * rec_out (N, 3, S, S) NCHW receive the draw and the reconstruction when not NULL.  Runs in chunks of 256 images like
+ * ldp_vae_encode / ldp_vae_decode; the loss reads the caller's frames in place (NHWC) against the decoder's NCHW output, and the
+ * per-block partial results of all chunks are merged in a fixed order by one final kernel (centred variances, float64, no atomics).
+ * Needs encoder and decoder weights; behind the fault check and the fp16-plane range guard like the two calls above. */
+LDP_API int ldp_vae_metrics(ldp_handle* h, const float* img_nhwc, int32_t N, int32_t use_kl, float beta, const float* eps,
+                    uint64_t seed, int64_t row_offset, float* metrics_out, float* z_out, float* rec_out, void* stream);
 
 /* -- elementwise pre/post-processing (utils/data_utils.py:9-16,61-65) ----------------------
  * y = (x - lo) / (hi - lo) * 2 - 1            (normalize != 0)

@@ -19,6 +19,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ldp_hip.h")
 LDP_MAX_LEVELS = 4
 SAMPLER_DDPM, SAMPLER_DDIM = 0, 1
 MOD_PLANNER, MOD_IDM, MOD_VAE = 1, 2, 4
+PHILOX_STREAM_VAE_EPS = 9          # LDP_PHILOX_STREAM_VAE_EPS: eps of the StableVAE posterior draw
+# LDP_VAE_METRIC_*: the keys of StableVAEModel.loss (model/stable_vae_model.py:42-53) in the order ldp_vae_metrics writes them
+VAE_METRIC_KEYS = ("img_min", "img_max", "img_mean", "img_std", "loss", "loss_mse", "loss_kl", "z_min", "z_max", "z_mean", "z_std")
 
 
 class LDPHipUnavailable(RuntimeError):
@@ -70,6 +73,9 @@ SIGNATURES: Dict[str, tuple] = {
                                  _FP, C.c_int32, C.c_int32, C.c_void_p]),
     "ldp_vae_encode": (C.c_int, [_H, _FP, _FP, C.c_int32, C.c_void_p]),
     "ldp_vae_decode": (C.c_int, [_H, _FP, _FP, C.c_int32, C.c_void_p]),
+    "ldp_vae_moments": (C.c_int, [_H, _FP, _FP, C.c_int32, C.c_void_p]),
+    "ldp_vae_posterior": (C.c_int, [_H, _FP, _FP, C.c_uint64, C.c_int64, _FP, _FP, _FP, _FP, C.c_int32, C.c_void_p]),
+    "ldp_vae_metrics": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_float, _FP, C.c_uint64, C.c_int64, _FP, _FP, _FP, C.c_void_p]),
     "ldp_conv2d_3x3_f32": (C.c_int, [_FP, C.c_void_p, C.c_void_p, _FP, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ldp_conv2d_3x3_bf16x3": (C.c_int, [_FP, C.c_void_p, C.c_void_p, _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32,

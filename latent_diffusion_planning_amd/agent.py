@@ -193,7 +193,100 @@ def load_pretrained_vae(vp: str):
     return loaded.get("vae_params") or loaded.get("vae") or next(iter(loaded.values()))
 
 
-class LDPAgent:
+class _EngineCalls:
+    """What every model class on a HipEngine shares (LDPAgent and its subclasses, vae_model.StableVAEModel): tensors onto the device, the
+    normalise kernel behind postprocess_batch, and the fault protocol of a policy call (_record / _guarded).  Needs `self._engine` and
+    `self._device`."""
+
+    # ---- pre/post-processing (utils/data_utils.py:18-80) ----------------------------------------
+    def _t(self, v) -> torch.Tensor:
+        v = as_tensor(v)
+        return v.to(device=self._device, dtype=torch.float32).contiguous()
+
+    def _apply_norm(self, v: torch.Tensor, entry: dict, normalize: bool) -> torch.Tensor:
+        if "min" in entry:
+            lo, hi = entry["min"], entry["max"]
+            if np.ndim(lo) != 0:
+                lo, hi = np.asarray(lo), np.asarray(hi)
+                diff = v.dim() - lo.ndim
+                assert diff in (0, 1, 2, 3, 4, 5), "shape length mismatch in normalize_obs"
+                assert tuple(v.shape[diff:]) == tuple(lo.shape), \
+                    f"shape mismatch in normalize obs. {tuple(v.shape)}, {lo.shape}"
+                lo, hi = lo.reshape(-1), hi.reshape(-1)
+                return self._engine.normalize_bounds(v.reshape(-1, lo.size), lo, hi, normalize).reshape(v.shape)
+            return self._engine.normalize_bounds(v, [lo], [hi], normalize)
+        # clip_min / clip_max: plain clip in both directions (utils/data_utils.py:61-65)
+        return self._engine.normalize_bounds(v, [entry["clip_min"]], [entry["clip_max"]], 2)
+
+    def _normalize_dict(self, d, table, normalize=True):
+        assert set(d.keys()).issubset(table), \
+            f"obs_normalization keys {table.keys()} do not match batch keys {d.keys()}"
+        return {k: self._apply_norm(self._t(v), table[k], normalize) for k, v in d.items()}
+
+    # ---- completion hook of a policy call (fault protocol, include/ldp_hip.h) --------------------------
+    def _engines(self):
+        """Every engine handle a policy call of this agent enqueues on (LDPHierAgent has two)."""
+        return [self._engine]
+
+    def _seqs(self):
+        return tuple(e.call_seq for e in self._engines())
+
+    def _record(self, recompute):
+        """recompute() -> list of replacement tensors (None for lazy arrays), in the order the call's
+        DeviceArrays were created."""
+        engines = self._engines()
+
+        def on_complete(rec: CallRecord):
+            # calls are asynchronous: a recorded fault may stem from any call enqueued so far, so the poll marks
+            # them all suspect (engine.fault_upto) and each is recomputed when ITS results are first read
+            for e in engines:
+                e.poll_fault_kinds()
+            if not any(s <= e.fault_upto for s, e in zip(rec.seqs, engines)):
+                return
+            kinds = 0
+            for s_, e in zip(rec.seqs, engines):               # the kind(s) of the poll that made THIS call suspect, not every kind the handle ever saw
+                if s_ <= e.fault_upto:
+                    kinds |= e.last_fault_kinds
+            if kinds & HipEngine.FAULT_RANGE:
+                warnings.warn("libldp_hip: an operand left the range of the two-fp16-plane convolutions (|x| >= 65504); the call "
+                              "is recomputed on three bf16 planes (fp32 range; the IDM on its exact-fp32 kernel), which this engine keeps from now on",
+                              RuntimeWarning, stacklevel=3)
+            if kinds & HipEngine.FAULT_EXCHANGE:
+                warnings.warn("libldp_hip: a split work-group timed out on its peer (GPU shared with another "
+                              "kernel?); the call is recomputed in safe mode, which this engine keeps from now on",
+                              RuntimeWarning, stacklevel=3)
+            # a recompute may meet the OTHER kind of fault for the first time (safe mode first, then the range guard): bounded retries
+            for attempt in range(3):
+                fresh = self._guarded(recompute)
+                torch.cuda.current_stream(self._device).synchronize()
+                again = 0
+                for e in engines:
+                    again |= e.poll_fault_kinds()
+                if not again:
+                    break
+            else:
+                raise RuntimeError("libldp_hip faulted again after switching to safe mode / bf16 planes")
+            for arr, t in zip(rec.arrays, fresh):
+                if arr is not None:
+                    arr._swap(t)
+        return CallRecord(on_complete)
+
+    def _guarded(self, run):
+        """Run the engine calls of one policy call; if an engine refuses because an earlier (unread) call
+        faulted, acknowledge on every engine -- that marks the earlier calls suspect, they are recomputed when read -- and retry."""
+        from ._lib import LDPHipFault
+        for attempt in range(4):                     # in-flight pre-safe-mode launches may still fault after the first acknowledge
+            try:
+                return run()
+            except LDPHipFault:
+                if attempt == 3:
+                    raise
+                torch.cuda.current_stream(self._device).synchronize()
+                for e in self._engines():
+                    e.poll_fault_kinds()
+
+
+class LDPAgent(_EngineCalls):
     # ---------------------------------------------------------------------------------------------
     def __init__(self, planner_state, idm_state, vae_params, obs_normalization, use_planner, use_idm,
                  alpha_planner, alpha_idm, config, engine: Optional[HipEngine], planner_spec, idm_spec,
@@ -388,31 +481,7 @@ class LDPAgent:
     def _idm_shapes(self):
         return W.idm_shapes(self._idm_spec)
 
-    # ---- pre/post-processing (utils/data_utils.py:18-80) ----------------------------------------
-    def _t(self, v) -> torch.Tensor:
-        v = as_tensor(v)
-        return v.to(device=self._device, dtype=torch.float32).contiguous()
-
-    def _apply_norm(self, v: torch.Tensor, entry: dict, normalize: bool) -> torch.Tensor:
-        if "min" in entry:
-            lo, hi = entry["min"], entry["max"]
-            if np.ndim(lo) != 0:
-                lo, hi = np.asarray(lo), np.asarray(hi)
-                diff = v.dim() - lo.ndim
-                assert diff in (0, 1, 2, 3, 4, 5), "shape length mismatch in normalize_obs"
-                assert tuple(v.shape[diff:]) == tuple(lo.shape), \
-                    f"shape mismatch in normalize obs. {tuple(v.shape)}, {lo.shape}"
-                lo, hi = lo.reshape(-1), hi.reshape(-1)
-                return self._engine.normalize_bounds(v.reshape(-1, lo.size), lo, hi, normalize).reshape(v.shape)
-            return self._engine.normalize_bounds(v, [lo], [hi], normalize)
-        # clip_min / clip_max: plain clip in both directions (utils/data_utils.py:61-65)
-        return self._engine.normalize_bounds(v, [entry["clip_min"]], [entry["clip_max"]], 2)
-
-    def _normalize_dict(self, d, table, normalize=True):
-        assert set(d.keys()).issubset(table), \
-            f"obs_normalization keys {table.keys()} do not match batch keys {d.keys()}"
-        return {k: self._apply_norm(self._t(v), table[k], normalize) for k, v in d.items()}
-
+    # ---- pre/post-processing: _t / _apply_norm / _normalize_dict are _EngineCalls' (utils/data_utils.py:18-80) ----
     def _postprocess(self, batch):
         """postprocess_batch / postprocess_batch_obs selection of agent/ldp_agent.py:436-440."""
         if "actions" in batch.keys():
@@ -486,68 +555,6 @@ class LDPAgent:
         B, H = lowdim.shape[:2]
         img = torch.cat([self._t(batch[k]) for k in self.config["rgb_obs"]], dim=1)
         return torch.cat([img.reshape(B, H, -1), lowdim.reshape(B, H, -1)], dim=-1)
-
-    # ---- completion hook of a policy call (fault protocol, include/ldp_hip.h) --------------------------
-    def _engines(self):
-        """Every engine handle a policy call of this agent enqueues on (LDPHierAgent has two)."""
-        return [self._engine]
-
-    def _seqs(self):
-        return tuple(e.call_seq for e in self._engines())
-
-    def _record(self, recompute):
-        """recompute() -> list of replacement tensors (None for lazy arrays), in the order the call's
-        DeviceArrays were created."""
-        engines = self._engines()
-
-        def on_complete(rec: CallRecord):
-            # calls are asynchronous: a recorded fault may stem from any call enqueued so far, so the poll marks
-            # them all suspect (engine.fault_upto) and each is recomputed when ITS results are first read
-            for e in engines:
-                e.poll_fault_kinds()
-            if not any(s <= e.fault_upto for s, e in zip(rec.seqs, engines)):
-                return
-            kinds = 0
-            for s_, e in zip(rec.seqs, engines):               # the kind(s) of the poll that made THIS call suspect, not every kind the handle ever saw
-                if s_ <= e.fault_upto:
-                    kinds |= e.last_fault_kinds
-            if kinds & HipEngine.FAULT_RANGE:
-                warnings.warn("libldp_hip: an operand left the range of the two-fp16-plane convolutions (|x| >= 65504); the call "
-                              "is recomputed on three bf16 planes (fp32 range; the IDM on its exact-fp32 kernel), which this engine keeps from now on",
-                              RuntimeWarning, stacklevel=3)
-            if kinds & HipEngine.FAULT_EXCHANGE:
-                warnings.warn("libldp_hip: a split work-group timed out on its peer (GPU shared with another "
-                              "kernel?); the call is recomputed in safe mode, which this engine keeps from now on",
-                              RuntimeWarning, stacklevel=3)
-            # a recompute may meet the OTHER kind of fault for the first time (safe mode first, then the range guard): bounded retries
-            for attempt in range(3):
-                fresh = self._guarded(recompute)
-                torch.cuda.current_stream(self._device).synchronize()
-                again = 0
-                for e in engines:
-                    again |= e.poll_fault_kinds()
-                if not again:
-                    break
-            else:
-                raise RuntimeError("libldp_hip faulted again after switching to safe mode / bf16 planes")
-            for arr, t in zip(rec.arrays, fresh):
-                if arr is not None:
-                    arr._swap(t)
-        return CallRecord(on_complete)
-
-    def _guarded(self, run):
-        """Run the engine calls of one policy call; if an engine refuses because an earlier (unread) call
-        faulted, acknowledge on every engine -- that marks the earlier calls suspect, they are recomputed when read -- and retry."""
-        from ._lib import LDPHipFault
-        for attempt in range(4):                     # in-flight pre-safe-mode launches may still fault after the first acknowledge
-            try:
-                return run()
-            except LDPHipFault:
-                if attempt == 3:
-                    raise
-                torch.cuda.current_stream(self._device).synchronize()
-                for e in self._engines():
-                    e.poll_fault_kinds()
 
     def _action_bounds(self):
         """(lo, hi, mode) of utils/data_utils.py:61-68 for the un-normalisation of actions."""

@@ -140,6 +140,15 @@ def param_trees(raw_restored: dict, keys: Optional[Iterable[str]] = None) -> Dic
 def load_snapshot(agent, path: str, restore_keys: Iterable[str] = ()):
     """train_bc.py:210-240 on this agent: every restored `<prefix>_params` replaces `<prefix>_state`'s params and
     ema_params (`vae_params` replaces the agent's VAE tree); returns the new agent (flax-style, the old one is untouched)."""
+    if hasattr(agent, "vae_state"):
+        # a StableVAEModel (train_vae.py saves `vae_params` and `ema_params`): both sets come back, the EMA falling back to the
+        # parameters when the file has none
+        raw = restore(path)
+        if not isinstance(raw.get("vae_params"), dict):
+            raise CheckpointError(f"{path}: no vae_params tree in this checkpoint (has {sorted(raw)})")
+        p = W.flatten(raw["vae_params"])
+        e = W.flatten(raw["ema_params"]) if isinstance(raw.get("ema_params"), dict) else p
+        return agent.replace(vae_state=agent.vae_state.replace(params=p, ema_params=e))
     trees = param_trees(restore(path), restore_keys)
     fields = {}
     for k, flat in trees.items():

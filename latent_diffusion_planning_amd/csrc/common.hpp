@@ -91,6 +91,16 @@ int add_noise_launch(const float* x0, const float* noise, const int* t_dev, cons
                      int64_t rows, int width, hipStream_t s);
 int normalize_launch(const float* x, float* y, int64_t n, const float* lo, const float* hi, int dim,
                      int normalize, hipStream_t s);
+// StableVAE loss head (kernels_misc.hip): posterior draw + per-image KL, the loss / image-statistics reduction, and the merge of their
+// per-block partials (6 doubles each: count, mean, M2, extra sum, min, max)
+int vae_posterior_blocks(int N, int E, int LC);
+int vae_posterior_launch(const float* moments, const float* eps, uint64_t seed, uint64_t row0, float* z, float* std_out, float* kl,
+                         double* part, int N, int E, int LC, hipStream_t s);
+int vae_loss_blocks(int64_t npix);
+int vae_loss_stats_launch(const float* x_nhwc, const float* y_nchw, int64_t npix, int HW, double* part, hipStream_t s);
+int vae_moment_final_launch(const double* part, int np, float* out4, hipStream_t s);
+int vae_metrics_final_launch(const double* ipart, int nip, const double* zpart, int nzp, const float* kl, int N, int use_kl, float beta,
+                             float* out11, hipStream_t s);
 // LayerNorm over the last axis (eps 1e-6, fast variance): y = (x-mean)*rstd*scale+bias
 int layernorm_launch(const float* x, float* y, const float* scale, const float* bias, int rows,
                      int dim, hipStream_t s);

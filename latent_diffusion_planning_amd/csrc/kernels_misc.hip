@@ -410,4 +410,211 @@ int layernorm_launch(const float* x, float* y, const float* scale, const float* 
   return LDP_OK;
 }
 
+// ---- StableVAE loss head (model/stable_vae_model.py:25-55; diffusers FlaxDiagonalGaussianDistribution) -------------------------
+// Every statistic is a (count, mean, M2, min, max) moment that is merged Chan-style (Chan, Golub, LeVeque 1979) in float64 and in a
+// fixed order: 12 register values per thread, shuffles within a wave, LDS across the waves, ONE partial per block in global memory,
+// and a single-block kernel that merges the partials of every 256-image chunk.  No atomics, no E[x^2] - E[x]^2.
+struct Moment {
+  double n, mean, m2, extra;          // extra: a plain sum that travels with the moment (sum of squared differences / of the KL terms)
+  float lo, hi;
+};
+__device__ __forceinline__ Moment moment_empty() { return Moment{0.0, 0.0, 0.0, 0.0, INFINITY, -INFINITY}; }
+__device__ __forceinline__ void moment_merge(Moment& a, const Moment& b) {
+  if (b.n > 0.0) {
+    const double n = a.n + b.n, d = b.mean - a.mean, f = b.n / n;
+    a.mean += d * f;
+    a.m2 += b.m2 + d * d * a.n * f;
+    a.n = n;
+  }
+  a.extra += b.extra;
+  a.lo = fminf(a.lo, b.lo);
+  a.hi = fmaxf(a.hi, b.hi);
+}
+// -> the block's moment in thread 0 (blockDim.x a multiple of 64, at most 1024)
+__device__ __forceinline__ Moment moment_block_reduce(Moment m) {
+  __shared__ Moment wv[16];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    Moment o;
+    o.n = __shfl_down(m.n, off); o.mean = __shfl_down(m.mean, off); o.m2 = __shfl_down(m.m2, off);
+    o.extra = __shfl_down(m.extra, off); o.lo = __shfl_down(m.lo, off); o.hi = __shfl_down(m.hi, off);
+    moment_merge(m, o);
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  if (lane == 0) wv[w] = m;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int i = 1; i < nw; ++i) moment_merge(m, wv[i]);
+  return m;
+}
+__device__ __forceinline__ void moment_store(double* p, const Moment& m) {
+  p[0] = m.n; p[1] = m.mean; p[2] = m.m2; p[3] = m.extra; p[4] = (double)m.lo; p[5] = (double)m.hi;
+}
+__device__ __forceinline__ Moment moment_load(const double* p) {
+  return Moment{p[0], p[1], p[2], p[3], (float)p[4], (float)p[5]};
+}
+
+// posterior: z = mean + exp(0.5 logvar) eps with logvar clamped to [-30, 20], kl[n] = 0.5 sum(mean^2 + var - 1 - logvar) over the image
+// (FlaxDiagonalGaussianDistribution.sample / .kl).  One thread per latent element, `ipb` whole images per block; moments (N, E, 2 LC):
+// channels [0, LC) mean, [LC, 2 LC) log-variance.  eps == nullptr: Philox element (row0 + n) * E * LC + e, stream LDP_PHILOX_STREAM_VAE_EPS.
+__global__ __launch_bounds__(256) void vae_posterior_kernel(const float* __restrict__ mom, const float* __restrict__ eps, uint64_t seed,
+                                                            uint64_t row0, float* __restrict__ z, float* __restrict__ std_out,
+                                                            float* __restrict__ kl, double* __restrict__ part, int N, int E, int LC,
+                                                            int ipb) {
+  __shared__ float term[256];
+  const int per = E * LC, t = threadIdx.x;
+  const int il = t / per, e = t - il * per;
+  const int64_t n = (int64_t)blockIdx.x * ipb + il;
+  const bool valid = il < ipb && n < N;
+  Moment m = moment_empty();
+  float tm = 0.0f;
+  if (valid) {
+    const int pix = e / LC, c = e - pix * LC;
+    const float* row = mom + ((size_t)n * E + pix) * 2 * LC;
+    const float mean = row[c];
+    const float lv = fminf(fmaxf(row[LC + c], -30.0f), 20.0f);
+    const float sd = expf(0.5f * lv), var = expf(lv);
+    const size_t i = (size_t)n * per + e;
+    const float ep = eps ? eps[i] : philox_normal(seed, (row0 + (uint64_t)n) * (uint64_t)per + (uint64_t)e, 0u, LDP_PHILOX_STREAM_VAE_EPS);
+    const float zz = mean + sd * ep;
+    z[i] = zz;
+    if (std_out) std_out[i] = sd;
+    tm = mean * mean + var - 1.0f - lv;
+    m.n = 1.0; m.mean = (double)zz; m.lo = m.hi = zz;
+  }
+  term[t] = tm;
+  __syncthreads();
+  if (valid && e == 0) {
+    double s = 0.0;
+    for (int j = 0; j < per; ++j) s += (double)term[t + j];
+    kl[n] = (float)(0.5 * s);
+  }
+  m = moment_block_reduce(m);
+  if (t == 0) moment_store(part + (size_t)blockIdx.x * 6, m);
+}
+
+int vae_posterior_blocks(int N, int E, int LC) { const int ipb = 256 / (E * LC); return (N + ipb - 1) / ipb; }
+
+int vae_posterior_launch(const float* moments, const float* eps, uint64_t seed, uint64_t row0, float* z, float* std_out, float* kl,
+                         double* part, int N, int E, int LC, hipStream_t s) {
+  if (E * LC > 256 || E * LC <= 0) return fail(LDP_EINVAL, "posterior: %d latent elements per image (at most 256)", E * LC);
+  const int ipb = 256 / (E * LC);
+  hipLaunchKernelGGL(vae_posterior_kernel, dim3(vae_posterior_blocks(N, E, LC)), dim3(256), 0, s, moments, eps, seed, row0, z, std_out,
+                     kl, part, N, E, LC, ipb);
+  LDP_HIP(hipGetLastError());
+  return LDP_OK;
+}
+
+// loss and image statistics: x (N, HW, 3) NHWC as the caller holds the frames, y (N, 3, HW) NCHW as the decoder leaves them, both indexed
+// in place.  A thread owns VAE_LOSS_PPT pixels (x: 12 bytes each, contiguous over the wave; y: one coalesced read per colour plane);
+// partial = moment of x, extra = sum (x - y)^2.
+constexpr int VAE_LOSS_PPT = 4;
+__global__ __launch_bounds__(256) void vae_loss_stats_kernel(const float* __restrict__ x, const float* __restrict__ y, int64_t npix, int HW,
+                                                             double* __restrict__ part) {
+  const int64_t base = (int64_t)blockIdx.x * (256 * VAE_LOSS_PPT);
+  float v[3 * VAE_LOSS_PPT];
+  double sum = 0.0, sq = 0.0;
+  int cnt = 0;
+  float lo = INFINITY, hi = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < VAE_LOSS_PPT; ++k) {
+    const int64_t gp = base + k * 256 + threadIdx.x;
+    const bool ok = gp < npix;
+    const int64_t n = ok ? gp / HW : 0;
+    const int64_t p = ok ? gp - n * HW : 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float xv = ok ? x[gp * 3 + c] : 0.0f;
+      const float yv = ok ? y[(n * 3 + c) * HW + p] : 0.0f;
+      const float d = xv - yv;
+      v[k * 3 + c] = xv;
+      if (ok) {
+        sum += (double)xv;
+        sq += (double)d * (double)d;
+        lo = fminf(lo, xv);
+        hi = fmaxf(hi, xv);
+      }
+    }
+    cnt += ok ? 3 : 0;
+  }
+  Moment m = moment_empty();
+  if (cnt > 0) {
+    const double mean = sum / (double)cnt;
+    double m2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3 * VAE_LOSS_PPT; ++i) {
+      const double d = (double)v[i] - mean;
+      if (i < cnt) m2 += d * d;                    // a thread's valid pixels are its first cnt / 3 (gp grows with k)
+    }
+    m.n = (double)cnt; m.mean = mean; m.m2 = m2; m.lo = lo; m.hi = hi;
+  }
+  m.extra = sq;
+  m = moment_block_reduce(m);
+  if (threadIdx.x == 0) moment_store(part + (size_t)blockIdx.x * 6, m);
+}
+
+int vae_loss_blocks(int64_t npix) { return (int)((npix + 256 * VAE_LOSS_PPT - 1) / (256 * VAE_LOSS_PPT)); }
+
+int vae_loss_stats_launch(const float* x_nhwc, const float* y_nchw, int64_t npix, int HW, double* part, hipStream_t s) {
+  hipLaunchKernelGGL(vae_loss_stats_kernel, dim3(vae_loss_blocks(npix)), dim3(256), 0, s, x_nhwc, y_nchw, npix, HW, part);
+  LDP_HIP(hipGetLastError());
+  return LDP_OK;
+}
+
+// merges `np` block partials in a fixed order (thread t takes t, t + 256, ...; then the block tree) -> thread 0
+__device__ __forceinline__ Moment moment_merge_parts(const double* __restrict__ part, int np) {
+  Moment m = moment_empty();
+  for (int i = threadIdx.x; i < np; i += blockDim.x) moment_merge(m, moment_load(part + (size_t)i * 6));
+  return moment_block_reduce(m);
+}
+
+// out4 = {min, max, mean, population std} of the merged partials (ldp_vae_posterior's statistics of z)
+__global__ __launch_bounds__(256) void vae_moment_final_kernel(const double* __restrict__ part, int np, float* __restrict__ out4) {
+  const Moment m = moment_merge_parts(part, np);
+  if (threadIdx.x == 0) {
+    out4[0] = m.lo; out4[1] = m.hi; out4[2] = (float)m.mean; out4[3] = (float)sqrt(m.m2 / m.n);
+  }
+}
+
+int vae_moment_final_launch(const double* part, int np, float* out4, hipStream_t s) {
+  hipLaunchKernelGGL(vae_moment_final_kernel, dim3(1), dim3(256), 0, s, part, np, out4);
+  LDP_HIP(hipGetLastError());
+  return LDP_OK;
+}
+
+// the eleven scalars of StableVAEModel.loss (model/stable_vae_model.py:34-53), in LDP_VAE_METRIC_* order
+__global__ __launch_bounds__(256) void vae_metrics_final_kernel(const double* __restrict__ ipart, int nip, const double* __restrict__ zpart,
+                                                                int nzp, const float* __restrict__ kl, int N, int use_kl, float beta,
+                                                                float* __restrict__ out) {
+  const Moment im = moment_merge_parts(ipart, nip);
+  __syncthreads();                                  // the reduction's LDS is reused
+  const Moment zm = moment_merge_parts(zpart, nzp);
+  __syncthreads();
+  Moment km = moment_empty();
+  for (int i = threadIdx.x; i < N; i += blockDim.x) km.extra += (double)kl[i];
+  km = moment_block_reduce(km);
+  if (threadIdx.x == 0) {
+    const float mse = (float)(im.extra / im.n);                        // jnp.mean((img - pred_img) ** 2)
+    const float klm = use_kl ? (float)(km.extra / (double)N) : 0.0f;   // jnp.mean(z_dist.kl()), or the literal 0 of :39
+    out[LDP_VAE_METRIC_IMG_MIN] = im.lo;
+    out[LDP_VAE_METRIC_IMG_MAX] = im.hi;
+    out[LDP_VAE_METRIC_IMG_MEAN] = (float)im.mean;
+    out[LDP_VAE_METRIC_IMG_STD] = (float)sqrt(im.m2 / im.n);
+    out[LDP_VAE_METRIC_LOSS] = use_kl ? mse + beta * klm : mse;
+    out[LDP_VAE_METRIC_LOSS_MSE] = mse;
+    out[LDP_VAE_METRIC_LOSS_KL] = klm;
+    out[LDP_VAE_METRIC_Z_MIN] = zm.lo;
+    out[LDP_VAE_METRIC_Z_MAX] = zm.hi;
+    out[LDP_VAE_METRIC_Z_MEAN] = (float)zm.mean;
+    out[LDP_VAE_METRIC_Z_STD] = (float)sqrt(zm.m2 / zm.n);
+  }
+}
+
+int vae_metrics_final_launch(const double* ipart, int nip, const double* zpart, int nzp, const float* kl, int N, int use_kl, float beta,
+                             float* out11, hipStream_t s) {
+  hipLaunchKernelGGL(vae_metrics_final_kernel, dim3(1), dim3(256), 0, s, ipart, nip, zpart, nzp, kl, N, use_kl, beta, out11);
+  LDP_HIP(hipGetLastError());
+  return LDP_OK;
+}
+
 }  // namespace ldp

@@ -50,6 +50,9 @@ struct VaeState {
   DevBuf b0, b1, b2, b3, b4, part, part2, stats, small[5], qkv;
   DevBuf planes, zero;                 // split-operand convs: the normalised input as three bf16 planes; a zero page
   int eout_cols = 32;                  // padded column count of the encoder's conv_out (2 LC real)
+  // loss head (ldp_vae_posterior / ldp_vae_metrics): homes outside the ping-pong buffers b0..b4, which encoder and decoder share
+  DevBuf mom, zlat, klv, rec;          // moments (N, hl, hl, 2 LC), draw (N, hl, hl, LC), per-image KL (N); one chunk's reconstruction
+  DevBuf zpart, ipart;                 // per-block partial moments of z / of the frames (6 doubles each), all chunks of a call
 };
 
 VaeState* V(ldp_handle* h) { return static_cast<VaeState*>(h->vae); }
@@ -721,56 +724,113 @@ void vae_destroy(ldp_handle* h) {
 
 using namespace ldp;
 
+// One chunk (n <= 256 images) of the encoder: img (n, S, S, 3) -> the first `nout` quant_conv channels, out (n, hl, hl, nout).
+// nout = LC keeps the mean (ldp_vae_encode), nout = 2 LC the mean and the log-variance (ldp_vae_moments): column j is the same fmaf
+// chain either way, so the mean channels of the two are the same bits.
+static int encode_chunk(ldp_handle* h, VaeState& S, hipStream_t s, const float* img, int n, float* out, int nout) {
+  const int NB = (int)S.ch.size();
+  const int hl = S.S >> (NB - 1);                          // latent side (2 for 64x64)
+  LDP_TRY(workspace(h, n));
+  Run R{h, S, s};
+  float *cur = S.b0.f(), *o1 = S.b1.f(), *t0 = S.b2.f(), *t1 = S.b3.f();
+  int H = S.S, C = S.ch[0];
+  {
+    constexpr int PPB = 8;                            // (C/4) * 8 = 256 threads at C = 128
+    const size_t lds = std::max((size_t)3 * (H + 2) * 3 * 4, (size_t)(C / 4) * PPB * 2 * 4);
+    // its GroupNorm sums go to S.part as part[n][row][C/4][2]: 2 * S * C bytes per image, and (C/4) * PPB threads per block
+    const bool stats_fit = !h->opt.vae_no_conv_in_stats && (size_t)n * H * (C / 4) * 8 <= S.part.bytes;
+    if ((C / 4) * PPB > 1024) return fail(LDP_EINVAL, "conv_in: %d output channels need %d threads per block", C, (C / 4) * PPB);
+    hipLaunchKernelGGL(conv_in3_kernel<PPB>, dim3(n * H), dim3((C / 4) * PPB), lds, s,
+                       img, S.cin_w.f(), S.cin_b.f(), cur, stats_fit ? S.part.f() : nullptr, n, H, C);
+    R.wrote(cur);
+    // stage-1 GroupNorm sums of `cur` are in S.part (one chunk per image row) when the kernel could write them there
+    if (stats_fit) { R.part_for = cur; R.part_nchunk = H; R.part_c = C; }
+    LDP_HIP(hipGetLastError());
+  }
+  for (int i = 0; i < NB; ++i) {
+    for (int j = 0; j < 2; ++j) {
+      LDP_TRY(R.res(S.down[i].r[j], cur, o1, t0, t1, S.b4.f(), n, H, H));
+      std::swap(cur, o1);
+    }
+    if (S.down[i].has_ds) {
+      LDP_TRY(R.conv3(S.down[i].ds, cur, o1, n, H, H, 2, nullptr));
+      std::swap(cur, o1);
+      H /= 2;
+    }
+  }
+  LDP_TRY(R.mid(S.emid, cur, o1, t0, t1, n, H, H));
+  LDP_TRY(R.gn_conv3(S.enorm, S.econv_out, cur, t1, t0, n, H, H, nullptr));          // (n, hl, hl, 32): first 2*LC real
+  // quant_conv 1x1 (2LC -> 2LC), keep the first nout channels
+  const int64_t rows = (int64_t)n * hl * hl;
+  hipLaunchKernelGGL(tiny_dense_kernel, dim3(nblk(rows * nout)), dim3(256), 0, s, t1, S.eout_cols, S.quant_w.f(),
+                     S.quant_b.f(), out, nout, rows, 2 * S.LC, 2 * S.LC, nout);
+  LDP_HIP(hipGetLastError());
+  return LDP_OK;
+}
+
+// One chunk of the decoder: z (n, hl, hl, LC) -> img_out (n, 3, S, S)
+static int decode_chunk(ldp_handle* h, VaeState& S, hipStream_t s, const float* z, int n, float* img_out) {
+  const int NB = (int)S.ch.size();
+  const int hl = S.S >> (NB - 1);
+  LDP_TRY(workspace(h, n));
+  Run R{h, S, s};
+  float *cur = S.b0.f(), *o1 = S.b1.f(), *t0 = S.b2.f(), *t1 = S.b3.f();
+  int H = hl;
+  const int64_t rows = (int64_t)n * hl * hl;
+  // post_quant 1x1 (LC -> LC) into a 64-channel zero-padded tensor (the conv kernel's channel chunk)
+  LDP_HIP(hipMemsetAsync(t0, 0, (size_t)rows * 64 * 4, s));
+  R.wrote(t0);
+  hipLaunchKernelGGL(tiny_dense_kernel, dim3(nblk(rows * S.LC)), dim3(256), 0, s, z,
+                     S.LC, S.pq_w.f(), S.pq_b.f(), t0, 64, rows, S.LC, S.LC, S.LC);
+  LDP_TRY(R.conv3(S.dconv_in, t0, cur, n, H, H, 1, nullptr));
+  LDP_TRY(R.mid(S.dmid, cur, o1, t0, t1, n, H, H));
+  for (int i = 0; i < NB; ++i) {
+    for (int j = 0; j < 3; ++j) {
+      LDP_TRY(R.res(S.up[i].r[j], cur, o1, t0, t1, S.b4.f(), n, H, H));
+      std::swap(cur, o1);
+    }
+    if (S.up[i].has_us) {
+      const int C = S.up[i].us.cin;
+      const int64_t tot = (int64_t)n * 4 * H * H * (C / 4);
+      hipLaunchKernelGGL(upsample2_kernel, dim3(nblk(tot)), dim3(256), 0, s, cur, t0, n, H, H, C);
+      R.wrote(t0);
+      H *= 2;
+      LDP_TRY(R.conv3(S.up[i].us, t0, o1, n, H, H, 1, nullptr));
+      std::swap(cur, o1);
+    }
+  }
+  LDP_TRY(R.gn_conv3(S.dnorm, S.dconv_out, cur, t1, t0, n, H, H, nullptr));          // (n, S, S, 32): first 3 real
+  const int64_t tot = (int64_t)n * 3 * H * H;
+  hipLaunchKernelGGL(nhwc_to_nchw3_kernel, dim3(nblk(tot)), dim3(256), 0, s, t1, img_out, n, H * H, 32);
+  LDP_HIP(hipGetLastError());
+  return LDP_OK;
+}
+
+static const int VAE_CHUNK = 256;                          // images per pass (bounds the workspace)
+
+static int encode_all(ldp_handle* h, const float* img, float* out, int N, int nout, void* stream) {
+  VaeState& S = *V(h);
+  const int hl = S.S >> ((int)S.ch.size() - 1);
+  for (int n0 = 0; n0 < N; n0 += VAE_CHUNK)
+    LDP_TRY(encode_chunk(h, S, (hipStream_t)stream, img + (size_t)n0 * S.S * S.S * 3, std::min(VAE_CHUNK, N - n0),
+                         out + (size_t)n0 * hl * hl * nout, nout));
+  return LDP_OK;
+}
+
 extern "C" {
 
 int ldp_vae_encode(ldp_handle* h, const float* img, float* mean_out, int32_t N, void* stream) {
   if (!h || !img || !mean_out || N <= 0) return fail(LDP_EINVAL, "bad argument");
   if (!h->vae || !V(h)->enc_ready) return fail(LDP_ESTATE, "vae weights not finalized");
   LDP_TRY(entry_fault_check(h));
-  VaeState& S = *V(h);
-  hipStream_t s = (hipStream_t)stream;
-  const int CHUNK = 256;                                   // images per pass (bounds the workspace)
-  const int NB = (int)S.ch.size();
-  const int hl = S.S >> (NB - 1);                          // latent side (2 for 64x64)
-  for (int n0 = 0; n0 < N; n0 += CHUNK) {
-    const int n = std::min(CHUNK, N - n0);
-    LDP_TRY(workspace(h, n));
-    Run R{h, S, s};
-    float *cur = S.b0.f(), *o1 = S.b1.f(), *t0 = S.b2.f(), *t1 = S.b3.f();
-    int H = S.S, C = S.ch[0];
-    {
-      constexpr int PPB = 8;                            // (C/4) * 8 = 256 threads at C = 128
-      const size_t lds = std::max((size_t)3 * (H + 2) * 3 * 4, (size_t)(C / 4) * PPB * 2 * 4);
-      // its GroupNorm sums go to S.part as part[n][row][C/4][2]: 2 * S * C bytes per image, and (C/4) * PPB threads per block
-      const bool stats_fit = !h->opt.vae_no_conv_in_stats && (size_t)n * H * (C / 4) * 8 <= S.part.bytes;
-      if ((C / 4) * PPB > 1024) return fail(LDP_EINVAL, "conv_in: %d output channels need %d threads per block", C, (C / 4) * PPB);
-      hipLaunchKernelGGL(conv_in3_kernel<PPB>, dim3(n * H), dim3((C / 4) * PPB), lds, s,
-                         img + (size_t)n0 * H * H * 3, S.cin_w.f(), S.cin_b.f(), cur, stats_fit ? S.part.f() : nullptr, n, H, C);
-      R.wrote(cur);
-      // stage-1 GroupNorm sums of `cur` are in S.part (one chunk per image row) when the kernel could write them there
-      if (stats_fit) { R.part_for = cur; R.part_nchunk = H; R.part_c = C; }
-      LDP_HIP(hipGetLastError());
-    }
-    for (int i = 0; i < NB; ++i) {
-      for (int j = 0; j < 2; ++j) {
-        LDP_TRY(R.res(S.down[i].r[j], cur, o1, t0, t1, S.b4.f(), n, H, H));
-        std::swap(cur, o1);
-      }
-      if (S.down[i].has_ds) {
-        LDP_TRY(R.conv3(S.down[i].ds, cur, o1, n, H, H, 2, nullptr));
-        std::swap(cur, o1);
-        H /= 2;
-      }
-    }
-    LDP_TRY(R.mid(S.emid, cur, o1, t0, t1, n, H, H));
-    LDP_TRY(R.gn_conv3(S.enorm, S.econv_out, cur, t1, t0, n, H, H, nullptr));          // (n, hl, hl, 32): first 2*LC real
-    // quant_conv 1x1 (2LC -> 2LC), keep the mean = first LC channels
-    const int64_t rows = (int64_t)n * hl * hl;
-    hipLaunchKernelGGL(tiny_dense_kernel, dim3(nblk(rows * S.LC)), dim3(256), 0, s, t1, S.eout_cols, S.quant_w.f(),
-                       S.quant_b.f(), mean_out + (size_t)n0 * hl * hl * S.LC, S.LC, rows, 2 * S.LC, 2 * S.LC, S.LC);
-    LDP_HIP(hipGetLastError());
-  }
-  return LDP_OK;
+  return encode_all(h, img, mean_out, N, V(h)->LC, stream);
+}
+
+int ldp_vae_moments(ldp_handle* h, const float* img, float* moments_out, int32_t N, void* stream) {
+  if (!h || !img || !moments_out || N <= 0) return fail(LDP_EINVAL, "bad argument");
+  if (!h->vae || !V(h)->enc_ready) return fail(LDP_ESTATE, "vae weights not finalized");
+  LDP_TRY(entry_fault_check(h));
+  return encode_all(h, img, moments_out, N, 2 * V(h)->LC, stream);
 }
 
 int ldp_vae_decode(ldp_handle* h, const float* z, float* img_out, int32_t N, void* stream) {
@@ -778,46 +838,66 @@ int ldp_vae_decode(ldp_handle* h, const float* z, float* img_out, int32_t N, voi
   if (!h->vae || !V(h)->dec_ready) return fail(LDP_ESTATE, "vae decoder weights not finalized");
   LDP_TRY(entry_fault_check(h));
   VaeState& S = *V(h);
-  hipStream_t s = (hipStream_t)stream;
-  const int CHUNK = 256;
-  const int NB = (int)S.ch.size();
-  const int hl = S.S >> (NB - 1);
-  for (int n0 = 0; n0 < N; n0 += CHUNK) {
-    const int n = std::min(CHUNK, N - n0);
-    LDP_TRY(workspace(h, n));
-    Run R{h, S, s};
-    float *cur = S.b0.f(), *o1 = S.b1.f(), *t0 = S.b2.f(), *t1 = S.b3.f();
-    int H = hl;
-    const int64_t rows = (int64_t)n * hl * hl;
-    // post_quant 1x1 (LC -> LC) into a 64-channel zero-padded tensor (the conv kernel's channel chunk)
-    LDP_HIP(hipMemsetAsync(t0, 0, (size_t)rows * 64 * 4, s));
-    R.wrote(t0);
-    hipLaunchKernelGGL(tiny_dense_kernel, dim3(nblk(rows * S.LC)), dim3(256), 0, s, z + (size_t)n0 * hl * hl * S.LC,
-                       S.LC, S.pq_w.f(), S.pq_b.f(), t0, 64, rows, S.LC, S.LC, S.LC);
-    LDP_TRY(R.conv3(S.dconv_in, t0, cur, n, H, H, 1, nullptr));
-    LDP_TRY(R.mid(S.dmid, cur, o1, t0, t1, n, H, H));
-    for (int i = 0; i < NB; ++i) {
-      for (int j = 0; j < 3; ++j) {
-        LDP_TRY(R.res(S.up[i].r[j], cur, o1, t0, t1, S.b4.f(), n, H, H));
-        std::swap(cur, o1);
-      }
-      if (S.up[i].has_us) {
-        const int C = S.up[i].us.cin;
-        const int64_t tot = (int64_t)n * 4 * H * H * (C / 4);
-        hipLaunchKernelGGL(upsample2_kernel, dim3(nblk(tot)), dim3(256), 0, s, cur, t0, n, H, H, C);
-        R.wrote(t0);
-        H *= 2;
-        LDP_TRY(R.conv3(S.up[i].us, t0, o1, n, H, H, 1, nullptr));
-        std::swap(cur, o1);
-      }
-    }
-    LDP_TRY(R.gn_conv3(S.dnorm, S.dconv_out, cur, t1, t0, n, H, H, nullptr));          // (n, S, S, 32): first 3 real
-    const int64_t tot = (int64_t)n * 3 * H * H;
-    hipLaunchKernelGGL(nhwc_to_nchw3_kernel, dim3(nblk(tot)), dim3(256), 0, s, t1,
-                       img_out + (size_t)n0 * 3 * H * H, n, H * H, 32);
-    LDP_HIP(hipGetLastError());
-  }
+  const int hl = S.S >> ((int)S.ch.size() - 1);
+  for (int n0 = 0; n0 < N; n0 += VAE_CHUNK)
+    LDP_TRY(decode_chunk(h, S, (hipStream_t)stream, z + (size_t)n0 * hl * hl * S.LC, std::min(VAE_CHUNK, N - n0),
+                         img_out + (size_t)n0 * 3 * S.S * S.S));
   return LDP_OK;
+}
+
+int ldp_vae_posterior(ldp_handle* h, const float* moments, const float* eps, uint64_t seed, int64_t row_offset, float* z_out,
+                      float* std_out, float* kl_out, float* stats_out, int32_t N, void* stream) {
+  if (!h || !moments || !z_out || !kl_out || N <= 0 || row_offset < 0) return fail(LDP_EINVAL, "bad argument");
+  const int S_ = h->cfg.image_size > 0 ? h->cfg.image_size : 64, LC = h->cfg.vae_latent_channels > 0 ? h->cfg.vae_latent_channels : 4;
+  const int hl = S_ / 32;
+  if (hl < 1 || hl * hl * LC > 256) return fail(LDP_EINVAL, "posterior: latent (%d, %d, %d) has more than 256 elements", hl, hl, LC);
+  if (!h->vae) h->vae = new VaeState();                    // workspace only: no weights are read
+  VaeState& S = *V(h);
+  hipStream_t s = (hipStream_t)stream;
+  const int nzb = vae_posterior_blocks(N, hl * hl, LC);
+  LDP_TRY(S.zpart.alloc((size_t)nzb * 6 * sizeof(double)));
+  LDP_TRY(vae_posterior_launch(moments, eps, seed, (uint64_t)row_offset, z_out, std_out, kl_out, S.zpart.as<double>(), N, hl * hl, LC, s));
+  if (stats_out) LDP_TRY(vae_moment_final_launch(S.zpart.as<double>(), nzb, stats_out, s));
+  return LDP_OK;
+}
+
+int ldp_vae_metrics(ldp_handle* h, const float* img, int32_t N, int32_t use_kl, float beta, const float* eps, uint64_t seed,
+                    int64_t row_offset, float* metrics_out, float* z_out, float* rec_out, void* stream) {
+  if (!h || !img || !metrics_out || N <= 0 || row_offset < 0) return fail(LDP_EINVAL, "bad argument");
+  if (!h->vae || !V(h)->enc_ready) return fail(LDP_ESTATE, "vae weights not finalized");
+  if (!V(h)->dec_ready) return fail(LDP_ESTATE, "vae decoder weights not finalized");
+  LDP_TRY(entry_fault_check(h));
+  VaeState& S = *V(h);
+  hipStream_t s = (hipStream_t)stream;
+  const int hl = S.S >> ((int)S.ch.size() - 1), E = hl * hl, LC = S.LC, HW = S.S * S.S;
+  if (E * LC > 256) return fail(LDP_EINVAL, "metrics: latent (%d, %d, %d) has more than 256 elements", hl, hl, LC);
+  // every chunk but the last holds VAE_CHUNK images, so block counts per chunk are fixed and partials of chunk k start at k * (per chunk)
+  const int nchunks = (N + VAE_CHUNK - 1) / VAE_CHUNK;
+  const int zb_full = vae_posterior_blocks(VAE_CHUNK, E, LC), ib_full = vae_loss_blocks((int64_t)VAE_CHUNK * HW);
+  LDP_TRY(S.mom.alloc((size_t)N * E * 2 * LC * 4));
+  LDP_TRY(S.klv.alloc((size_t)N * 4));
+  if (!z_out) LDP_TRY(S.zlat.alloc((size_t)N * E * LC * 4));
+  if (!rec_out) LDP_TRY(S.rec.alloc((size_t)std::min(N, VAE_CHUNK) * 3 * HW * 4));
+  LDP_TRY(S.zpart.alloc((size_t)nchunks * zb_full * 6 * sizeof(double)));
+  LDP_TRY(S.ipart.alloc((size_t)nchunks * ib_full * 6 * sizeof(double)));
+  float* zall = z_out ? z_out : S.zlat.f();
+  int nzp = 0, nip = 0;
+  for (int n0 = 0; n0 < N; n0 += VAE_CHUNK) {
+    const int n = std::min(VAE_CHUNK, N - n0);
+    const float* x = img + (size_t)n0 * HW * 3;
+    float* mom = S.mom.f() + (size_t)n0 * E * 2 * LC;
+    float* z = zall + (size_t)n0 * E * LC;
+    float* rec = rec_out ? rec_out + (size_t)n0 * 3 * HW : S.rec.f();
+    LDP_TRY(encode_chunk(h, S, s, x, n, mom, 2 * LC));
+    LDP_TRY(vae_posterior_launch(mom, eps ? eps + (size_t)n0 * E * LC : nullptr, seed, (uint64_t)row_offset + (uint64_t)n0, z, nullptr,
+                                 S.klv.f() + n0, S.zpart.as<double>() + (size_t)nzp * 6, n, E, LC, s));
+    nzp += vae_posterior_blocks(n, E, LC);
+    // the decoder reuses b0..b4; what the loss reads of the encoder side is the caller's frames, and moments / z live outside them
+    LDP_TRY(decode_chunk(h, S, s, z, n, rec));
+    LDP_TRY(vae_loss_stats_launch(x, rec, (int64_t)n * HW, HW, S.ipart.as<double>() + (size_t)nip * 6, s));
+    nip += vae_loss_blocks((int64_t)n * HW);
+  }
+  return vae_metrics_final_launch(S.ipart.as<double>(), nip, S.zpart.as<double>(), nzp, S.klv.f(), N, use_kl != 0, beta, metrics_out, s);
 }
 
 }  // extern "C"

@@ -335,6 +335,63 @@ class HipEngine:
         self.call_seq += 1
         return out
 
+    def vae_moments(self, img_nhwc: torch.Tensor) -> torch.Tensor:
+        """The full quant_conv output (N, S/32, S/32, 2 LC): channels [0, LC) the posterior mean (the bits of vae_encode), [LC, 2 LC) the
+        unclamped log-variance."""
+        img = _f32(img_nhwc, self.device)
+        n, s = img.shape[0], img.shape[1]
+        _want("img_nhwc", img, (n, self.image_size, self.image_size, 3))
+        out = torch.empty((n, s // 32, s // 32, 2 * self.latent_channels), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_vae_moments(self._h, _ptr(img), _ptr(out), n, self._stream()))
+        self.call_seq += 1
+        return out
+
+    def _vae_noise_args(self, noise, n, seed, row_offset):
+        s = self.image_size // 32
+        eps = None if noise is None else _f32(noise, self.device)
+        _want("noise", eps, (n, s, s, self.latent_channels))
+        if int(row_offset) < 0:
+            raise ValueError(f"row_offset must be >= 0, got {row_offset}")
+        return eps, C.c_uint64(int(seed) & (2**64 - 1)), C.c_int64(int(row_offset))
+
+    def vae_posterior(self, moments: torch.Tensor, noise: Optional[torch.Tensor] = None, seed: int = 0, row_offset: int = 0):
+        """z = mean + exp(0.5 clip(logvar, -30, 20)) * eps and the per-image KL of (N, S/32, S/32, 2 LC) moments; eps = `noise` or the
+        Philox stream (seed, global element, PHILOX_STREAM_VAE_EPS).  -> z (N, s, s, LC), std (same), kl (N,), (min, max, mean, std) of z."""
+        m = _f32(moments, self.device)
+        n, s, lc = m.shape[0], self.image_size // 32, self.latent_channels
+        _want("moments", m, (n, s, s, 2 * lc))
+        eps, seed_c, row_c = self._vae_noise_args(noise, n, seed, row_offset)
+        z = torch.empty((n, s, s, lc), device=self.device, dtype=torch.float32)
+        std, kl = torch.empty_like(z), torch.empty((n,), device=self.device, dtype=torch.float32)
+        stats = torch.empty((4,), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_vae_posterior(self._h, _ptr(m), _ptr(eps), seed_c, row_c, _ptr(z), _ptr(std), _ptr(kl), _ptr(stats), n,
+                                         self._stream()))
+        return z, std, kl, stats
+
+    def vae_metrics(self, img_nhwc: torch.Tensor, use_kl: bool = True, beta: float = 1e-5, seed: int = 0,
+                    noise: Optional[torch.Tensor] = None, row_offset: int = 0, want: Sequence[str] = ()):
+        """StableVAEModel.loss forward in ONE call: the eleven scalars as an (11,) device tensor in _lib.VAE_METRIC_KEYS order.
+        want: any of "z" (the posterior draw, (N, s, s, LC) NHWC) and "rec" (the reconstruction, (N, 3, S, S)) -> (metrics, {name: tensor})."""
+        img = _f32(img_nhwc, self.device)
+        n, s = img.shape[0], self.image_size
+        _want("img_nhwc", img, (n, s, s, 3))
+        bad = [w for w in want if w not in ("z", "rec")]
+        if bad:
+            raise ValueError(f"want={bad}: vae_metrics can return 'z' and 'rec'")
+        if not np.isfinite(float(beta)):
+            raise ValueError(f"beta must be finite, got {beta}")
+        eps, seed_c, row_c = self._vae_noise_args(noise, n, seed, row_offset)
+        out = torch.empty((len(_lib.VAE_METRIC_KEYS),), device=self.device, dtype=torch.float32)
+        extra = {}
+        if "z" in want:
+            extra["z"] = torch.empty((n, s // 32, s // 32, self.latent_channels), device=self.device, dtype=torch.float32)
+        if "rec" in want:
+            extra["rec"] = torch.empty((n, 3, s, s), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_vae_metrics(self._h, _ptr(img), n, int(bool(use_kl)), C.c_float(float(beta)), _ptr(eps), seed_c, row_c,
+                                       _ptr(out), _ptr(extra.get("z")), _ptr(extra.get("rec")), self._stream()))
+        self.call_seq += 1              # ONE call for the fault protocol, like vae_encode / vae_decode
+        return out, extra
+
     # -- elementwise ----------------------------------------------------------------------------
     def normalize_bounds(self, x: torch.Tensor, lo, hi, normalize) -> torch.Tensor:
         """normalize: True/1 -> to [-1,1]; False/0 -> back (+clip); 2 -> plain clip to [lo, hi]."""

@@ -353,3 +353,18 @@ def eval_loss_metrics(policy, batch: dict, rng) -> dict:
         per_index("full_action_mse", pred_action_full)
         metrics["plan_mse"] = float(stats["plan_mse"])
     return metrics
+
+
+def eval_vae_metrics(model, batches, rng, max_batches: int = 11) -> dict:
+    """The evaluation loop of train_vae.py:146-157 on a StableVAEModel: `get_metrics` on up to `max_batches` held-out batches, the mean of
+    every key over the batches, prefixed `evaldata/`.  `rng` seeds batch i with rng + i (the reference splits its key once per batch)."""
+    from .agent import _seed_of
+    seed = _seed_of(rng)
+    all_metrics = []
+    for i, batch in enumerate(batches):
+        if i >= max_batches:
+            break
+        all_metrics.append({k: float(v) for k, v in model.get_metrics(batch, seed + i).items()})
+    if not all_metrics:
+        raise ValueError("eval_vae_metrics: no batches")
+    return {f"evaldata/{k}": float(np.mean([m[k] for m in all_metrics])) for k in all_metrics[0]}

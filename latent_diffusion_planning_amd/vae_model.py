@@ -1,0 +1,243 @@
+"""StableVAEModel -- the reference's VAE model class (model/stable_vae_model.py:18-175) on the HIP engine, forward side.
+
+`create`, `.vae_state` (`.params`, `.ema_params`, `.step`, `.replace`), `.config[...]`, `.obs_normalization`, `.replace`, `get_params`,
+`get_metrics`, `reconstruct` and `sample` have the reference's names, argument meaning and return structure: what `train_vae.py:140-230`
+calls at every evaluation.  `update` (the backward pass of the 2-D convolutions, Adam and the EMA on the VAE arena) is not built and raises.
+
+Deliberate differences, the same as for the agents (agent.py):
+  * `rng`: an int seed, a uint32[2] key or a torch.Generator seeds the in-kernel Philox stream (JAX's threefry stream is a non-goal);
+    `noise=` gives the explicit-noise parity mode (`get_metrics`: the eps of the posterior draw; `sample`: the four latents).
+  * metrics are device-resident scalars that read like the reference's 0-d arrays (`float(m["loss"])`, `np.mean([...])`); images are
+    `arrays.DeviceArray`s.
+  * `get_metrics` concatenates the cameras of `rgb_obs` on the batch axis like the reference (:28), so more than one camera works here.
+  * `params` and `ema_params` are two weight sets for ONE engine slot: each has a version token and is uploaded only when the slot holds
+    something else (a loop of `get_metrics` calls uploads nothing; a `reconstruct` in between swaps the EMA in and back).
+"""
+from __future__ import annotations
+
+import copy
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import weights as W
+from .agent import _Elem, _EngineCalls, _get, _norm_entry, _philox_normal, _seed_of
+from .arrays import DeviceArray
+from .dp_vae_agent import DPState
+from .engine import HipEngine
+
+IMAGE_SIZES = (64, 96, 128)               # what the 3x3 conv tiles of csrc/vae.hip are built for (latent side 2 / 3 / 4)
+LATENT_CHANNELS = (4, 8)
+PHILOX_STREAM_VAE_SAMPLE = 10             # the four latents of sample(): a stream of its own (include/ldp_hip.h lists them)
+SAMPLE_COUNT = 4                          # model/stable_vae_model.py:112
+
+
+def _check_vae_cfg(vae) -> W.VAESpec:
+    """The `vae:` mapping of model/stable_vae_model.yaml:4-16 against what the engine builds; anything else is refused with the reason."""
+    ref = W.VAESpec()
+    n = len(ref.block_out_channels)
+    down = list(_get(vae, "down_block_types", ["DownEncoderBlock2D"] * n))
+    up = list(_get(vae, "up_block_types", ["UpDecoderBlock2D"] * n))
+    if len(down) != n or any(str(b) != "DownEncoderBlock2D" for b in down):
+        raise NotImplementedError(f"vae.down_block_types={down}: the engine builds {n} DownEncoderBlock2D stages (n_downsample = {n})")
+    if len(up) != n or any(str(b) != "UpDecoderBlock2D" for b in up):
+        raise NotImplementedError(f"vae.up_block_types={up}: the engine builds {n} UpDecoderBlock2D stages")
+    ch = tuple(int(c) for c in _get(vae, "block_out_channels", ref.block_out_channels))
+    if ch != ref.block_out_channels:
+        raise NotImplementedError(f"vae.block_out_channels={ch}: the engine builds {ref.block_out_channels}")
+    for key, want in (("layers_per_block", ref.layers_per_block), ("norm_num_groups", ref.norm_num_groups),
+                      ("in_channels", ref.in_channels), ("out_channels", ref.out_channels)):
+        got = int(_get(vae, key, want))
+        if got != want:
+            raise NotImplementedError(f"vae.{key}={got}: the engine builds {want}")
+    act = str(_get(vae, "act_fn", "silu"))
+    if act not in ("silu", "swish"):
+        raise NotImplementedError(f"vae.act_fn={act!r}: the GroupNorm kernels fuse silu")
+    lc = int(_get(vae, "latent_channels", ref.latent_channels))
+    if lc not in LATENT_CHANNELS:
+        raise NotImplementedError(f"vae.latent_channels={lc}: built for {LATENT_CHANNELS}")
+    return W.VAESpec(latent_channels=lc)
+
+
+class StableVAEModel(_EngineCalls):
+    def __init__(self, vae_state: DPState, obs_normalization, config, engine: Optional[HipEngine], vae_spec: W.VAESpec, image_size: int,
+                 device, lr_schedule=None, ema_decay: float = 0.99):
+        self.vae_state = vae_state
+        self.ema_decay = float(ema_decay)            # kept for the training step that is not built yet (TrainStateEMA.apply_ema)
+        self.obs_normalization = obs_normalization
+        self.config = config
+        self.lr_schedule = lr_schedule
+        self._engine = engine
+        self._vae_spec = vae_spec
+        self._image_size = int(image_size)
+        self._device = device
+        self._uploads = [0]                   # weight uploads of this model and its .replace copies (they share the engine)
+
+    # ---------------------------------------------------------------------------------------------
+    @classmethod
+    def create(cls, rng, batch, shape_meta, *,
+               # Hydra config (model/stable_vae_model.yaml)
+               name, vae, rgb_obs, obs_normalization,
+               lr, end_lr, warmup_steps, decay_steps, ema_decay,
+               use_kl, beta, data_name, device=None, exclusive_gpu=True):
+        """model/stable_vae_model.py:128-175.  `batch` is accepted for signature parity; the frame size comes from `shape_meta`
+        (64 when it does not list the cameras, the reference's `jnp.zeros((2, 3, 64, 64))` of :139)."""
+        rgb_obs = list(rgb_obs)
+        if not rgb_obs:
+            raise ValueError("rgb_obs is empty: the VAE trains on at least one camera")
+        spec = _check_vae_cfg(vae)
+        sizes = set()
+        for k in rgb_obs:
+            shp = (shape_meta or {}).get("all_shapes", {}).get(k)
+            if shp is None:
+                continue
+            shp = tuple(int(v) for v in shp)
+            if len(shp) != 3 or shp[0] != shp[1] or shp[2] != 3:
+                raise NotImplementedError(f"image key {k!r} has shape {shp}: the StableVAE takes square (S, S, 3) frames")
+            sizes.add(shp[0])
+        if len(sizes) > 1:
+            raise NotImplementedError(f"rgb_obs cameras of different sizes {sorted(sizes)}: they are concatenated on the batch axis")
+        image_size = sizes.pop() if sizes else 64
+        if image_size not in IMAGE_SIZES:
+            raise NotImplementedError(f"{image_size}-pixel frames: the 3x3 conv tiles are built for {IMAGE_SIZES} pixel squares")
+        decay = float(ema_decay)
+        if not 0.0 <= decay <= 1.0:
+            raise ValueError(f"ema_decay={decay} must lie in [0, 1]")
+        if not np.isfinite(float(beta)):
+            raise ValueError(f"beta={beta} must be finite")
+        seed = _seed_of(rng)
+        params = W.init_vae_params(spec, seed=seed * 3 + 1, perturb=False)
+        state = DPState(params, None, ema_is_params=True)                     # TrainStateEMA.create(..., ema_params=params) (:157-163)
+        from .schedule import warmup_cosine_decay_schedule
+        sched = warmup_cosine_decay_schedule(float(end_lr), float(lr), int(warmup_steps), int(decay_steps), float(end_lr))   # :144-150
+        config = dict(rgb_obs=rgb_obs, name=name, use_kl=use_kl, beta=beta, n_downsample=len(spec.block_out_channels),
+                      data_name=data_name)                                     # :166-169, the reference's six keys
+        norm = {"obs": {k: _norm_entry(v) for k, v in dict(obs_normalization["obs"]).items()}}
+        if "actions" in obs_normalization:
+            norm["actions"] = _norm_entry(obs_normalization["actions"])
+        missing = [k for k in rgb_obs if k not in norm["obs"]]
+        if missing:
+            raise KeyError(f"obs_normalization has no entry for the camera(s) {missing}")
+        if not torch.cuda.is_available():
+            raise _lib.LDPHipUnavailable("no HIP device visible: StableVAEModel has no CPU fallback")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        # the handle's planner / IDM slots stay empty: the smallest shapes the library accepts
+        engine = HipEngine(obs_dim=25, action_dim=7, global_cond_dim=25, pred_horizon=8, action_horizon=4, image_size=image_size,
+                           vae_latent_channels=spec.latent_channels, device=dev)
+        if not exclusive_gpu:
+            engine.set_option("safe_mode", 1)
+        return cls(state, norm, config, engine, spec, image_size, dev, lr_schedule=sched, ema_decay=decay)
+
+    # ---------------------------------------------------------------------------------------------
+    def replace(self, **fields):
+        """flax.struct `.replace`: a shallow copy sharing the engine (weights re-upload lazily, by version token)."""
+        new = copy.copy(self)
+        for k, v in fields.items():
+            if k not in ("vae_state", "obs_normalization", "config", "lr_schedule"):
+                raise AttributeError(f"StableVAEModel has no field {k!r}")
+            setattr(new, k, v)
+        return new
+
+    def get_params(self):
+        """model/stable_vae_model.py:125-126: the names train_vae.py saves and load_pretrained_vae looks for."""
+        return dict(vae_params=self.vae_state.params, ema_params=self.vae_state.ema_params)
+
+    @property
+    def uploads(self) -> int:
+        """How many times this model (or a .replace copy) put a weight set into the engine."""
+        return self._uploads[0]
+
+    def _sync_weights(self, use_ema: bool) -> None:
+        """The engine's VAE slot must hold `params` (get_metrics) or `ema_params` (reconstruct, sample): each set has its own token."""
+        st, eng = self.vae_state, self._engine
+        want = st.ema_version if use_ema else st.version
+        if eng.loaded["vae"] == want:
+            return
+        tree = st.ema_params if use_ema else st.params
+        W.check_params(tree, W.vae_shapes(self._vae_spec))
+        eng.load_params(vae=tree, versions={"vae": want})
+        self._uploads[0] += 1
+
+    # ---- model/stable_vae_model.py:28 after postprocess_batch (utils/data_utils.py:70-80) ------------------------------------------
+    def _frames(self, batch, keys) -> torch.Tensor:
+        """Frame 0 of every key, normalised with the camera's own bounds, concatenated on the BATCH axis -> (len(keys) * B, S, S, 3) NHWC
+        (the reference transposes to NCHW for Flax's wrapper, which transposes back)."""
+        obs = batch["obs"]
+        table = self.obs_normalization["obs"]
+        assert set(obs.keys()).issubset(table), f"obs_normalization keys {table.keys()} do not match batch keys {obs.keys()}"
+        S = self._image_size
+        out = []
+        for k in keys:
+            v = self._t(obs[k])
+            if v.dim() != 5 or tuple(v.shape[2:]) != (S, S, 3):
+                raise ValueError(f"batch['obs'][{k!r}] must have shape (B, H, {S}, {S}, 3), got {tuple(v.shape)}")
+            out.append(self._apply_norm(v[:, 0].contiguous(), table[k], True))
+        return out[0] if len(out) == 1 else torch.cat(out, dim=0).contiguous()
+
+    # ---- model/stable_vae_model.py:25-55, 75-87 ---------------------------------------------------------------------------------------
+    def get_metrics(self, batch, rng, noise=None, row_offset: int = 0):
+        """`get_metrics_step` on `params`: ONE ldp_vae_metrics call -> the eleven keys of `loss` (img_min / max / mean / std, loss, loss_mse,
+        loss_kl, z_min / max / mean / std).  noise: optional eps (frames, S/32, S/32, LC) of the posterior draw for parity runs;
+        row_offset: global index of the first frame (the Philox eps of a frame does not depend on how a batch is sharded)."""
+        seed = _seed_of(rng)
+        use_kl, beta = bool(self.config["use_kl"]), float(self.config["beta"])
+        eps = None if noise is None else self._t(noise)
+
+        def run():
+            self._sync_weights(use_ema=False)
+            img = self._frames(batch, self.config["rgb_obs"])
+            return [self._engine.vae_metrics(img, use_kl, beta, seed=seed, noise=eps, row_offset=row_offset)[0]]
+        rec = self._record(run)
+        res = self._guarded(run)
+        rec.seqs = self._seqs()
+        vec = DeviceArray(res[0], record=rec)
+        return {k: _Elem(vec, i) for i, k in enumerate(_lib.VAE_METRIC_KEYS)}
+
+    # ---- model/stable_vae_model.py:89-101 --------------------------------------------------------------------------------------------
+    def reconstruct(self, batch, rng, rgb_key):
+        """decode(encode(frame 0 of `rgb_key`).latent_dist.mode()) on `ema_params` -> (B, 3, S, S).  The mode of the diagonal Gaussian is
+        its mean, which is what vae_encode returns; `rng` is unused, as in the reference."""
+        if rgb_key not in batch["obs"]:
+            raise KeyError(f"batch['obs'] has no {rgb_key!r}")
+
+        def run():
+            self._sync_weights(use_ema=True)
+            img = self._frames(batch, [rgb_key])
+            return [self._engine.vae_decode(self._engine.vae_encode(img))]
+        rec = self._record(run)
+        res = self._guarded(run)
+        rec.seqs = self._seqs()
+        return DeviceArray(res[0], record=rec)
+
+    # ---- model/stable_vae_model.py:103-123 -------------------------------------------------------------------------------------------
+    def sample(self, rng, noise=None):
+        """decode of four N(0, I) latents (4, 2, 2, LC) on `ema_params` -> (4, 3, 64, 64): the `n_downsample == 6` branch (z_dim = 2).
+        noise: the latents themselves, for parity runs."""
+        if self.config["n_downsample"] != 6:
+            raise NotImplementedError                                            # :110-111
+        if self._image_size != 64:
+            raise NotImplementedError(f"sample(): the reference draws (4, 2, 2, LC) latents for n_downsample == 6, i.e. 64-pixel frames; this "
+                                      f"model was built for {self._image_size}-pixel frames, whose latent side is {self._image_size // 32}")
+        seed = _seed_of(rng)
+        shape = (SAMPLE_COUNT, 2, 2, self._vae_spec.latent_channels)
+        z_in = None if noise is None else self._t(noise)
+        if z_in is not None and tuple(z_in.shape) != shape:
+            raise ValueError(f"noise must have shape {shape}, got {tuple(z_in.shape)}")
+
+        def run():
+            self._sync_weights(use_ema=True)
+            z = z_in if z_in is not None else _philox_normal(seed, 0, 0, PHILOX_STREAM_VAE_SAMPLE, int(np.prod(shape)),
+                                                             self._device).reshape(shape)
+            return [self._engine.vae_decode(z)]
+        rec = self._record(run)
+        res = self._guarded(run)
+        rec.seqs = self._seqs()
+        return DeviceArray(res[0], record=rec)
+
+    # ---- model/stable_vae_model.py:57-73 ---------------------------------------------------------------------------------------------
+    def update(self, batch, rng, step):
+        raise NotImplementedError("StableVAEModel.update: the backward pass of the 2-D convolutions (3x3 / stride-2 / attention blocks), Adam "
+                                  "and the EMA on the VAE arena are not built; train the VAE with the reference and import its snapshot "
+                                  "(checkpoint.load_snapshot)")
