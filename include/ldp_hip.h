@@ -255,7 +255,7 @@ LDP_API int ldp_reduce_stats(const float* x, int64_t n, float* out4, void* strea
 
 /* -- training step (agent/ldp_agent.py:113-180 losses, :223-272 update / update_step, :274-323 update_mixed) ------------------------
  * The reference's step is `grads = jax.grad(loss)(params)`, `g_norm = optax.global_norm(grads)`, one `TrainState.apply_gradients` per
- * network with tx = optax.adam(warmup_cosine_decay_schedule) (:583-596, :621-634).  Here the handle keeps, per module (1 planner, 2 idm),
+ * network with tx = optax.adam(warmup_cosine_decay_schedule) (:583-596, :621-634).  Here the handle keeps, per module (1 planner, 2 idm, 4 vae),
  * fp32 master parameters, gradients and the two Adam moments as flat arenas in the reference's Flax leaf layouts; every GEMM-shaped
  * piece of the forward and backward pass (Dense, k = 5 / stride-2 / transposed / 1x1 convolutions, dgrad and wgrad) runs on the exact-fp32
  * MFMA (csrc/train.hip).  Timesteps and noise are inputs (the reference draws them from its JAX key inside the traced step); the caller
@@ -279,6 +279,18 @@ LDP_API int ldp_train_planner_grad(ldp_handle* h, const float* x0, const float* 
 /* alpha * idm_loss (agent/ldp_agent.py:129-140, 154) and its gradient: s (R, 2D) = s_sprime rows, a0 / noise (R, A), t_dev (R). */
 LDP_API int ldp_train_idm_grad(ldp_handle* h, const float* s, const float* a0, const float* noise, const int32_t* t_dev, float alpha,
                                float* loss_out, int32_t R, void* stream);
+
+/* StableVAEModel.loss (model/stable_vae_model.py:25-55, 57-73) and its gradient w.r.t. every leaf of module 4 (vae; ldp_train_init(h, 4)):
+ *   moments = encoder(img); z = mean + exp(clip(logvar, -30, 20) / 2) eps; rec = decoder(z); loss = mse(img, rec) + beta mean(kl) (use_kl)
+ * on the module's master parameters, exact fp32 forward with saved activations, hand-written backward (csrc/vae_train.hpp).  The gradients
+ * replace module 4's gradient arena; metrics_out receives the LDP_VAE_N_METRICS scalars in LDP_VAE_METRIC_* order as device floats.
+ * img (N, S, S, 3) NHWC normalised to [-1, 1]; eps / seed / row_offset as ldp_vae_metrics (explicit (N, S/32, S/32, LC) noise, or Philox
+ * stream LDP_PHILOX_STREAM_VAE_EPS element (row_offset + n) * (S/32)^2 * LC + e).  64-pixel frames, 1 <= N <= 256 per call (LDP_EINVAL
+ * otherwise, with the limit in the message); no atomics: the same state and batch give the same gradients bit for bit.
+ * Module bit 4 also takes part in ldp_train_apply / _ema / _step_count / _read / _write / _arena / _publish(_ema) (which rebuild the
+ * VAE's sampling weights) / _grad_norm; a handle created with image_size = 0 refuses it with LDP_EINVAL. */
+LDP_API int ldp_train_vae_grad(ldp_handle* h, const float* img_nhwc, int32_t N, int32_t use_kl, float beta, const float* eps, uint64_t seed,
+                               int64_t row_offset, float* metrics_out, void* stream);
 
 /* optax.global_norm over the gradient arenas of the listed modules (agent/ldp_agent.py:253) -> out[0] (device scalar).  Two-stage
  * reduction in a fixed order (bit-reproducible).  Called AFTER ldp_train_apply of the same gradients it costs one small launch: the optimiser

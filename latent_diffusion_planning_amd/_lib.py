@@ -104,6 +104,7 @@ SIGNATURES: Dict[str, tuple] = {
     "ldp_train_init": (C.c_int, [_H, C.c_int32, C.c_void_p]),
     "ldp_train_planner_grad": (C.c_int, [_H, _FP, _FP, _FP, _FP, C.c_float, _FP, C.c_int32, C.c_void_p]),
     "ldp_train_idm_grad": (C.c_int, [_H, _FP, _FP, _FP, _FP, C.c_float, _FP, C.c_int32, C.c_void_p]),
+    "ldp_train_vae_grad": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_float, _FP, C.c_uint64, C.c_int64, _FP, C.c_void_p]),
     "ldp_train_grad_norm": (C.c_int, [_H, C.c_int32, _FP, C.c_void_p]),
     "ldp_train_apply": (C.c_int, [_H, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "ldp_train_step_count": (C.c_int, [_H, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),

@@ -1094,7 +1094,8 @@ struct Module {
     l.shape = shape;
     if (shape.size() == 1) { l.cols = (int)shape[0]; }
     else if (shape.size() == 2) { l.rows = (int)shape[0]; l.cols = (int)shape[1]; }
-    else { l.taps = (int)shape[0]; l.rows = (int)shape[1]; l.cols = (int)shape[2]; }
+    else if (shape.size() == 3) { l.taps = (int)shape[0]; l.rows = (int)shape[1]; l.cols = (int)shape[2]; }
+    else { l.taps = (int)(shape[0] * shape[1]); l.rows = (int)shape[2]; l.cols = (int)shape[3]; }      // 2-D conv kernel (kh, kw, Cin, Cout)
     l.rows_p = rows_p < 0 ? l.rows : rows_p;
     l.cols_p = cols_p < 0 ? l.cols : cols_p;
     l.off = total;
@@ -1144,6 +1145,10 @@ struct Trainer {
   int IH = 0, INP = 0, NB = 0, TD = 0;                                           // IDM hidden, padded input width, blocks, time dim
   std::vector<int> dims, Tl;
   Module pl, idm;
+  Module vae;                      // StableVAE (vae_train.hpp): described by the first ldp_train_init that asks for bit 4
+  bool vae_described = false;
+  std::map<std::string, ConvPlan> vconvs;      // its 2-D convolutions' tables, built on the first call for a frame size
+  bool tables_dirty = false;       // h_segs / h_batches grew since the last upload
   // launch tables
   std::vector<GemmSeg> h_segs;
   std::vector<GemmBatch> h_batches;
@@ -1160,7 +1165,7 @@ struct Trainer {
   std::vector<std::pair<int, int>> film_of;      // block -> (group, slot)
   // tables and workspaces
   DevBuf sintab_p, sintab_i;       // (n_train, E) sin|cos and (n_train, TD) cos|sin
-  Lane lane[2];                    // [0] the planner's tape, [1] the IDM's: nothing mutable is shared, the two may be enqueued on different streams
+  Lane lane[3];                    // [0] the planner's tape, [1] the IDM's, [2] the VAE's: nothing mutable is shared, they may be enqueued on different streams
 };
 
 Trainer* trainer(ldp_handle* h) { return static_cast<Trainer*>(h->train); }
@@ -1593,6 +1598,7 @@ Module* module_of(ldp_handle* h, int32_t module, const char** prefix) {
   Trainer* t = trainer(h);
   if (module == 1) { if (prefix) *prefix = "planner/"; return &t->pl; }
   if (module == 2) { if (prefix) *prefix = "idm/"; return &t->idm; }
+  if (module == 4 && t->vae_described) { if (prefix) *prefix = "vae/"; return &t->vae; }
   return nullptr;
 }
 
@@ -2069,6 +2075,8 @@ int idm_tape(Ctx& c, const float* s_in, const float* a0, const float* noise, con
   return LDP_OK;
 }
 
+#include "vae_train.hpp"
+
 // size the workspace with a dry walk of the tape, then enqueue it
 template <class F>
 int run_tape(ldp_handle* h, int lane, hipStream_t s, F&& tape) {
@@ -2100,7 +2108,7 @@ int need_module(ldp_handle* h, int32_t module, Module** out) {
   if (!h) return fail(LDP_EINVAL, "null handle");
   if (!h->train) return fail(LDP_ESTATE, "ldp_train_init was not called");
   Module* m = module_of(h, module, nullptr);
-  if (!m) return fail(LDP_EINVAL, "module must be 1 (planner) or 2 (idm), got %d", module);
+  if (!m) return fail(module == 4 ? LDP_ESTATE : LDP_EINVAL, module == 4 ? "ldp_train_init was not called for module %d" : "module must be 1 (planner), 2 (idm) or 4 (vae), got %d", module);
   if (!m->ready) return fail(LDP_ESTATE, "ldp_train_init was not called for module %d", module);
   *out = m;
   return LDP_OK;
@@ -2121,14 +2129,19 @@ extern "C" {
 
 int ldp_train_init(ldp_handle* h, int32_t modules, void* stream) {
   if (!h) return fail(LDP_EINVAL, "null handle");
-  if (!(modules & 3) || (modules & ~3)) return fail(LDP_EINVAL, "modules must be a mask of 1 (planner) and 2 (idm)");
+  if (!(modules & 7) || (modules & ~7)) return fail(LDP_EINVAL, "modules must be a mask of 1 (planner), 2 (idm) and 4 (vae)");
+  if ((modules & 4) && h->cfg.image_size <= 0) return fail(LDP_EINVAL, "module 4 (vae): this handle was created with image_size = 0, it has no StableVAE");
   LDP_HIP(hipSetDevice(h->cfg.device));
   LDP_TRY(ensure_trainer(h));
   LDP_HIP(hipDeviceSynchronize());                                      // (the module's lane may have work on other streams than `stream`)
-  for (int bit = 1; bit <= 2; bit <<= 1) {
+  if ((modules & 4) && !trainer(h)->vae_described) {
+    describe_vae(*trainer(h), h->cfg.vae_latent_channels);
+    trainer(h)->vae_described = true;
+  }
+  for (int bit = 1; bit <= 4; bit <<= 1) {
     if (!(modules & bit)) continue;
     {
-      Lane& t = trainer(h)->lane[bit - 1];
+      Lane& t = trainer(h)->lane[bit == 4 ? 2 : bit - 1];
       LDP_TRY(t.gemm_cnt.alloc(CNT_TILES * 4));
       LDP_HIP(hipMemset(t.gemm_cnt.p, 0, CNT_TILES * 4));
       for (int k = 0; k < Lane::NS; ++k) {
@@ -2196,14 +2209,32 @@ int ldp_train_idm_grad(ldp_handle* h, const float* s, const float* a0, const flo
   return run_tape(h, 1, (hipStream_t)stream, [&](Ctx& c) { return idm_tape(c, s, a0, noise, t_dev, alpha, loss_out, R); });
 }
 
+int ldp_train_vae_grad(ldp_handle* h, const float* img_nhwc, int32_t N, int32_t use_kl, float beta, const float* eps, uint64_t seed, int64_t row_offset,
+                       float* metrics_out, void* stream) {
+  if (!h) return fail(LDP_EINVAL, "null handle");
+  if (h->cfg.image_size <= 0) return fail(LDP_EINVAL, "module 4 (vae): this handle was created with image_size = 0, it has no StableVAE");
+  Module* m = nullptr;
+  LDP_TRY(need_module(h, 4, &m));
+  if (!img_nhwc || !metrics_out || N <= 0 || row_offset < 0) return fail(LDP_EINVAL, "bad argument");
+  if (h->cfg.image_size != 64)
+    return fail(LDP_EINVAL, "ldp_train_vae_grad: built and tested for 64-pixel frames, this handle has %d", h->cfg.image_size);
+  if (N > VAE_TRAIN_MAX_FRAMES)
+    return fail(LDP_EINVAL, "ldp_train_vae_grad: %d frames, at most %d per call (the tape keeps every activation of the batch)", N, VAE_TRAIN_MAX_FRAMES);
+  if (!std::isfinite(beta)) return fail(LDP_EINVAL, "beta must be finite");
+  LDP_HIP(hipSetDevice(h->cfg.device));
+  m->gpart_fresh = false;
+  return run_vae_tape(h, (hipStream_t)stream, [&](Ctx& c) { return vae_tape(c, img_nhwc, N, use_kl != 0, beta, eps, seed, (uint64_t)row_offset, metrics_out); });
+}
+
 int ldp_train_grad_norm(ldp_handle* h, int32_t modules, float* out, void* stream) {
   if (!h || !out) return fail(LDP_EINVAL, "bad argument");
-  if (!(modules & 3) || (modules & ~3)) return fail(LDP_EINVAL, "modules must be a mask of 1 (planner) and 2 (idm)");
+  if (!(modules & 7) || (modules & ~7)) return fail(LDP_EINVAL, "modules must be a mask of 1 (planner), 2 (idm) and 4 (vae)");
+  if (modules == 7) return fail(LDP_EINVAL, "ldp_train_grad_norm takes at most two modules per call");
   hipStream_t s = (hipStream_t)stream;
   const float* pa[2] = {nullptr, nullptr};
   long long na[2] = {0, 0};
   int k = 0;
-  for (int bit = 1; bit <= 2; bit <<= 1) {
+  for (int bit = 1; bit <= 4; bit <<= 1) {
     if (!(modules & bit)) continue;
     Module* m = nullptr;
     LDP_TRY(need_module(h, bit, &m));
@@ -2301,16 +2332,16 @@ int ldp_train_arena(ldp_handle* h, int32_t module, int32_t which, float** dev_ou
 // master parameters (or their EMA) -> the handle's weight store -> finalize of the listed modules
 static int publish(ldp_handle* h, int32_t modules, bool ema, void* stream) {
   if (!h) return fail(LDP_EINVAL, "null handle");
-  if (!(modules & 3) || (modules & ~3)) return fail(LDP_EINVAL, "modules must be a mask of 1 (planner) and 2 (idm)");
+  if (!(modules & 7) || (modules & ~7)) return fail(LDP_EINVAL, "modules must be a mask of 1 (planner), 2 (idm) and 4 (vae)");
   hipStream_t s = (hipStream_t)stream;
   LDP_HIP(hipSetDevice(h->cfg.device));
   LDP_HIP(hipStreamSynchronize(s));
-  for (int bit = 1; bit <= 2; bit <<= 1) {
+  for (int bit = 1; bit <= 4; bit <<= 1) {
     if (!(modules & bit)) continue;
     Module* m = nullptr;
     LDP_TRY(need_module(h, bit, &m));
     if (ema && !m->ema_on) return fail(LDP_ESTATE, "module %d keeps no EMA (ldp_train_ema was not called)", bit);
-    const char* prefix = bit == 1 ? "planner/" : "idm/";
+    const char* prefix = bit == 1 ? "planner/" : bit == 2 ? "idm/" : "vae/";
     std::vector<float> img(m->total);
     LDP_HIP(hipMemcpy(img.data(), ema ? m->E.p : m->P.p, m->total * 4, hipMemcpyDeviceToHost));
     for (const Leaf& l : m->leaves) {
@@ -2324,6 +2355,7 @@ static int publish(ldp_handle* h, int32_t modules, bool ema, void* stream) {
   drop_graphs(h);
   if (modules & 1) LDP_TRY(planner_finalize(h, s));
   if (modules & 2) LDP_TRY(idm_finalize(h, s));
+  if (modules & 4) LDP_TRY(vae_finalize(h, s));
   LDP_HIP(hipStreamSynchronize(s));
   return LDP_OK;
 }

@@ -450,7 +450,7 @@ class HipEngine:
         return hit
 
     # -- training step (include/ldp_hip.h "training step"; agent/ldp_agent.py:113-180, 223-323) -----------------------
-    _MODS = {"planner": MOD_PLANNER, "idm": MOD_IDM}
+    _MODS = {"planner": MOD_PLANNER, "idm": MOD_IDM, "vae": MOD_VAE}
 
     def _mask(self, modules) -> int:
         if isinstance(modules, str):
@@ -517,6 +517,25 @@ class HipEngine:
         check(self.lib.ldp_train_idm_grad(self._h, _ptr(s), _ptr(a0), _ptr(noise), _ptr(td), C.c_float(alpha), _ptr(loss), R, self._stream()))
         self._keep_i = (s, a0, noise, td)
         return loss
+
+    def train_vae_grad(self, img: torch.Tensor, use_kl: bool = True, beta: float = 1e-5, seed: int = 0, noise: Optional[torch.Tensor] = None,
+                       row_offset: int = 0) -> torch.Tensor:
+        """StableVAEModel.loss and its gradients (model/stable_vae_model.py:25-73) on module "vae"'s master parameters: img (N, S, S, 3) NHWC
+        normalised frames -> the eleven metrics as an (11,) device tensor in _lib.VAE_METRIC_KEYS order; the gradients replace the module's
+        gradient arena.  noise / seed / row_offset: the eps of the posterior draw, as vae_metrics."""
+        img = _f32(img, self.device)
+        if img.dim() != 4:
+            raise ValueError(f"img must have shape (N, {self.image_size}, {self.image_size}, 3), got {tuple(img.shape)}")
+        n = img.shape[0]
+        _want("img", img, (n, self.image_size, self.image_size, 3))
+        if not np.isfinite(float(beta)):
+            raise ValueError(f"beta must be finite, got {beta}")
+        eps, seed_c, row_c = self._vae_noise_args(noise, n, seed, row_offset)
+        out = torch.empty((len(_lib.VAE_METRIC_KEYS),), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_train_vae_grad(self._h, _ptr(img), n, int(bool(use_kl)), C.c_float(float(beta)), _ptr(eps), seed_c, row_c, _ptr(out),
+                                          self._stream()))
+        self._keep_v = (img, eps)                      # the launches are asynchronous: the inputs must outlive them
+        return out
 
     def train_grad_norm(self, modules) -> torch.Tensor:
         out = torch.empty((), dtype=torch.float32, device=self.device)

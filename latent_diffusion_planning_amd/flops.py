@@ -92,3 +92,51 @@ def plan_flops(pspec: PlannerSpec, T: int, n_steps: int, ispec: IDMSpec = None, 
     if ispec is not None:
         f += idm_steps * idm_rows * idm_forward_flops(ispec)
     return f
+
+
+def _taps_same_2d(s: int) -> int:
+    """live taps of a 3x3, stride-1, pad-1 conv summed over the output pixels of an s x s image."""
+    return _valid_taps_same(s, 3) ** 2
+
+
+def _taps_down_2d(s_in: int) -> int:
+    """3x3 stride 2 with XLA SAME pads (0, 1) on an even side: live taps over the output pixels."""
+    return _valid_taps_down(s_in) ** 2
+
+
+def vae_forward_flops(spec: VAESpec, image_size: int) -> dict:
+    """FLOPs of one StableVAE forward pass for one frame, non-padding taps only (like planner_forward_flops) ->
+    {"encoder": .., "decoder": .., "total": ..}.  The nearest x2 upsample is folded into its 3x3 (the taps of the upsampled image that
+    hit data); the attention counts its four Dense layers and the two (tokens x tokens x C) products; GroupNorm / SiLU are not counted."""
+    ch, lc, layers = spec.block_out_channels, spec.latent_channels, spec.layers_per_block
+
+    def res(s, ci, co):
+        m = _taps_same_2d(s) * (ci * co + co * co)
+        return m + (s * s * ci * co if ci != co else 0)
+
+    def mid(s, c):
+        t = s * s
+        return 2 * res(s, c, c) + 4 * t * c * c + 2 * t * t * c
+
+    s, c = image_size, ch[0]
+    enc = _taps_same_2d(s) * spec.in_channels * c
+    for i, co in enumerate(ch):
+        for _ in range(layers):
+            enc += res(s, c, co)
+            c = co
+        if i != len(ch) - 1:
+            enc += _taps_down_2d(s) * c * c
+            s //= 2
+    enc += mid(s, c) + _taps_same_2d(s) * c * 2 * lc + s * s * (2 * lc) ** 2
+    dec = s * s * lc * lc + _taps_same_2d(s) * lc * ch[-1]
+    c = ch[-1]
+    dec += mid(s, c)
+    for i, co in enumerate(reversed(ch)):
+        for _ in range(layers + 1):
+            dec += res(s, c, co)
+            c = co
+        if i != len(ch) - 1:
+            s *= 2
+            dec += _taps_same_2d(s) * c * c
+    dec += _taps_same_2d(s) * c * spec.out_channels
+    return {"encoder": 2.0 * enc, "decoder": 2.0 * dec, "total": 2.0 * (enc + dec)}

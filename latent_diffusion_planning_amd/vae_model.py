@@ -1,8 +1,11 @@
-"""StableVAEModel -- the reference's VAE model class (model/stable_vae_model.py:18-175) on the HIP engine, forward side.
+"""StableVAEModel -- the reference's VAE model class (model/stable_vae_model.py:18-175) on the HIP engine.
 
 `create`, `.vae_state` (`.params`, `.ema_params`, `.step`, `.replace`), `.config[...]`, `.obs_normalization`, `.replace`, `get_params`,
-`get_metrics`, `reconstruct` and `sample` have the reference's names, argument meaning and return structure: what `train_vae.py:140-230`
-calls at every evaluation.  `update` (the backward pass of the 2-D convolutions, Adam and the EMA on the VAE arena) is not built and raises.
+`get_metrics`, `reconstruct`, `sample` and `update` have the reference's names, argument meaning and return structure: what `train_vae.py`
+calls.  `update` runs the loss, its hand-written backward pass (csrc/vae_train.hpp: exact-fp32 2-D convolutions, GroupNorm, attention),
+Adam and the EMA on the engine's VAE arena (module bit 4 of the training calls); the new model's `params` / `ema_params` are fetched from
+the arenas on first access, and only the newest model's are readable (the reference donates the old state's buffers the same way).
+Training is built for 64-pixel frames, the reference's `init` shape; `update` refuses other sizes.
 
 Deliberate differences, the same as for the agents (agent.py):
   * `rng`: an int seed, a uint32[2] key or a torch.Generator seeds the in-kernel Philox stream (JAX's threefry stream is a non-goal);
@@ -23,7 +26,7 @@ import torch
 
 from . import _lib
 from . import weights as W
-from .agent import _Elem, _EngineCalls, _get, _norm_entry, _philox_normal, _seed_of
+from .agent import _Elem, _EngineCalls, _get, _norm_entry, _philox_normal, _seed_of, _versions
 from .arrays import DeviceArray
 from .dp_vae_agent import DPState
 from .engine import HipEngine
@@ -65,7 +68,7 @@ class StableVAEModel(_EngineCalls):
     def __init__(self, vae_state: DPState, obs_normalization, config, engine: Optional[HipEngine], vae_spec: W.VAESpec, image_size: int,
                  device, lr_schedule=None, ema_decay: float = 0.99):
         self.vae_state = vae_state
-        self.ema_decay = float(ema_decay)            # kept for the training step that is not built yet (TrainStateEMA.apply_ema)
+        self.ema_decay = float(ema_decay)            # TrainStateEMA.apply_ema (update)
         self.obs_normalization = obs_normalization
         self.config = config
         self.lr_schedule = lr_schedule
@@ -155,6 +158,15 @@ class StableVAEModel(_EngineCalls):
         want = st.ema_version if use_ema else st.version
         if eng.loaded["vae"] == want:
             return
+        tokens = getattr(eng, "train_token", {}), getattr(eng, "train_ema_token", {})
+        if not use_ema and tokens[0].get("vae") == st.version:          # a trained state: publish from the arena (no tree passes through Python)
+            eng.train_publish(["vae"], versions={"vae": want})
+            self._uploads[0] += 1
+            return
+        if use_ema and tokens[1].get("vae") == st.ema_version:
+            eng.train_publish_ema(["vae"], versions={"vae": want})
+            self._uploads[0] += 1
+            return
         tree = st.ema_params if use_ema else st.params
         W.check_params(tree, W.vae_shapes(self._vae_spec))
         eng.load_params(vae=tree, versions={"vae": want})
@@ -237,7 +249,73 @@ class StableVAEModel(_EngineCalls):
         return DeviceArray(res[0], record=rec)
 
     # ---- model/stable_vae_model.py:57-73 ---------------------------------------------------------------------------------------------
-    def update(self, batch, rng, step):
-        raise NotImplementedError("StableVAEModel.update: the backward pass of the 2-D convolutions (3x3 / stride-2 / attention blocks), Adam "
-                                  "and the EMA on the VAE arena are not built; train the VAE with the reference and import its snapshot "
-                                  "(checkpoint.load_snapshot)")
+    TRAIN_SIZES = (64,)                       # frame sizes the training tape is built and tested for
+
+    def update(self, batch, rng, step, noise=None, row_offset: int = 0):
+        """`update_step`: jax.grad of `loss` on `params`, one optax.adam step with the warmup-cosine schedule, then the EMA -> (new model,
+        metrics).  metrics: the eleven keys of `loss` on the pre-update parameters (device scalars, as get_metrics), then vae_lr =
+        schedule(old step) and vae_step = old step.  rng / noise / row_offset: the eps of the posterior draw, as get_metrics (the same seed draws
+        the same eps here and there).  `step` is unused, as in the reference."""
+        eng = self._engine
+        if not hasattr(eng, "train_vae_grad"):
+            raise NotImplementedError("StableVAEModel.update: this engine has no backward pass of the 2-D convolutions (HipEngine.train_vae_grad); "
+                                      "train the VAE with a build that has it, or import a snapshot (checkpoint.load_snapshot)")
+        if self._image_size not in self.TRAIN_SIZES:
+            raise NotImplementedError(f"StableVAEModel.update: the backward pass of the 2-D convolutions is built for {self.TRAIN_SIZES}-pixel frames; "
+                                      f"this model takes {self._image_size}-pixel frames")
+        if self.lr_schedule is None:
+            raise ValueError("update() needs the optimiser settings of StableVAEModel.create (lr, end_lr, warmup_steps, decay_steps)")
+        seed = _seed_of(rng)
+        use_kl, beta = bool(self.config["use_kl"]), float(self.config["beta"])
+        eps = None if noise is None else self._t(noise)
+        st = self.vae_state
+        lr = np.float32(self.lr_schedule(st.step))
+
+        def run():
+            self._train_sync(st)
+            img = self._frames(batch, self.config["rgb_obs"])
+            out = eng.train_vae_grad(img, use_kl, beta, seed=seed, noise=eps, row_offset=row_offset)
+            eng.train_apply("vae", float(lr))                                   # Adam + EMA, one launch
+            return [out]
+        # the tape runs on exact-fp32 kernels only (no range guard, no in-launch exchange): a later fault poll has nothing to recompute here,
+        # and re-running the step would apply it twice
+        rec = self._record(lambda: [None])
+        res = self._guarded(run)
+        rec.seqs = self._seqs()
+        new_state = self._trained_state(st)
+        vec = DeviceArray(res[0], record=rec)
+        metrics = {k: _Elem(vec, i) for i, k in enumerate(_lib.VAE_METRIC_KEYS)}
+        metrics["vae_lr"], metrics["vae_step"] = lr, st.step                  # the OLD state's count (:71-72)
+        return self.replace(vae_state=new_state), metrics
+
+    def _train_sync(self, st: DPState) -> None:
+        """The engine's VAE arenas must hold THIS state: parameters, Adam moments (fresh after a restore, as train_vae.py:62-75) and the EMA."""
+        eng = self._engine
+        if eng.train_token.get("vae") == st.version and eng.train_ema_token.get("vae") == st.ema_version:
+            return
+        shapes = W.vae_shapes(self._vae_spec)
+        W.check_params(st.params, shapes)
+        ema = None if st.ema_is_params else st.ema_params                    # (read before the arenas are overwritten)
+        o = st.opt_state
+        eng.train_load("vae", st.params, mu=None if o is None else o["mu"], nu=None if o is None else o["nu"], step=st.step, token=st.version)
+        if eng.ema_decay.get("vae") != self.ema_decay:
+            eng.train_ema("vae", self.ema_decay)
+        if ema is not None:
+            W.check_params(ema, shapes)
+            eng.train_write("vae", eng.TRAIN_EMA, ema)
+        eng.train_ema_token["vae"] = st.ema_version
+
+    def _trained_state(self, old: DPState) -> DPState:
+        eng = self._engine
+        shapes = W.vae_shapes(self._vae_spec)
+        token, etoken = next(_versions), next(_versions)
+        eng.train_token["vae"] = token
+        eng.train_ema_token["vae"] = etoken
+        which = {"params": eng.TRAIN_PARAMS, "ema": eng.TRAIN_EMA}
+
+        def fetch(what):
+            if eng.train_token.get("vae") != token or (what == "ema" and eng.train_ema_token.get("vae") != etoken):
+                raise RuntimeError("this StableVAEModel state was superseded by a later update(): its buffers were donated to the next step "
+                                   "(keep the model that update() returned, as train_vae.py does)")
+            return eng.train_read("vae", which[what], shapes)
+        return DPState(None, None, old.step + 1, token, None, fetch, etoken, lambda: fetch("ema"))

@@ -1,0 +1,167 @@
+"""StableVAEModel.update without a GPU: the float64 autograd oracle (tests/vae_train_oracle.py) against central differences of the independent
+numpy restatement (oracle.np64 through tests/vae_model_oracle.py), the host logic of `update` on a stub engine, the FLOP count of the VAE."""
+import numpy as np
+import pytest
+import torch
+
+from latent_diffusion_planning_amd import _lib, flops, weights as W
+from latent_diffusion_planning_amd.dp_vae_agent import DPState
+from latent_diffusion_planning_amd.schedule import warmup_cosine_decay_schedule
+from latent_diffusion_planning_amd.vae_model import StableVAEModel
+from tests import vae_model_oracle as VO
+from tests import vae_train_oracle as VT
+from tests.util import rng
+
+KEY, KEY2 = "agentview_image", "robot0_eye_in_hand_image"
+NORM = {"obs": {KEY: dict(min=0.0, max=255.0), KEY2: dict(min=0.0, max=255.0)}}
+
+
+# ---- 1. the oracle's gradient against central differences of oracle.np64 ---------------------------------------------------------------
+# one entry of each kind the issue names: a 3x3 kernel at 64 px, a stride-2 kernel, a GroupNorm scale, an attention query kernel, a
+# quant_conv log-variance column (LC = 4: output channels 4..7)
+ENTRIES = (("encoder/down_blocks_0/resnets_0/conv1/kernel", (1, 2, 5, 17)),
+           ("encoder/down_blocks_1/downsamplers_0/conv/kernel", (0, 2, 33, 101)),
+           ("decoder/up_blocks_5/resnets_1/norm2/scale", (70,)),
+           ("encoder/mid_block/attentions_0/query/kernel", (12, 200)),
+           ("quant_conv/kernel", (0, 0, 3, 6)))
+H = 1e-4          # central-difference step
+
+
+def test_oracle_gradient_matches_central_differences_of_np64():
+    """Central differences have truncation error h^2 f''' / 6 and cancellation error ~1e-16 |loss| / h; at h = 1e-4 on weights of size
+    0.01 - 1 both are below 1e-7 of these entries' gradients (checked: halving h moves the estimates by less than that).  The bound, 1e-5
+    relative + 1e-11, is two orders of magnitude above both and seven below an error in the backward pass (a missing term moves a
+    gradient by O(1) of itself)."""
+    torch.set_num_threads(16)
+    p = W.init_vae_params(seed=5)
+    x = rng(31).uniform(-1, 1, (1, 64, 64, 3))
+    eps = rng(32).standard_normal((1, 2, 2, 4))
+    _, g, mom, _ = VT.loss_and_grads(p, x, eps, True, VT.BETA)
+    lv = mom[..., 4:]
+    assert lv.min() > -29 and lv.max() < 19                         # the clamp is not what this tests
+
+    def loss_at(path, idx, delta):
+        q = dict(p)
+        a = np.array(p[path], np.float64)
+        a[idx] += delta
+        q[path] = a
+        return VO.loss(q, x, eps, True, VT.BETA)[0]["loss"]
+    for path, idx in ENTRIES:
+        fd = (loss_at(path, idx, H) - loss_at(path, idx, -H)) / (2 * H)
+        ad = float(g[path][idx])
+        print(path, idx, "autograd", ad, "central difference", fd)
+        assert abs(fd - ad) <= 1e-5 * abs(ad) + 1e-11, (path, idx, ad, fd)
+
+
+# ---- 2. host logic of update on a stub engine ----------------------------------------------------------------------------------------
+class _TrainStub:
+    """The engine calls update makes, recorded; gradients are not computed here."""
+    TRAIN_PARAMS, TRAIN_GRADS, TRAIN_MU, TRAIN_NU, TRAIN_EMA = 0, 1, 2, 3, 4
+
+    def __init__(self):
+        self.loaded = {"planner": None, "idm": None, "vae": None}
+        self.call_seq, self.fault_upto, self.last_fault_kinds = 0, -1, 0
+        self.train_token, self.train_ema_token, self.ema_decay = {}, {}, {}
+        self.calls = []
+
+    def normalize_bounds(self, x, lo, hi, normalize):
+        return (x - lo[0]) / (hi[0] - lo[0]) * 2 - 1
+
+    def poll_fault_kinds(self):
+        return 0
+
+    def train_load(self, module, params, mu=None, nu=None, step=0, token=None):
+        self.calls.append(("load", module, step, mu is None))
+        self.train_token[module] = token
+
+    def train_ema(self, module, decay):
+        self.calls.append(("ema", module, decay))
+        self.ema_decay[module] = decay
+
+    def train_write(self, module, which, tree):
+        self.calls.append(("write", module, which))
+
+    def train_vae_grad(self, img, use_kl, beta, seed=0, noise=None, row_offset=0):
+        self.calls.append(("grad", tuple(img.shape), use_kl, beta, seed, row_offset))
+        self.frames = img
+        return torch.arange(11, dtype=torch.float32) + seed
+
+    def train_apply(self, module, lr, b1=0.9, b2=0.999, eps=1e-8):
+        self.calls.append(("apply", module, lr))
+
+    def train_read(self, module, which, shapes):
+        self.calls.append(("read", module, which))
+        return {k: np.full((1,), which, np.float32) for k in shapes}
+
+
+@pytest.fixture
+def stub_model(monkeypatch):
+    from latent_diffusion_planning_amd import vae_model
+    monkeypatch.setattr(vae_model.W, "check_params", lambda tree, shapes: None)      # the stub's trees are not 41.7 M parameters
+
+    def make(rgb_obs=(KEY,), use_kl=True, image_size=64):
+        cfg = dict(rgb_obs=list(rgb_obs), name="stable_vae_model", use_kl=use_kl, beta=1e-5, n_downsample=6, data_name="rm_lift")
+        sched = warmup_cosine_decay_schedule(1e-6, 1e-4, 1000, 300000, 1e-6)
+        p = {"quant_conv/bias": np.zeros(8, np.float32)}
+        return StableVAEModel(DPState(p, None, ema_is_params=True), NORM, cfg, _TrainStub(), W.VAESpec(), image_size, "cpu",
+                              lr_schedule=sched, ema_decay=0.99)
+    return make
+
+
+def _raw(seed, B):
+    return rng(seed).integers(0, 256, (B, 2, 64, 64, 3)).astype(np.float32)
+
+
+def test_update_returns_the_reference_metrics_and_advances_the_step(stub_model):
+    m0 = stub_model()
+    sched = m0.lr_schedule
+    m1, met = m0.update({"obs": {KEY: _raw(1, 2)}}, 7, 0)
+    assert list(met) == list(_lib.VAE_METRIC_KEYS) + ["vae_lr", "vae_step"]                     # 13 keys, the reference's order
+    assert [float(met[k]) for k in _lib.VAE_METRIC_KEYS] == [float(i + 7) for i in range(11)]
+    assert met["vae_lr"] == np.float32(sched(0)) and met["vae_step"] == 0
+    m2, met2 = m1.update({"obs": {KEY: _raw(2, 2)}}, 8, 1)
+    assert met2["vae_lr"] == np.float32(sched(1)) and met2["vae_step"] == 1 and m2.vae_state.step == 2
+    kinds = [c[0] for c in m0._engine.calls]
+    # the first step loads the arenas (fresh moments) and enables the EMA; the second trains on what the first left there
+    assert kinds == ["load", "ema", "grad", "apply", "grad", "apply"]
+    assert [c for c in m0._engine.calls if c[0] == "apply"] == [("apply", "vae", float(np.float32(sched(0)))),
+                                                                ("apply", "vae", float(np.float32(sched(1))))]
+
+
+def test_update_concatenates_the_cameras_and_passes_use_kl(stub_model):
+    m = stub_model((KEY, KEY2), use_kl=False)
+    a, b = _raw(3, 2), _raw(4, 2)
+    m.update({"obs": {KEY: a, KEY2: b}}, 5, 0, row_offset=9)
+    grad = [c for c in m._engine.calls if c[0] == "grad"][0]
+    assert grad == ("grad", (4, 64, 64, 3), False, 1e-5, 5, 9)
+    img = m._engine.frames.numpy()
+    assert np.allclose(img[:2], a[:, 0] / 255 * 2 - 1, atol=1e-6) and np.allclose(img[2:], b[:, 0] / 255 * 2 - 1, atol=1e-6)
+
+
+def test_only_the_newest_model_is_readable(stub_model):
+    m0 = stub_model()
+    m1, _ = m0.update({"obs": {KEY: _raw(1, 2)}}, 0, 0)
+    m2, _ = m1.update({"obs": {KEY: _raw(1, 2)}}, 0, 1)
+    with pytest.raises(RuntimeError, match="superseded"):
+        m1.vae_state.params
+    with pytest.raises(RuntimeError, match="superseded"):
+        m1.vae_state.ema_params
+    assert float(m2.vae_state.params["quant_conv/bias"][0]) == 0.0            # read from the parameter arena (which = 0)
+    assert float(m2.vae_state.ema_params["quant_conv/bias"][0]) == 4.0        # ... and from the EMA arena (which = 4)
+    assert m0.vae_state.params["quant_conv/bias"].shape == (8,)               # the host tree the first model was built with
+
+
+def test_update_refuses_frame_sizes_it_was_not_built_for(stub_model):
+    m = stub_model(image_size=128)
+    with pytest.raises(NotImplementedError, match="128-pixel"):
+        m.update({"obs": {KEY: _raw(1, 2)}}, 0, 0)
+    assert m._engine.calls == []
+
+
+# ---- 3. FLOPs -----------------------------------------------------------------------------------------------------------------------------
+def test_vae_forward_flops_counts_live_taps():
+    f = flops.vae_forward_flops(W.VAESpec(), 64)
+    assert round(f["encoder"] / 1e9, 1) == 11.0 and round(f["decoder"] / 1e9, 1) == 23.9
+    assert f["total"] == f["encoder"] + f["decoder"]
+    # a 3x3 at 64 px has 62^2 * 9 + edges: fewer live taps than 9 per pixel
+    assert flops._taps_same_2d(64) < 9 * 64 * 64 and flops._taps_down_2d(64) == (32 * 3 - 1) ** 2
