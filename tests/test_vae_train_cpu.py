@@ -1,5 +1,6 @@
 """StableVAEModel.update without a GPU: the float64 autograd oracle (tests/vae_train_oracle.py) against central differences of the independent
-numpy restatement (oracle.np64 through tests/vae_model_oracle.py), the host logic of `update` on a stub engine, the FLOP count of the VAE."""
+numpy restatement (oracle.np64 through tests/vae_model_oracle.py), the host logic of `update` on a stub engine, the FLOP count of the VAE,
+the fixture conditions of the whole-leaf GPU tests (tests/test_hip_vae_train_full.py)."""
 import numpy as np
 import pytest
 import torch
@@ -9,6 +10,7 @@ from latent_diffusion_planning_amd.dp_vae_agent import DPState
 from latent_diffusion_planning_amd.schedule import warmup_cosine_decay_schedule
 from latent_diffusion_planning_amd.vae_model import StableVAEModel
 from tests import vae_model_oracle as VO
+from tests import vae_train_cases as VC
 from tests import vae_train_oracle as VT
 from tests.util import rng
 
@@ -165,3 +167,52 @@ def test_vae_forward_flops_counts_live_taps():
     assert f["total"] == f["encoder"] + f["decoder"]
     # a 3x3 at 64 px has 62^2 * 9 + edges: fewer live taps than 9 per pixel
     assert flops._taps_same_2d(64) < 9 * 64 * 64 and flops._taps_down_2d(64) == (32 * 3 - 1) ** 2
+
+
+# ---- 4. the conditions tests/test_hip_vae_train_full.py rests on --------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def case_b():
+    """Case b (seeded parameters 5, B = 3, beta = 1) through the float64 and float32 chains, once."""
+    p, frames, eps, use_kl, beta = VC.case_inputs("b")
+    return dict(VC.oracle_run(p, frames, eps, use_kl, beta), params=p, frames=frames, eps=eps, beta=beta)
+
+
+def test_batch_gradient_is_the_weighted_sum_of_chunk_gradients_in_float64(case_b):
+    """The loss is a mean over frames and GroupNorm is per sample: G(batch) = sum_c (|c| / B) G(chunk c), here 2 + 1 frames.  Round-off of the
+    float64 chain is ~1e-14 of a leaf's maximum; a coupling between frames would show at O(1)."""
+    o = case_b
+    chunks = [(hi - lo, VC.oracle_run(o["params"], o["frames"][lo:hi], o["eps"][lo:hi], True, o["beta"], with32=False)["grads"])
+              for lo, hi in ((0, 2), (2, 3))]
+    comb = VC.combine(chunks)
+    worst = max(float(np.abs(g - comb[k]).max()) / max(float(np.abs(g).max()), 1e-300) for k, g in o["grads"].items()
+                if not k.endswith("attentions_0/key/bias"))
+    print("float64 decomposition residual / leafmax", worst)
+    assert worst < 1e-12
+    for k, g in o["grads"].items():
+        if k.endswith("attentions_0/key/bias"):                    # true gradient 0: round-off on both sides
+            assert float(np.abs(g).max()) < 1e-15 and float(np.abs(comb[k]).max()) < 1e-15
+
+
+def test_clamp_fixture_saturates_two_channels_and_no_others():
+    """Case d: log-variance channels 0 / 1 at least 10 beyond the clamp (-30, 20), channels 2 / 3 at least 1 inside it."""
+    from oracle import torch32
+    p, frames, _, _, _ = VC.case_inputs("d")
+    lc = VO.latent_channels(p)
+    torch.set_num_threads(16)
+    mom = torch32.vae_encode_mean(torch32.TorchParams(p, dtype=torch.float64), torch.tensor(frames, dtype=torch.float64),
+                                  latent_channels=2 * lc).numpy()
+    lv = mom[..., lc:]
+    print("case d log-variance ranges per channel", [(float(lv[..., c].min()), float(lv[..., c].max())) for c in range(lc)])
+    assert lv[..., 0].min() >= 30.0 and lv[..., 1].max() <= -40.0
+    assert lv[..., 2:].min() >= -29.0 and lv[..., 2:].max() <= 19.0
+
+
+def test_kl_term_dominates_the_encoder_gradients_at_beta_1(case_b):
+    """What case b relies on: at beta = 1 switching the KL term off moves at least 90 % of the encoder / quant_conv leaves by more than
+    100 x the bound the GPU test applies to them (at beta = 1e-5 it moves 140 of 332 leaves by at most 4 x the bound)."""
+    o = case_b
+    off = VC.oracle_run(o["params"], o["frames"], o["eps"], False, o["beta"], with32=False)["grads"]
+    enc = [k for k in o["grads"] if k.startswith(("encoder/", "quant_conv/"))]
+    ratio = np.asarray([float(np.abs(o["grads"][k] - off[k]).max()) / VC.leaf_bound(o["grads"][k], o["err32"][k]) for k in enc])
+    print(f"KL on/off at beta = 1: {int((ratio > 100).sum())} of {len(enc)} encoder leaves move by > 100 x their bound, median {np.median(ratio):.0f} x")
+    assert len(enc) == 142 and (ratio > 100).sum() >= 0.9 * len(enc)
