@@ -425,7 +425,8 @@ LDP_API int64_t ldp_range_fallbacks(void);
  * above 256 plans: "planner_split" (0: exact fp32 everywhere), "planner_split_f16" (as for the
  * StableVAE), "planner_split_mb2", "planner_split_t16"; the IDM above 256 plans: "idm_f16" (1: its MLPResNet blocks on two fp16 planes over 32-row
  * tiles, 0: exact fp32), "idm_f16_min_rows", "idm_f16_hs"; and the A/B switches listed in
- * csrc/engine.hpp; read-only counters "stat_mb2_launches", "stat_f16_launches".  Timing ablations for
+ * csrc/engine.hpp; read-only counters "stat_mb2_launches", "stat_f16_launches", "stat_train_gemm_<nn|nt|tn>_<32|64|128>[_ki2]",
+ * "stat_train_gemm_fused", "stat_train_gemm_reduce" (training GEMM launches per kernel instantiation).  Timing ablations for
  * tools/ (results WRONG by construction): "dbg" (bit mask), "repeat".  Test hook: "inject_fault" (1: an
  * exchange fault, 2: a range fault).
  * Read-only through ldp_get_option: "any_debug", "faults_seen", "range_faults_seen", "n_cu", "graphs".

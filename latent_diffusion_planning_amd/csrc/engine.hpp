@@ -152,6 +152,8 @@ struct Options {
   bool any_debug() const { return dbg != 0 || repeat != 1 || timeline_ptr != 0; }
 };
 
+constexpr int LDP_STAT_GEMM_FUSED = 15, LDP_STAT_GEMM_REDUCE = 16;      // ldp_handle::stat_train_gemm
+
 struct GraphEntry {
   hipGraphExec_t exec;
   int64_t conv_launches, total_launches;
@@ -206,6 +208,10 @@ struct ldp_handle {
   int64_t stat_f16_launches = 0;         // likewise: conv launches on fp16 planes
   std::map<uint64_t, int64_t> plan_log;       // every distinct tconv instantiation this handle launched, keyed by plan_key (option "dump_plans" prints it: tools/r5/plans_used.py)
   int64_t stat_mb2_launches = 0;         // conv launches enqueued (eagerly or into a capture) on two-row-block split tiles since ldp_create: read-only option
+  // training GEMM launches enqueued since ldp_create, per instantiation of train.hip's kernel family: [form (NN, NT, TN) * 5 + {32-row, 32-row KI = 2,
+  // 64-row, 64-row KI = 2, 128 x 128}], then launches that finished split K in-launch and reduce_parts_kernel launches.  Read-only options
+  // "stat_train_gemm_<nn|nt|tn>_<32|64|128>[_ki2]", "stat_train_gemm_fused", "stat_train_gemm_reduce"; the dry walk of a tape counts nothing.
+  int64_t stat_train_gemm[17] = {};
   void* vae = nullptr;                   // VaeState (vae.hip)
   void* train = nullptr;                 // Trainer (train.hip): master parameters, gradients, Adam moments, launch tables; created by ldp_train_init
 };

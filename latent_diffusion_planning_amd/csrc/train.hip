@@ -537,7 +537,7 @@ long long fused_part_bytes(const GemmArgs& g, int nbatch, const GemmShape& sh) {
   return (tiles <= CNT_TILES && bytes < (1ll << 31)) ? bytes : 0;
 }
 int gemm_launch(GemmForm f, GemmArgs g, int nbatch, hipStream_t s, const GemmTune& tn = GemmTune(), int min_steps = 0, float* part = nullptr,
-                long long c_extent = 0, unsigned int* cnt = nullptr) {
+                long long c_extent = 0, unsigned int* cnt = nullptr, int64_t* stat = nullptr) {
   if (nbatch <= 0 || g.M <= 0 || g.N <= 0) return LDP_OK;
   if (g.K % BK || g.M % 4 || g.N % 4 || g.lda % 4 || g.ldb % 4)
     return fail(LDP_EINVAL, "seg_gemm: K = %d must be a multiple of %d and M, N, lda, ldb multiples of 4 (%d, %d, %d, %d)", g.K, BK, g.M, g.N, g.lda, g.ldb);
@@ -569,6 +569,10 @@ int gemm_launch(GemmForm f, GemmArgs g, int nbatch, hipStream_t s, const GemmTun
 #undef LDP_SEG_LAUNCH
   }
   if (sh.ks > 1 && !g.cnt) hipLaunchKernelGGL(reduce_parts_kernel, g1((long long)g.M * g.N * nbatch), dim3(256), 0, s, g, nbatch);
+  if (stat) {                                        // which instantiation was enqueued (ldp_handle::stat_train_gemm: read-only options, host side only)
+    ++stat[(int)f * 5 + (sh.big ? 4 : (sh.small32 ? 0 : 2) + (sh.ki == 2 ? 1 : 0))];
+    if (sh.ks > 1) ++stat[g.cnt ? LDP_STAT_GEMM_FUSED : LDP_STAT_GEMM_REDUCE];
+  }
   LDP_HIP(hipGetLastError());
   return LDP_OK;
 }
@@ -1345,7 +1349,7 @@ int run_gemm(const Ctx& c, GemmForm f, const GemmArgs& g, int nbatch, int min_st
             steps, sh.ks * sh.ki, sh.big ? "128x128" : sh.small32 ? "32x64" : "64x64", 2.0 * g.M * g.N * BK * steps / 1e9);
   }
   return gemm_launch(f, g, nbatch, c.s, tn, min_steps, (c.side ? c.L->gemm_part2[c.side - 1] : c.L->gemm_part).f(), c_extent,
-                     (c.side ? c.L->gemm_cnt2[c.side - 1] : c.L->gemm_cnt).as<unsigned int>());
+                     (c.side ? c.L->gemm_cnt2[c.side - 1] : c.L->gemm_cnt).as<unsigned int>(), c.h->stat_train_gemm);
 }
 // y (Bp, Tout, cout) = conv(x (Bp, Tin, cin)) + bias
 int conv_fwd(const Ctx& c, const ConvPlan& p, const float* x, const float* w, const float* bias, float* y, int Bp) {

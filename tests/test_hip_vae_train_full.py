@@ -4,8 +4,12 @@ A. Whole leaves against the float64 autograd oracle (tests/vae_train_oracle.py) 
    edge (tests/vae_train_cases.CASES): one live row of 32, the KL backward dominant (beta = 1), use_kl = 0 with a beta it must ignore, and
    log-variances beyond both ends of the clamp.  The rule is the project's (tests/test_hip_vae_train.py), applied to all 41 672 679 entries:
    |got - ref64| <= max(1e-4 leafmax64, 3 err32_leaf) + 1e-12, err32 = the leaf's max |float32 autograd - float64| of the same chain.
-B. Batches no oracle can afford, through the other tile families of `gemm_shape` (rows = rup(B, 32): 64, 96 and 160): the loss is a mean
-   over frames and nothing couples frames, so G(batch) = sum_c (|c| / B) G(chunk c); the chunks have 32 rows, the shape part A pins.
+B. Batches no oracle can afford (rows = rup(B, 32): 64, 96 and 160): the loss is a mean over frames and nothing couples frames, so
+   G(batch) = sum_c (|c| / B) G(chunk c); the chunks have 32 rows, the shape part A pins.  With the default options every one of these
+   launches runs the 32-row tile (csrc/train.hip gemm_shape: train_small_wg = 1 << 20, train_big = 0), two, three and five row tiles
+   deep; at 96 and 160 rows the same batch is run again on the 64-row tiles (train_small_wg = 0: a half-empty last row tile) and on
+   seg_gemm_big (train_big = 1: the weight gradients at 96 rows, all three forms at 160 = 128 + 32 rows), each held per entry against the
+   default-option gradient and attested by the handle's launch counters (stat_train_gemm_*).
 C. The backward's own Philox draw (eps == NULL) is the forward's, keyed by (seed, row_offset).
 D. The global norm and the zero padding of the gradient arena.
 """
@@ -16,6 +20,7 @@ import pytest
 import torch
 
 from latent_diffusion_planning_amd import _lib, weights as W
+from tests import train_cases as TC
 from tests import vae_model_oracle as VO
 from tests import vae_train_cases as VC
 from tests.golden.make_golden_vae_update import golden_path
@@ -165,13 +170,14 @@ def test_grad_norm_and_arena_padding(base_model):
 # ---- B. batch decomposition at the other tile shapes ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B", (33, 70, 129))
 def test_batch_gradient_is_the_weighted_sum_of_its_chunks(B, base_model):
-    """Rows = rup(B, 32) = 64 (the golden's own batch), 96 (the 64-row tile with a half-empty second tile) and 160 (seg_gemm_big, ragged, 31
-    padding rows) against chunks of at most 32 frames, per entry:  |G - sum_c w_c G_c| <= 2 max(1e-4, 3 rel32_leaf) leafmax(G) + 1e-12,
+    """Rows = rup(B, 32) = 64 (the golden's own batch), 96 and 160 (31 padding rows), all on the 32-row tile, against chunks of at most 32
+    frames, per entry:  |G - sum_c w_c G_c| <= 2 max(1e-4, 3 rel32_leaf) leafmax(G) + 1e-12,
     rel32_leaf = err32 / leafmax64 of the committed B = 33 golden (capped at 1 on the two key/bias leaves, whose true gradient is 0: both sides
     are the exact zero there); the factor 2 because each side carries one allowance of the project's rule.
     That rel32 carries over from B = 33 to the other sizes was checked once with the float32 CPU chain (seeded parameters 6, beta = 1,
     B = 65 in chunks 32 + 32 + 1): its residual |G32 - sum w_c G32_c| is at most 0.197 of this bound (on encoder/.../key/bias, whose float32
-    autograd value is round-off; median over the leaves 0.0056).  In float64 the identity holds to 2e-14 of the leaf maximum."""
+    autograd value is round-off; median over the leaves 0.0056).  In float64 the identity holds to 2e-14 of the leaf maximum.
+    At 96 and 160 rows the batch then runs on the 64-row tiles and on seg_gemm_big, against the default-option gradient under the same bound."""
     z = np.load(golden_path("vae_update_seeded_b33"))
     assert int(z["seed_params"]) == 6 and int(z["seed_B"]) == 33
     rel32 = np.minimum(z["out_err32"] / np.maximum(z["out_gdig"][:, 1].astype(np.float64), 1e-300), 1.0)
@@ -179,7 +185,11 @@ def test_batch_gradient_is_the_weighted_sum_of_its_chunks(B, base_model):
     frames, eps = VC.frames_and_eps(B)
     if B == 33:
         assert np.array_equal(eps, z["out_eps"][0].astype(np.float32))         # the golden's own batch
+    eng = model._engine
+    c0 = TC.read_counters(eng)
     m_full, g_full = _run(model, frames, True, 1.0, noise=_f32(eps).cuda())
+    TC.check_counters(c0, TC.read_counters(eng), {"nn_32", "nt_32", "tn_32"}, {k for k in TC.KERNELS if k not in ("nn_32", "nt_32", "tn_32")},
+                      f"batch {B}, default options")
     chunks, m_comb = [], np.zeros(11)
     for lo in range(0, B, 32):
         hi = min(lo + 32, B)
@@ -195,3 +205,26 @@ def test_batch_gradient_is_the_weighted_sum_of_its_chunks(B, base_model):
     assert np.isfinite(m_full).all() and float(sum(np.abs(v).max() for v in g_full.values())) > 0
     for k in LOSSES:
         assert abs(m_full[K[k]] - m_comb[K[k]]) <= 1e-5 * abs(m_comb[K[k]]), (k, m_full[K[k]], m_comb[K[k]])
+    if B == 33:
+        return
+    # the same batch on the other tile families: convolutions have M = the rows (forward, data gradient) or M = cin (weight gradient); 128- and
+    # 256-channel layers on both sides, so the 128-row tile needs 128 rows for NN / NT and runs for TN at any batch
+    rows = -(-B // 32) * 32
+    for cfg in ("t64", "t128"):
+        opt = TC.options(cfg)
+        big = {f"{f}_128" for f, M in (("nn", rows), ("nt", rows), ("tn", 128)) if TC.gemm_shape(M, 128, 1, 8, opt)[0] == 128}
+        must = {"nn_64", "nt_64", "tn_64"} if cfg == "t64" else big | {f"{f}_32" for f in TC.FORMS if f"{f}_128" not in big}
+        never = {k for k in TC.KERNELS if "_32" in k} if cfg == "t64" else {k for k in TC.KERNELS if "_64" in k}
+        before = {k: eng.get_option(k) for k in TC.CONFIGS[cfg]}
+        try:
+            for k, v in TC.CONFIGS[cfg].items():
+                eng.set_option(k, v)
+            c0 = TC.read_counters(eng)
+            m_cfg, g_cfg = _run(model, frames, True, 1.0, noise=_f32(eps).cuda())
+            TC.check_counters(c0, TC.read_counters(eng), must, never, f"batch {B}, {cfg}")
+        finally:
+            for k, v in before.items():
+                eng.set_option(k, v)
+        _assert_every_entry(g_cfg, g_full, bounds, f"batch {B} (rows {rows}) under {cfg} against the default options")
+        for k in LOSSES:
+            assert abs(m_cfg[K[k]] - m_full[K[k]]) <= 1e-5 * abs(m_full[K[k]]), (cfg, k, m_cfg[K[k]], m_full[K[k]])

@@ -1,6 +1,7 @@
 """CPU checks of the training-step oracle and host logic (oracle/train.py, latent_diffusion_planning_amd/schedule.py): analytic known answers for
 optax.adam and warmup_cosine_decay_schedule as restated, the autograd definition against central differences, the product's schedule against the
-oracle's, the digests the goldens keep."""
+oracle's, the digests the goldens keep; and what tests/test_hip_train_shapes.py rests on (tests/train_cases.py): the batch decomposition, the IDM
+row selection, the restated launch-shape rule."""
 import math
 
 import numpy as np
@@ -126,3 +127,92 @@ def test_hierarchical_losses_shapes_and_central_differences():
     noisy = OT._add_noise(torch.tensor(emb[:, 1::ih]), torch.tensor(nzp["noise_plan"]), nzp["t_plan"], 100)
     pred = torch32.unet_forward(PP, noisy, torch.tensor(nzp["t_plan"]), torch.tensor(emb[:, 0]))
     assert lp["plan_loss"] == pytest.approx(float(((pred - torch.tensor(nzp["noise_plan"])) ** 2).mean()), rel=1e-12)
+
+
+# ---- what tests/test_hip_train_shapes.py rests on ------------------------------------------------------------------------------------------
+def test_batch_gradient_is_the_weighted_sum_of_chunk_gradients_in_float64():
+    """The loss is a mean over samples, GroupNorm is per sample and LayerNorm per row: G(batch) = sum_c (|c| / B) G(chunk c).  B = 5 as 3 + 2."""
+    from tests import train_cases as TC
+    from tests.util import planner_params
+    pp, ip = planner_params(D=TC.D), idm_params(D=TC.D, A=TC.A)
+    for what, run, c in (("planner", lambda c: TC.oracle_planner(pp, c), TC.planner_batch(5, 61)),
+                         ("idm", lambda c: TC.oracle_idm(ip, c), TC.idm_pool(5, 62))):
+        full = run(c)
+        parts = [(n, run(TC.take_rows(c, sl))) for n, sl in ((3, slice(0, 3)), (2, slice(3, 5)))]
+        comb = TC.combine([(n, r["grads"]) for n, r in parts])
+        worst = max(float(np.abs(comb[k] - v).max()) / max(float(np.abs(v).max()), 1e-300) for k, v in full["grads"].items())
+        print(f"{what}: |G(5) - (3 G(0:3) + 2 G(3:5)) / 5| <= {worst:.1e} of the leaf maximum")
+        assert worst <= 1e-12
+        assert sum(n / 5 * r["loss"] for n, r in parts) == pytest.approx(full["loss"], rel=1e-12)
+
+
+@pytest.mark.parametrize("rows,seed", [(24, 2024), (320, 2320), (2048, 3048)])
+def test_idm_row_selection_keeps_relu_inputs_clear_of_float32_round_off(rows, seed):
+    """The batches of tests/test_hip_train_shapes.py (same seeds): the smallest kept margin is at least 16 x the largest |float32 - float64| ReLU
+    input of the pool, a third of the pool is dropped, and the margin is _relu_margins of tests/test_hip_train.py applied per row."""
+    from tests import train_cases as TC
+    from tests.test_hip_train import _relu_margins
+    ip = idm_params(D=TC.D, A=TC.A)
+    c, info = TC.idm_rows(ip, rows, seed)
+    print(f"IDM row selection, {rows} rows of {rows * 3 // 2}: smallest kept margin {info['kept_min']:.2e}, round-off {info['roundoff']:.2e}, ratio {info['ratio']:.1f}")
+    assert info["ratio"] >= TC.MARGIN_OVER_ROUNDOFF, info
+    assert len(c["t"]) == rows and all(len(v) == rows for v in c.values())
+    emb, act = TC.idm_as_samples(c)
+    m = _relu_margins(ip, emb, act, dict(noise_idm=c["noise"], t_idm=c["t"]))
+    assert m.shape == (rows,) and m.min() == pytest.approx(info["kept_min"], rel=1e-9)
+    pool = TC.idm_pool(rows * 3 // 2, seed)
+    emb, act = TC.idm_as_samples(pool)
+    mp = np.sort(_relu_margins(ip, emb, act, dict(noise_idm=pool["noise"], t_idm=pool["t"])))
+    assert mp[len(mp) - rows] == pytest.approx(info["kept_min"], rel=1e-9)            # exactly the rows with the largest margins were kept
+
+
+def test_restated_gemm_shape_rule_known_answers():
+    """csrc/train.hip gemm_shape as tests/train_cases.py restates it, against cases worked out by hand -> (tile rows, K split, quartets)."""
+    from tests import train_cases as TC
+    o = lambda **kw: dict(TC.DEFAULTS, **kw)          # noqa: E731
+    #      M,   N,  batches, K steps, options                      -> tile, ks, ki
+    table = [
+        (32, 1024, 1, 8, o(), (32, 4, 1)),                         # 16 tiles: x2 (4 steps each), x4 (2 steps each); x8 would leave one step
+        (32, 1024, 1, 8, o(train_intra_split=1), (32, 2, 2)),      # the first factor of two inside the work-group
+        (32, 1024, 1, 8, o(train_small_wg=0), (64, 4, 1)),         # a half-empty 64-row tile
+        (96, 1024, 1, 8, o(train_small_wg=0), (64, 4, 1)),         # 32 tiles, the second row of them half empty
+        (36, 1024, 1, 8, o(), (64, 4, 1)),                         # M no multiple of 32: never the 32-row tile
+        (160, 256, 8, 24, o(train_big=1), (128, 8, 1)),            # 2 x 2 x 8 = 32 tiles: x8 (3 steps each) = 256 work-groups; x16 would leave one step
+        (160, 256, 8, 24, o(train_big=1, train_intra_split=1), (128, 8, 1)),      # no two-quartet form of the 128-row tile
+        (64, 1024, 1, 8, o(train_big=1), (32, 4, 1)),              # M < 128: not the 128-row tile
+        (256, 64, 1, 8, o(train_big=1), (32, 4, 1)),               # N < 128: neither; 8 tiles
+        (256, 1024, 1, 1, o(), (32, 1, 1)),                        # a weight gradient over 32 rows: one K step, no split
+        (256, 1024, 1, 1, o(train_intra_split=1), (32, 1, 1)),     # ... and nothing to hand to a second quartet
+        (32, 1024, 1, 8, o(train_split=0), (32, 1, 1)),
+        (32, 1024, 1, 8, o(train_wg_target=48), (32, 4, 1)),       # 16 -> 32 -> 64 work-groups
+        (32, 1024, 1, 64, o(train_wg_target=48), (32, 4, 1)),      # the target stops it, not the depth
+        (32, 1024, 1, 64, o(train_wg_target=1536), (32, 32, 1)),   # 16 x 32 = 512 < 1536: the cap of 32
+        (32, 64, 1, 4096, o(), (32, 32, 1)),                       # one tile, K deep: the cap of 32
+        (256, 256, 5, 48, o(), (32, 4, 1)),                        # 4 x 8 x 5 = 160 tiles -> 320 (< 384) -> 640: split while the launch is below the target
+    ]
+    for M, N, nb, steps, opt, want in table:
+        assert TC.gemm_shape(M, N, nb, steps, opt) == want, (M, N, nb, steps, want)
+    assert TC.gemm_shape(32, 1024, 1, 8, o(), can_split=False) == (32, 1, 1)
+    assert TC.kernel_of("tn", 64, 2) == "tn_64_ki2" and TC.kernel_of("nn", 128, 1) == "nn_128" and len(TC.KERNELS) == 15 and len(TC.COUNTERS) == 17
+
+
+def test_the_shape_cases_reach_every_training_gemm_instantiation():
+    """Over the (case, configuration) pairs tests/test_hip_train_shapes.py runs against the float64 oracle, the counters it requires to rise
+    cover all 15 instantiations, the in-launch split-K finish and the reduce launch; and no requirement contradicts a prohibition."""
+    from tests import train_cases as TC
+    from tests.test_hip_train_shapes import CASES
+    seen = set()
+    for name, (model, n, _, cfgs) in CASES.items():
+        for cfg in cfgs:
+            must, never = TC.expected(model, -(-n // 32) * 32, cfg)
+            seen |= must
+    assert seen == set(TC.KERNELS) | {"fused", "reduce"}, sorted((set(TC.KERNELS) | {"fused", "reduce"}) - seen)
+    # the table's cells at the batches that can reach them
+    assert {"nn_32", "nt_32", "tn_32", "fused"} <= TC.expected("planner", 64, "t32")[0]
+    assert {"nn_64", "nt_64", "tn_64"} <= TC.expected("planner", 32, "t64")[0]
+    assert {"nn_128", "nt_128", "tn_128"} <= TC.expected("planner", 160, "t128")[0] and {"nn_128", "nt_128", "tn_128"} <= TC.expected("idm", 320, "t128")[0]
+    assert "tn_128" in TC.expected("planner", 64, "t128")[0] and not {"nn_128", "nt_128"} & TC.expected("planner", 64, "t128")[0]
+    assert {"tn_128", "nn_64", "nt_64"} <= TC.expected("planner", 64, "t128_64")[0]
+    assert {"nn_32_ki2", "nt_32_ki2", "tn_32_ki2"} <= TC.expected("planner", 32, "ki2_32")[0]
+    assert {"nn_64_ki2", "nt_64_ki2", "tn_64_ki2"} <= TC.expected("planner", 32, "ki2_64")[0] and {"nn_64_ki2", "nt_64_ki2", "tn_64_ki2"} <= TC.expected("idm", 320, "ki2_64")[0]
+    assert "fused" in TC.expected("planner", 64, "deep")[0] and "reduce" in TC.expected("idm", 32, "reduce")[0]
