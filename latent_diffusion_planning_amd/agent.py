@@ -24,6 +24,8 @@ Differences that are deliberate and documented:
 """
 from __future__ import annotations
 
+import collections
+import contextlib
 import copy
 import itertools
 import warnings
@@ -37,6 +39,9 @@ from .arrays import CallRecord, DeviceArray, as_tensor
 from .engine import HipEngine
 
 _versions = itertools.count(1)        # tokens of parameter trees (never reused, unlike id())
+
+# one diffusion network of an agent (LDPAgent._nets): where it lives and how one training step drives it
+_Net = collections.namedtuple("_Net", "key eng slot shapes grad stream noise steps")
 
 # vae_feature_dim -> (latent side, latent channels) as agent/ldp_agent.py:69-80 reshapes them; the image side is
 # 32 x the latent side (five stride-2 stages): 64-pixel frames for 16 / 32, 96-pixel frames for 36 (3x3x4), 128 for 64.
@@ -108,6 +113,63 @@ class ParamState:
             new.version = kw.pop("version")
         if kw:
             raise AttributeError(f"ParamState has no field(s) {sorted(kw)}")
+        return new
+
+
+class DPState(ParamState):
+    """flax_utils.TrainStateEMA (utils/flax_utils.py:18-27) as DPVAEAgent's callers see it: ParamState plus an EMA tree with a version
+    token of its own (`ema_version`), so the engine's single sampling slot always knows which of the two weight sets it holds.  The EMA
+    of a trained state lives in the engine's EMA arena and is fetched on first access, like its parameters."""
+
+    def __init__(self, params=None, ema_params=None, step: int = 0, version: Optional[int] = None, opt_state=None, _fetch=None,
+                 ema_version: Optional[int] = None, _ema_fetch=None, ema_is_params: bool = False):
+        self._ema = None
+        super().__init__(params, ema_params, step, version, opt_state, _fetch)
+        self.ema_version = next(_versions) if ema_version is None else ema_version
+        self._ema_fetch = _ema_fetch
+        # the EMA equals the parameters (TrainStateEMA.create, load_snapshot): restoring the state re-seeds the engine's EMA arena from them
+        self.ema_is_params = bool(ema_is_params)
+
+    @property
+    def ema_params(self):
+        if self._ema is None and self._ema_fetch is not None:
+            self._ema = self._ema_fetch()
+        if self._ema is None and self.ema_is_params:
+            return self.params
+        return self._ema
+
+    @ema_params.setter
+    def ema_params(self, value):
+        self._ema = value
+
+    def replace(self, **kw):
+        new = DPState(self._params, None, self.step, self.version, self._opt_state, self._fetch, self.ema_version, self._ema_fetch,
+                      self.ema_is_params)
+        new._ema = self._ema
+        same = "params" in kw and "ema_params" in kw and kw["ema_params"] is kw["params"]
+        if "params" in kw and "ema_params" not in kw and self.ema_is_params:
+            new._ema = self.params                      # the EMA stays what it was: the OLD parameters
+        if "params" in kw:
+            new.version = kw.pop("version", next(_versions))
+            new._params = _as_flat(kw.pop("params"))
+            new._fetch = None
+            new._opt_state = None if "opt_state" not in kw else new._opt_state
+            new.ema_is_params = False
+        if "ema_params" in kw:
+            e = kw.pop("ema_params")
+            new.ema_version = kw.pop("ema_version", next(_versions))
+            new._ema_fetch = None
+            new._ema = None if same or e is None else _as_flat(e)
+            new.ema_is_params = same
+        if "opt_state" in kw:
+            o = kw.pop("opt_state")
+            new._opt_state = None if o is None else dict(mu=_as_flat(o["mu"]), nu=_as_flat(o["nu"]), count=int(o.get("count", new.step)))
+            new.version = next(_versions) if new._fetch is None else new.version
+        for k in ("step", "version", "ema_version"):
+            if k in kw:
+                setattr(new, k, int(kw.pop(k)) if k == "step" else kw.pop(k))
+        if kw:
+            raise AttributeError(f"DPState has no field(s) {sorted(kw)}")
         return new
 
 
@@ -285,6 +347,84 @@ class _EngineCalls:
                 for e in self._engines():
                     e.poll_fault_kinds()
 
+    def _call(self, run, recompute=None):
+        """One policy call under the fault protocol -> (run()'s tensors, the CallRecord its DeviceArrays carry).  recompute: what a later
+        fault poll runs instead of `run` (a call with lazy arrays, or one that must not run twice)."""
+        rec = self._record(run if recompute is None else recompute)
+        res = self._guarded(run)
+        rec.seqs = self._seqs()
+        return res, rec
+
+    # ---- the hand-off between a state (ParamState / DPState) and one module slot of an engine handle ---------------------------
+    _ema_decay = None                     # decay of the parameter EMA a class trains with (DPVAEAgent, StableVAEModel); None: no EMA, ParamState
+
+    def _slot_weights(self, eng, slot, state, shapes, use_ema=False):
+        """Sampling side: the slot must hold this state's parameters (its EMA when use_ema; each set has its own token).  Nothing to do when
+        the engine already holds the token; a state an update() left in the training arenas is published from there (master parameters ->
+        packed sampling layouts on the device, no tree passes through Python); otherwise -> the checked host tree, for the caller to upload
+        under that token (LDPAgent sends several slots in one load_params).  shapes: () -> {path: shape}, called only for a host tree."""
+        want = state.ema_version if use_ema else state.version
+        if eng.loaded[slot] == want:
+            return None
+        if getattr(eng, "train_ema_token" if use_ema else "train_token", {}).get(slot) == want:
+            (eng.train_publish_ema if use_ema else eng.train_publish)([slot], versions={slot: want})
+            return None
+        tree = state.ema_params if use_ema else state.params
+        W.check_params(tree, shapes())
+        return tree
+
+    def _train_sync(self, slot, state, shapes, eng=None):
+        """Training side: the arenas of `eng` (default: the first handle) must hold THIS state -- parameters, Adam moments (fresh when the
+        state has none) and, for a class with an EMA, the EMA arena: enabled with the class's decay, re-seeded from the parameters by the
+        (re)load, then overwritten with a distinct EMA tree.  Another model sharing the engine, a load_snapshot or a fresh create may have left
+        something else there.  A (re)load synchronises the device: call it before anything of the step is in flight."""
+        eng = self._engine if eng is None else eng
+        decay = self._ema_decay
+        if eng.train_token.get(slot) == state.version and (decay is None or eng.train_ema_token.get(slot) == state.ema_version):
+            return
+        W.check_params(state.params, shapes)
+        ema = None if decay is None or state.ema_is_params else state.ema_params          # (read before the arenas are overwritten)
+        o = state.opt_state
+        eng.train_load(slot, state.params, mu=None if o is None else o["mu"], nu=None if o is None else o["nu"], step=state.step,
+                       token=state.version)
+        if decay is None:
+            return
+        if eng.ema_decay.get(slot) != decay:
+            eng.train_ema(slot, decay)
+        if ema is not None:
+            W.check_params(ema, shapes)
+            eng.train_write(slot, eng.TRAIN_EMA, ema)
+        eng.train_ema_token[slot] = state.ema_version
+
+    def _trained_state(self, slot, old, shapes, eng=None):
+        """The state after a step: parameters, moments and EMA stay in the arenas and are fetched on demand, while it is the newest state."""
+        eng = self._engine if eng is None else eng
+        with_ema = self._ema_decay is not None
+        token, etoken = next(_versions), next(_versions) if with_ema else None
+        eng.train_token[slot] = token
+        if with_ema:
+            eng.train_ema_token[slot] = etoken
+        which = {"params": eng.TRAIN_PARAMS, "mu": eng.TRAIN_MU, "nu": eng.TRAIN_NU, "ema": eng.TRAIN_EMA}
+
+        def fetch(what):
+            if eng.train_token.get(slot) != token or (what == "ema" and eng.train_ema_token.get(slot) != etoken):
+                raise RuntimeError(f"this {slot} state was superseded by a later update(): its buffers were donated to the next step "
+                                   "(keep what update() returned, as train_bc.py:107 and train_vae.py do)")
+            return eng.train_read(slot, which[what], shapes)
+        if with_ema:
+            return DPState(None, None, old.step + 1, token, None, fetch, etoken, lambda: fetch("ema"))
+        return ParamState(None, old.ema_params, old.step + 1, token, None, fetch)
+
+    # ---- the statistics scalars of a metrics dict: 4-vectors (min, max, mean, std) on the device, a metric is one element of its vector ----
+    @staticmethod
+    def _stat_metrics(m, emb_key, arrs, obs_keys, n=2):
+        """arrs: the reduce_stats vectors of [embedding / condition, actions, every obs key]; the first n of the four statistics per obs key."""
+        tail = ("min", "max", "mean", "std")
+        m.update({f"{emb_key}_{s}": _Elem(arrs[0], i) for i, s in enumerate(tail)})
+        m["action_min"], m["action_max"] = _Elem(arrs[1], 0), _Elem(arrs[1], 1)
+        for j, k in enumerate(obs_keys):
+            m.update({f"{k}_{s}": _Elem(arrs[2 + j], i) for i, s in enumerate(tail[:n])})
+
 
 class LDPAgent(_EngineCalls):
     # ---------------------------------------------------------------------------------------------
@@ -456,24 +596,36 @@ class LDPAgent(_EngineCalls):
     def _sync_weights(self, need_vae=False):
         """Upload whatever the (possibly shared) engine does not hold for THIS agent: the engine keeps the
         version token of each module's tree, the agent compares it with its own."""
-        up, ver = {}, {}
-        held = self._engine.loaded
-        for name, use, st, shapes in (("planner", self.use_planner, self.planner_state, self._planner_shapes),
-                                      ("idm", self.use_idm, self.idm_state, self._idm_shapes)):
-            if not use or held[name] == st.version:
-                continue
-            if self._engine.train_token.get(name) == st.version:
-                # the state an update() left in the training arenas: master parameters -> packed sampling layouts, on the device side
-                self._engine.train_publish([name], versions={name: st.version})
-                continue
-            W.check_params(st.params, shapes())
-            up[name], ver[name] = st.params, st.version
-        if need_vae and held["vae"] != self._vae_version:
+        use_ema, ups = self._sample_ema, []                   # ups: (handle, slot, tree, token) still to upload
+        for net in self._nets():
+            st = getattr(self, f"{net.key}_state")
+            tree = self._slot_weights(net.eng, net.slot, st, net.shapes, use_ema)
+            if tree is not None:
+                ups.append((net.eng, net.slot, tree, st.ema_version if use_ema else st.version))
+        if need_vae and self._engine.loaded["vae"] != self._vae_version:
             if self.vae_params is None:
                 raise ValueError("raw image observations need VAE weights (vae_pretrain_path / vae_params)")
-            up["vae"], ver["vae"] = self.vae_params, self._vae_version
-        if up:
-            self._engine.load_params(**up, versions=ver)
+            ups.append((self._engine, "vae", self.vae_params, self._vae_version))
+        for eng in self._engines():                           # one load_params per handle
+            mine = [u for u in ups if u[0] is eng]
+            if mine:
+                eng.load_params(**{slot: tree for _, slot, tree, _ in mine}, versions={slot: token for _, slot, _, token in mine})
+
+    _sample_ema = False                                       # sample with the EMA of the parameters (DPVAEAgent's use_ema)
+
+    def _nets(self):
+        """The diffusion networks of this agent, the planner first: `key` names the `<key>_state` attribute, the schedule, the alpha and
+        the metric prefix; `eng` / `slot` say where the network lives (LDPHierAgent's IDM is a U-Net in a second handle's planner slot);
+        `grad` is its tape, for the planner (x0, eps, t, cond, alpha) and for the IDM (s, a, eps, t, alpha); `stream` is the Philox stream
+        of its training noise, `noise` the keys of its explicit timesteps / noise, `steps` its number of diffusion steps."""
+        cfg, eng = self.config, self._engine
+        nets = []
+        if self.use_planner:
+            nets.append(_Net("planner", eng, "planner", self._planner_shapes, eng.train_planner_grad, 7, ("t_plan", "noise_plan"),
+                             cfg.get("planner_n_diffusion_steps")))
+        if self.use_idm:
+            nets.append(_Net("idm", eng, "idm", self._idm_shapes, eng.train_idm_grad, 8, ("t_idm", "noise_idm"), cfg.get("idm_n_diffusion_steps")))
+        return nets
 
     def _planner_shapes(self):
         return W.planner_shapes(self._planner_spec)
@@ -503,9 +655,7 @@ class LDPAgent(_EngineCalls):
         def run():
             out = self._vae_encode_t(batch)
             return [out[k] for k in out]
-        rec = self._record(run)
-        res = self._guarded(run)
-        rec.seqs = self._seqs()
+        res, rec = self._call(run)
         order = [(f"latent_{k}" if k in keys else k) for k in batch.keys()]
         return {k: DeviceArray(t, record=rec) for k, t in zip(order, res)}
 
@@ -544,9 +694,7 @@ class LDPAgent(_EngineCalls):
 
         def run():
             return [self._vae_decode_t(t)]
-        rec = self._record(run)                                # the decoder's split convs sit behind the range guard
-        res = self._guarded(run)
-        rec.seqs = self._seqs()
+        res, rec = self._call(run)                                # the decoder's split convs sit behind the range guard
         return DeviceArray(res[0], record=rec)
 
     # ---- agent/ldp_agent.py:88-97 -----------------------------------------------------------------
@@ -586,9 +734,7 @@ class LDPAgent(_EngineCalls):
             obs = self._vae_encode_t(nb["obs"])
             start = self.get_obs_cond(obs)
             return [self._idm_actions(start, self._t(next_plan), seed, start.shape[0], noise)]
-        rec = self._record(run)
-        res = self._guarded(run)
-        rec.seqs = self._seqs()
+        res, rec = self._call(run)
         return DeviceArray(res[0], record=rec)
 
     # ---- agent/ldp_agent.py:391-430 ---------------------------------------------------------------
@@ -601,9 +747,7 @@ class LDPAgent(_EngineCalls):
             obs = self._vae_encode_t(nb["obs"])
             plan = self.get_obs_cond(obs)
             return [self._idm_actions(plan[:, :-1], plan[:, 1:], seed, plan.shape[0], noise)]
-        rec = self._record(run)
-        res = self._guarded(run)
-        rec.seqs = self._seqs()
+        res, rec = self._call(run)
         return DeviceArray(res[0], record=rec)
 
     # ---- agent/ldp_agent.py:432-506 ---------------------------------------------------------------
@@ -657,9 +801,7 @@ class LDPAgent(_EngineCalls):
             if obs_emb.shape[1] > oh:                          # from a training batch, not inference (:447-448)
                 out.append(self._engine.mean_sq_diff(x, obs_emb[:, oh:]))
             return out
-        rec = self._record(lambda: run() + [None])             # plan_viz re-decodes itself from the new plan
-        res = self._guarded(run)
-        rec.seqs = self._seqs()
+        res, rec = self._call(run, lambda: run() + [None])             # plan_viz re-decodes itself from the new plan
         action = DeviceArray(res[0], record=rec)
         plan = DeviceArray(res[1], record=rec)
         metrics = {"plan": plan}
@@ -696,39 +838,15 @@ class LDPAgent(_EngineCalls):
         use_planner, use_idm = self._gates(int(step))
         return self._update_step(batch, mixed_batch, rng, use_planner, use_idm, noise)
 
-    def _train_sync(self, name, state, shapes, eng=None):
-        """The engine's training arenas must hold THIS agent's state of the module (another agent sharing the engine, a load_snapshot or a
-        fresh create may have left something else there).  eng: the handle that trains the module (default: the agent's first)."""
-        eng = self._engine if eng is None else eng
-        if eng.train_token.get(name) == state.version:
-            return
-        W.check_params(state.params, shapes)
-        o = state.opt_state
-        eng.train_load(name, state.params, mu=None if o is None else o["mu"], nu=None if o is None else o["nu"], step=state.step,
-                       token=state.version)
-
-    def _trained_state(self, name, old, shapes, eng=None):
-        """The state after this step: parameters / moments stay on the GPU and are fetched on demand (while it is the newest state)."""
-        eng = self._engine if eng is None else eng
-        token = next(_versions)
-        eng.train_token[name] = token
-        which = {"params": eng.TRAIN_PARAMS, "mu": eng.TRAIN_MU, "nu": eng.TRAIN_NU}
-
-        def fetch(what):
-            if eng.train_token.get(name) != token:
-                raise RuntimeError(f"this {name} state was superseded by a later update(): its buffers were donated to the next step "
-                                   "(keep the agent that update() returned, as train_bc.py:107 does)")
-            return eng.train_read(name, which[what], shapes)
-        return ParamState(None, old.ema_params, old.step + 1, token, None, fetch)
-
     def _update_step(self, batch, mixed_batch, rng, use_planner, use_idm, noise, shard=None):
-        """shard (dist.update_sharded): dict(group, rows=(lo, n), mixed_rows=(lo, n)) -- `batch` / `mixed_batch` are rows [lo, lo + B) of a
+        """One step of the networks `_nets` describes, on what `_planner_targets` / `_idm_pairs` read of the batch(es).
+        shard (dist.update_sharded): dict(group, rows=(lo, n), mixed_rows=(lo, n)) -- `batch` / `mixed_batch` are rows [lo, lo + B) of a
         global batch of n rows split over the ranks of `group`.  Timesteps and noise are those of the global rows (so the step does not
         depend on the world size), each rank's loss is weighted B / n, the gradient arenas are summed over the ranks with one all-reduce per
-        module, and everything after it (global norm, Adam) runs replicated."""
-        cfg, eng = self.config, self._engine
+        network, and everything after it (global norm, Adam) runs replicated."""
+        cfg = self.config
         if not self._lr_schedules:
-            raise ValueError("update() needs the optimiser settings of LDPAgent.create (lr, end_lr, idm_lr, idm_end_lr, warmup_steps, decay_steps)")
+            raise ValueError(f"update() needs the optimiser settings of {type(self).__name__}.create (lr, end_lr, idm_lr, idm_end_lr, warmup_steps, decay_steps)")
         seed = _seed_of(rng)
         oh = cfg["obs_horizon"]
         nz = noise or {}
@@ -738,110 +856,102 @@ class LDPAgent(_EngineCalls):
         obs_emb = self.get_obs_cond(nb["obs"]).contiguous()
         action = nb["actions"]
         emb_i, action_i = obs_emb, action
-        if mixed_batch is not None:
+        if mixed_batch is not None:                                   # loss_mixed: the IDM learns from the mixed batch
             nbm = self._postprocess(mixed_batch)
             emb_i, action_i = self.get_obs_cond(nbm["obs"]).contiguous(), nbm["actions"]
         B, Bi = obs_emb.shape[0], emb_i.shape[0]
-        lo_p, n_p = (0, B) if shard is None else shard["rows"]
-        lo_i, n_i = (0, Bi) if shard is None else shard.get("mixed_rows", shard["rows"]) if mixed_batch is not None else shard["rows"]
-        w_p, w_i = np.float32(B) / np.float32(n_p), np.float32(Bi) / np.float32(n_i)     # 1 without shards
-
-        def rows_of(x, lo, n_loc, n_glob, per=1):
-            """An explicit parity input given for the global batch -> this rank's rows."""
-            return x[lo * per:(lo + n_loc) * per] if len(x) == n_glob * per and n_glob != n_loc else x
+        rows_p = (0, B) if shard is None else shard["rows"]           # (first global row, global rows): the weights are 1 without shards
+        rows_i = (0, Bi) if shard is None else shard.get("mixed_rows", shard["rows"]) if mixed_batch is not None else shard["rows"]
+        trained = {n.key: n for n in self._nets() if (use_planner if n.key == "planner" else use_idm)}
+        pn, im = trained.get("planner"), trained.get("idm")
         hg = np.random.Generator(np.random.PCG64(seed & (2**63 - 1)))
+
+        def rows_of(x, rows, n_loc, per=1):
+            """An explicit parity input given for the global batch -> this rank's rows."""
+            lo, n_glob = rows
+            return x[lo * per:(lo + n_loc) * per] if len(x) == n_glob * per and n_glob != n_loc else x
+
+        def timesteps(net, rows, n_loc, per=1):
+            """One per row of the network's x0, of the GLOBAL batch: given, or the generator's next draw."""
+            t = nz.get(net.noise[0])
+            return rows_of(np.asarray(hg.integers(0, int(net.steps), size=rows[1] * per) if t is None else t).reshape(-1), rows, n_loc, per)
+
+        def noise_of(net, x0, rows, n_loc):
+            eps = nz.get(net.noise[1])
+            if eps is not None:
+                return self._t(rows_of(eps, rows, n_loc, x0.shape[0] // n_loc))
+            return _philox_normal(seed, rows[0] * (x0.numel() // n_loc), 0, net.stream, x0.numel(), self._device).reshape(x0.shape)
+
+        def weight(net, rows, n_loc):
+            return float(np.float32(getattr(self, f"alpha_{net.key}")) * (np.float32(n_loc) / np.float32(rows[1])))
         zero = torch.zeros((), dtype=torch.float32, device=self._device)
         plan_loss = idm_loss = zero
-        mods = []
         # The two networks' gradients are independent: the IDM's tape (0.5 ms at 256 samples) is enqueued FIRST, on a second stream, and runs next to
         # the planner's (csrc/train.hip keeps one workspace lane per module); the statistics scalars read inputs only and go to a third.  The
         # main stream waits for both before anything reads a gradient or a scalar.
-        if use_planner:                                               # (a (re)load of a module's training state synchronises the device: before anything is in flight)
-            self._train_sync("planner", self.planner_state, self._planner_shapes())
-        if use_idm:
-            self._train_sync("idm", self.idm_state, self._idm_shapes())
-        main = torch.cuda.current_stream(self._device)
+        for net in trained.values():                                  # (a (re)load of a training state synchronises the device: before anything is in flight)
+            self._train_sync(net.slot, getattr(self, f"{net.key}_state"), net.shapes(), eng=net.eng)
+        eng = self._engine
         side = eng.aux_streams() if eng.get_option("train_streams") else {}
-        idm_stream = side.get("idm") if (use_planner and use_idm) else None
+        idm_stream = side.get("idm") if (pn and im) else None
         stats_stream = side.get("stats")
-        if stats_stream is not None:
-            stats_stream.wait_stream(main)
-        with torch.cuda.stream(stats_stream if stats_stream is not None else main):
+        main = torch.cuda.current_stream(self._device) if side else None     # (no side stream: the step touches no stream at all)
+
+        def on(stream):
+            """Enqueue on a side stream, behind what the main stream holds so far -- or on the main stream itself."""
+            if stream is None:
+                return contextlib.nullcontext()
+            stream.wait_stream(main)
+            return torch.cuda.stream(stream)
+        with on(stats_stream):
             stats = [eng.reduce_stats(obs_emb), eng.reduce_stats(action)] + [eng.reduce_stats(nb["obs"][k]) for k in nb["obs"]]
         # host draws in the reference's order of use (planner, then IDM), whatever the enqueue order below
-        t_plan = t_idm = None
-        if use_planner:
-            npl = int(cfg["planner_n_diffusion_steps"])
-            t_plan = nz.get("t_plan")
-            t_plan = rows_of(np.asarray(hg.integers(0, npl, size=n_p) if t_plan is None else t_plan).reshape(-1), lo_p, B, n_p)
-        if use_idm:                                                   # idm_loss, :129-140
-            s = torch.cat([emb_i[:, oh - 1:-1], emb_i[:, oh:]], dim=-1)
-            s = s.reshape(-1, s.shape[-1]).contiguous()               # 'B H D -> (B H) D'
-            a = action_i[:, :-1].reshape(-1, action_i.shape[-1]).contiguous()
-            if a.shape[0] != s.shape[0]:
-                raise ValueError(f"idm_loss pairs {s.shape[0]} transitions with {a.shape[0]} actions: the batch needs "
-                                 "actions.shape[1] - 1 == obs.shape[1] - obs_horizon (agent/ldp_agent.py:130-131)")
-            nid = int(cfg["idm_n_diffusion_steps"])
-            H = a.shape[0] // Bi                                      # transitions per sample
-            t_idm = nz.get("t_idm")
-            t_idm = rows_of(np.asarray(hg.integers(0, nid, size=n_i * H) if t_idm is None else t_idm).reshape(-1), lo_i, Bi, n_i, H)
-            eps_i = nz.get("noise_idm")
-            eps_i = (self._t(rows_of(eps_i, lo_i, Bi, n_i, H)) if eps_i is not None
-                     else _philox_normal(seed, lo_i * H * a.shape[-1], 0, 8, a.numel(), self._device).reshape(a.shape))
-            if idm_stream is not None:
-                idm_stream.wait_stream(main)                          # its inputs were written on the main stream
-            with torch.cuda.stream(idm_stream if idm_stream is not None else main):
-                idm_loss = eng.train_idm_grad(s, a, eps_i, t_idm, float(np.float32(self.alpha_idm) * w_i))
-        if use_planner:                                               # plan_loss, :113-127
-            nxt = obs_emb[:, oh:].contiguous()
-            eps = nz.get("noise_plan")
-            per = nxt.numel() // B
-            eps = (self._t(rows_of(eps, lo_p, B, n_p)) if eps is not None
-                   else _philox_normal(seed, lo_p * per, 0, 7, nxt.numel(), self._device).reshape(nxt.shape))
+        t_plan = timesteps(pn, rows_p, B) if pn else None
+        if im:                                                        # idm_loss
+            s, a = self._idm_pairs(emb_i, action_i)
+            t_idm = timesteps(im, rows_i, Bi, a.shape[0] // Bi)       # one per transition
+            eps = noise_of(im, a, rows_i, Bi)
+            with on(idm_stream):                                      # (its inputs were written on the main stream)
+                idm_loss = im.grad(s, a, eps, t_idm, weight(im, rows_i, Bi))
+        if pn:                                                        # plan_loss
+            nxt = self._planner_targets(obs_emb)
+            eps = noise_of(pn, nxt, rows_p, B)
             cond = obs_emb[:, :oh].reshape(B, -1).contiguous()
-            plan_loss = eng.train_planner_grad(nxt, eps, t_plan, cond, float(np.float32(self.alpha_planner) * w_p))
-            mods.append("planner")
-        if use_idm:
-            mods.append("idm")
+            plan_loss = pn.grad(nxt, eps, t_plan, cond, weight(pn, rows_p, B))
         for st in (idm_stream, stats_stream):
             if st is not None:
                 main.wait_stream(st)
         if shard is not None:                                         # data parallel: sum of the B / n weighted shard gradients = the global batch's
             import torch.distributed as tdist
-            for name in mods:
-                tdist.all_reduce(eng.train_arena(name, eng.TRAIN_GRADS), group=shard.get("group"))
+            for net in trained.values():
+                tdist.all_reduce(net.eng.train_arena(net.slot, net.eng.TRAIN_GRADS), group=shard.get("group"))
             both = torch.stack([plan_loss.reshape(()), idm_loss.reshape(())])
             tdist.all_reduce(both, group=shard.get("group"))
             plan_loss, idm_loss = both[0], both[1]
-        rep = self.lr_schedule
-        new_p, new_i = self.planner_state, self.idm_state
-        m = {}
-        if use_planner:
-            st = self.planner_state
-            eng.train_apply("planner", float(np.float32(self._lr_schedules["planner"](st.step))))
-            m["planner_lr"], m["planner_step"] = np.float32(rep(st.step)), st.step        # the OLD state's step, the LAST-built schedule (:257-258)
-            new_p = self._trained_state("planner", st, self._planner_shapes())
-        else:
-            m.update(planner_lr=0, planner_step=0, noise_diff=0)
-        if use_idm:
-            st = self.idm_state
-            eng.train_apply("idm", float(np.float32(self._lr_schedules["idm"](st.step))))
-            m["idm_lr"], m["idm_step"] = np.float32(rep(st.step)), st.step
-            new_i = self._trained_state("idm", st, self._idm_shapes())
-        else:
-            m.update(idm_lr=0, idm_step=0)
+        new, m = {}, {}
+        for key, off in (("planner", dict(planner_lr=0, planner_step=0, noise_diff=0)), ("idm", dict(idm_lr=0, idm_step=0))):
+            net = trained.get(key)
+            if net is None:
+                m.update(off)
+                continue
+            st = getattr(self, f"{key}_state")
+            net.eng.train_apply(net.slot, float(np.float32(self._lr_schedules[key](st.step))))
+            m[f"{key}_lr"], m[f"{key}_step"] = np.float32(self.lr_schedule(st.step)), st.step     # the OLD state's step, the LAST-built schedule (:257-258)
+            new[f"{key}_state"] = self._trained_state(net.slot, st, net.shapes(), eng=net.eng)
         # linear_algebra.global_norm(grads), :253 -- a metric only (nothing is clipped), taken after the optimiser launches, which leave the
-        # per-stripe sums of squares of the gradients they consumed behind (one small launch instead of a second pass over the arenas)
-        g_norm = eng.train_grad_norm(mods) if mods else zero
-        arrs = [DeviceArray(x) for x in (plan_loss, idm_loss, g_norm)] + [DeviceArray(x) for x in stats]
+        # per-stripe sums of squares of the gradients they consumed behind (one small launch instead of a second pass over the arenas): one
+        # call per engine handle over the slots it trained; two handles' norms (LDPHierAgent) combine as sqrt(a^2 + b^2)
+        handles = {}
+        for net in trained.values():
+            handles.setdefault(id(net.eng), (net.eng, []))[1].append(net.slot)
+        norms = [e.train_grad_norm(slots) for e, slots in handles.values()]
+        g_norm = zero if not norms else norms[0] if len(norms) == 1 else torch.sqrt(norms[0].double() ** 2 + norms[1].double() ** 2).float()
+        arrs = [DeviceArray(x) for x in [plan_loss, idm_loss, g_norm] + stats]
         # (alpha_planner / alpha_idm are already inside the two device scalars: the gradients are those of the weighted losses)
         m.update(plan_loss=_HostScalar(lambda: arrs[0].numpy()), idm_loss=_HostScalar(lambda: arrs[1].numpy()),
                  loss=_HostScalar(lambda: arrs[0].numpy() + arrs[1].numpy()), g_norm=_HostScalar(lambda: arrs[2].numpy()))
-        m["emb_min"], m["emb_max"], m["emb_mean"], m["emb_std"] = (_Elem(arrs[3], i) for i in range(4))
-        m["action_min"], m["action_max"] = _Elem(arrs[4], 0), _Elem(arrs[4], 1)
-        for j, k in enumerate(nb["obs"]):
-            m[f"{k}_min"], m[f"{k}_max"] = _Elem(arrs[5 + j], 0), _Elem(arrs[5 + j], 1)
-        return self.replace(planner_state=new_p, idm_state=new_i), m
+        self._stat_metrics(m, "emb", arrs[3:], nb["obs"])
+        return self.replace(**new), m
 
     # ---- agent/ldp_agent.py:113-180, 328-349: the training losses, FORWARD ONLY ---------------------------
     def get_metrics(self, batch, rng, noise=None):
@@ -895,9 +1005,7 @@ class LDPAgent(_EngineCalls):
                    eng.reduce_stats(obs_emb), eng.reduce_stats(action)]
             out += [eng.reduce_stats(nb["obs"][k]) for k in nb["obs"]]
             return out
-        rec = self._record(run)
-        res = self._guarded(run)
-        rec.seqs = self._seqs()
+        res, rec = self._call(run)
         keys = list(self._postprocess_keys(batch))
         arrs = [DeviceArray(t, record=rec) for t in res]
         # the two mean-squared errors are device scalars; alpha_planner / alpha_idm and the sum (agent/ldp_agent.py:146-158) are applied in
@@ -905,11 +1013,7 @@ class LDPAgent(_EngineCalls):
         ap, ai = np.float32(self.alpha_planner if self.use_planner else 0), np.float32(self.alpha_idm if self.use_idm else 0)
         m = dict(plan_loss=_HostScalar(lambda: ap * arrs[0].numpy()), idm_loss=_HostScalar(lambda: ai * arrs[1].numpy()),
                  loss=_HostScalar(lambda: ap * arrs[0].numpy() + ai * arrs[1].numpy()))
-        # the statistics live in 4-vectors (min, max, mean, std) on the device; a metric is one element of its vector
-        m["emb_min"], m["emb_max"], m["emb_mean"], m["emb_std"] = (_Elem(arrs[2], i) for i in range(4))
-        m["action_min"], m["action_max"] = _Elem(arrs[3], 0), _Elem(arrs[3], 1)
-        for j, k in enumerate(keys):
-            m[f"{k}_min"], m[f"{k}_max"] = _Elem(arrs[4 + j], 0), _Elem(arrs[4 + j], 1)
+        self._stat_metrics(m, "emb", arrs[2:], keys)
         return m
 
     # what the two losses read of a training batch (LDPHierAgent overrides the three: strided targets, a U-Net IDM)

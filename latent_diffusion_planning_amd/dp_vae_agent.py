@@ -21,67 +21,10 @@ import numpy as np
 import torch
 
 from . import weights as W
-from .agent import (LATENT_SHAPES, LDPAgent, ParamState, _Elem, _HostScalar, _as_flat, _get, _norm_entry, _philox_normal, _seed_of,
-                    _versions, load_pretrained_vae)
+from .agent import (LATENT_SHAPES, DPState, LDPAgent, _HostScalar, _as_flat, _get, _norm_entry, _philox_normal, _seed_of,   # noqa: F401
+                    load_pretrained_vae)                 # (DPState, this agent's state class, is defined next to ParamState)
 from .arrays import DeviceArray
 from .engine import HipEngine
-
-
-class DPState(ParamState):
-    """flax_utils.TrainStateEMA (utils/flax_utils.py:18-27) as DPVAEAgent's callers see it: ParamState plus an EMA tree with a version
-    token of its own (`ema_version`), so the engine's single sampling slot always knows which of the two weight sets it holds.  The EMA
-    of a trained state lives in the engine's EMA arena and is fetched on first access, like its parameters."""
-
-    def __init__(self, params=None, ema_params=None, step: int = 0, version: Optional[int] = None, opt_state=None, _fetch=None,
-                 ema_version: Optional[int] = None, _ema_fetch=None, ema_is_params: bool = False):
-        self._ema = None
-        super().__init__(params, ema_params, step, version, opt_state, _fetch)
-        self.ema_version = next(_versions) if ema_version is None else ema_version
-        self._ema_fetch = _ema_fetch
-        # the EMA equals the parameters (TrainStateEMA.create, load_snapshot): restoring the state re-seeds the engine's EMA arena from them
-        self.ema_is_params = bool(ema_is_params)
-
-    @property
-    def ema_params(self):
-        if self._ema is None and self._ema_fetch is not None:
-            self._ema = self._ema_fetch()
-        if self._ema is None and self.ema_is_params:
-            return self.params
-        return self._ema
-
-    @ema_params.setter
-    def ema_params(self, value):
-        self._ema = value
-
-    def replace(self, **kw):
-        new = DPState(self._params, None, self.step, self.version, self._opt_state, self._fetch, self.ema_version, self._ema_fetch,
-                      self.ema_is_params)
-        new._ema = self._ema
-        same = "params" in kw and "ema_params" in kw and kw["ema_params"] is kw["params"]
-        if "params" in kw and "ema_params" not in kw and self.ema_is_params:
-            new._ema = self.params                      # the EMA stays what it was: the OLD parameters
-        if "params" in kw:
-            new.version = kw.pop("version", next(_versions))
-            new._params = _as_flat(kw.pop("params"))
-            new._fetch = None
-            new._opt_state = None if "opt_state" not in kw else new._opt_state
-            new.ema_is_params = False
-        if "ema_params" in kw:
-            e = kw.pop("ema_params")
-            new.ema_version = kw.pop("ema_version", next(_versions))
-            new._ema_fetch = None
-            new._ema = None if same or e is None else _as_flat(e)
-            new.ema_is_params = same
-        if "opt_state" in kw:
-            o = kw.pop("opt_state")
-            new._opt_state = None if o is None else dict(mu=_as_flat(o["mu"]), nu=_as_flat(o["nu"]), count=int(o.get("count", new.step)))
-            new.version = next(_versions) if new._fetch is None else new.version
-        for k in ("step", "version", "ema_version"):
-            if k in kw:
-                setattr(new, k, int(kw.pop(k)) if k == "step" else kw.pop(k))
-        if kw:
-            raise AttributeError(f"DPState has no field(s) {sorted(kw)}")
-        return new
 
 
 def dp_obs_cond(frame_emb: torch.Tensor, obs_horizon: int, img_width: int) -> torch.Tensor:
@@ -179,27 +122,9 @@ class DPVAEAgent(LDPAgent):
         """agent/dp_repr_agent.py:220-223."""
         return dict(planner_params=self.planner_state.params, planner_ema_params=self.planner_state.ema_params)
 
-    def _sync_weights(self, need_vae=False, use_ema=None):
-        """The sampling slot must hold THIS agent's parameters -- or their EMA when use_ema (:176-179): each set has its own token."""
-        eng, st = self._engine, self.planner_state
-        use_ema = bool(self.config["use_ema"]) if use_ema is None else use_ema
-        want = st.ema_version if use_ema else st.version
-        up, ver = {}, {}
-        if eng.loaded["planner"] != want:
-            if not use_ema and eng.train_token.get("planner") == st.version:
-                eng.train_publish(["planner"], versions={"planner": want})
-            elif use_ema and eng.train_ema_token.get("planner") == st.ema_version:
-                eng.train_publish_ema(["planner"], versions={"planner": want})
-            else:
-                tree = st.ema_params if use_ema else st.params
-                W.check_params(tree, self._planner_shapes())
-                up["planner"], ver["planner"] = tree, want
-        if need_vae and eng.loaded["vae"] != self._vae_version:
-            if self.vae_params is None:
-                raise ValueError("raw image observations need VAE weights (vae_pretrain_path / vae_params)")
-            up["vae"], ver["vae"] = self.vae_params, self._vae_version
-        if up:
-            eng.load_params(**up, versions=ver)
+    # the hand-off between planner_state and the engine is LDPAgent's: sampling with the EMA when use_ema (:176-179), training with one
+    _sample_ema = property(lambda self: bool(self.config["use_ema"]))
+    _ema_decay = property(lambda self: self.config["planner_ema_decay"])
 
     # ---- agent/dp_repr_agent.py:76-85 ---------------------------------------------------------------
     def _frame_emb(self, obs) -> torch.Tensor:
@@ -226,9 +151,7 @@ class DPVAEAgent(LDPAgent):
             return [self._engine.policy_sample(self._frame_emb(obs), cfg["obs_horizon"], cfg["vae_feature_dim"], x_init=nz.get("x_init"),
                                                x_noise=nz.get("x_noise"), seed=seed, row_offset=row_offset, sampler=sampler,
                                                n_steps=n_steps, action_bounds=(lo, hi), action_mode=mode)]
-        rec = self._record(run)
-        res = self._guarded(run)
-        rec.seqs = self._seqs()
+        res, rec = self._call(run)
         return DeviceArray(res[0], record=rec), {}
 
     def get_action(self, batch, eval_rng, **kw):
@@ -260,39 +183,6 @@ class DPVAEAgent(LDPAgent):
             raise NotImplementedError("random_shift > 0 shifts the rgb keys as raw (B, T, H, W, C) images (agent/dp_repr_agent.py:135-144); "
                                       "a latent training batch holds none")
         return self._update_step(batch, None, rng, True, False, noise)
-
-    def _train_sync(self, name, state, shapes, eng=None):
-        """The engine's arenas must hold THIS state: parameters, Adam moments and the EMA (enabled with the agent's decay; a (re)load
-        re-seeds it from the parameters, then a distinct EMA tree is written over it)."""
-        eng = self._engine if eng is None else eng
-        if eng.train_token.get(name) == state.version and eng.train_ema_token.get(name) == state.ema_version:
-            return
-        W.check_params(state.params, shapes)
-        ema = None if state.ema_is_params else state.ema_params          # (read before the arenas are overwritten)
-        o = state.opt_state
-        eng.train_load(name, state.params, mu=None if o is None else o["mu"], nu=None if o is None else o["nu"], step=state.step,
-                       token=state.version)
-        decay = self.config["planner_ema_decay"]
-        if eng.ema_decay.get(name) != decay:
-            eng.train_ema(name, decay)
-        if ema is not None:
-            W.check_params(ema, shapes)
-            eng.train_write(name, eng.TRAIN_EMA, ema)
-        eng.train_ema_token[name] = state.ema_version
-
-    def _trained_state(self, name, old, shapes, eng=None):
-        eng = self._engine if eng is None else eng
-        token, etoken = next(_versions), next(_versions)
-        eng.train_token[name] = token
-        eng.train_ema_token[name] = etoken
-        which = {"params": eng.TRAIN_PARAMS, "mu": eng.TRAIN_MU, "nu": eng.TRAIN_NU, "ema": eng.TRAIN_EMA}
-
-        def fetch(what):
-            if eng.train_token.get(name) != token or (what == "ema" and eng.train_ema_token.get(name) != etoken):
-                raise RuntimeError(f"this {name} state was superseded by a later update(): its buffers were donated to the next step "
-                                   "(keep the agent that update() returned, as train_bc.py:107 does)")
-            return eng.train_read(name, which[what], shapes)
-        return DPState(None, None, old.step + 1, token, None, fetch, etoken, lambda: fetch("ema"))
 
     def _update_step(self, batch, mixed_batch, rng, use_planner, use_idm, noise, shard=None):
         """shard (dist.update_sharded): dict(group, rows=(lo, n)) -- `batch` holds rows [lo, lo + B) of a global batch of n: global-row
@@ -340,10 +230,7 @@ class DPVAEAgent(LDPAgent):
         new_state = self._trained_state("planner", st, self._planner_shapes())
         arrs = [DeviceArray(loss)] + [DeviceArray(x) for x in stats]
         m = dict(loss=_HostScalar(lambda: arrs[0].numpy()))
-        m["obs_min"], m["obs_max"], m["obs_mean"], m["obs_std"] = (_Elem(arrs[1], i) for i in range(4))
-        m["action_min"], m["action_max"] = _Elem(arrs[2], 0), _Elem(arrs[2], 1)
-        for j, k in enumerate(nb["obs"]):
-            m[f"{k}_min"], m[f"{k}_max"], m[f"{k}_mean"], m[f"{k}_std"] = (_Elem(arrs[3 + j], i) for i in range(4))
+        self._stat_metrics(m, "obs", arrs[1:], nb["obs"], n=4)
         m["planner_lr"], m["planner_step"] = np.float32(sched(st.step)), st.step       # the OLD state's step (:156-157)
         return self.replace(planner_state=new_state), m
 
@@ -372,13 +259,8 @@ class DPVAEAgent(LDPAgent):
             pred = eng.unet_forward(eng.add_noise(action, eps, t, npl), t, cond)
             out = [eng.mean_sq_diff(pred, eps), eng.reduce_stats(cond), eng.reduce_stats(action)]
             return out + [eng.reduce_stats(nb["obs"][k]) for k in nb["obs"]]
-        rec = self._record(run)
-        res = self._guarded(run)
-        rec.seqs = self._seqs()
+        res, rec = self._call(run)
         arrs = [DeviceArray(x, record=rec) for x in res]
         m = dict(loss=_HostScalar(lambda: arrs[0].numpy()))
-        m["obs_min"], m["obs_max"], m["obs_mean"], m["obs_std"] = (_Elem(arrs[1], i) for i in range(4))
-        m["action_min"], m["action_max"] = _Elem(arrs[2], 0), _Elem(arrs[2], 1)
-        for j, k in enumerate(batch["obs"].keys()):
-            m[f"{k}_min"], m[f"{k}_max"], m[f"{k}_mean"], m[f"{k}_std"] = (_Elem(arrs[3 + j], i) for i in range(4))
+        self._stat_metrics(m, "obs", arrs[1:], batch["obs"].keys(), n=4)
         return m

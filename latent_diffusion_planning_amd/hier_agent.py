@@ -128,28 +128,17 @@ class LDPHierAgent(LDPAgent):
         acknowledges each of them -- a fault on the IDM handle marks the call suspect like one on the planner handle."""
         return [self._engine, self._idm_engine]
 
-    # the IDM is a U-Net here: it lives in the second handle's planner slot
-    def _sync_weights(self, need_vae=False):
-        held = self._engine.loaded
-        up, ver = {}, {}
-        if self.use_planner and held["planner"] != self.planner_state.version:
-            if self._engine.train_token.get("planner") == self.planner_state.version:       # the state an update() left in the training arenas
-                self._engine.train_publish(["planner"], versions={"planner": self.planner_state.version})
-            else:
-                W.check_params(self.planner_state.params, W.planner_shapes(self._planner_spec))
-                up["planner"], ver["planner"] = self.planner_state.params, self.planner_state.version
-        if need_vae and held["vae"] != self._vae_version:
-            if self.vae_params is None:
-                raise ValueError("raw image observations need VAE weights (vae_pretrain_path / vae_params)")
-            up["vae"], ver["vae"] = self.vae_params, self._vae_version
-        if up:
-            self._engine.load_params(**up, versions=ver)
-        if self.use_idm and self._idm_engine.loaded["planner"] != self.idm_state.version:
-            if self._idm_engine.train_token.get("planner") == self.idm_state.version:
-                self._idm_engine.train_publish(["planner"], versions={"planner": self.idm_state.version})
-            else:
-                W.check_params(self.idm_state.params, W.planner_shapes(self._idm_unet_spec))
-                self._idm_engine.load_params(planner=self.idm_state.params, versions={"planner": self.idm_state.version})
+    # the IDM is a U-Net here: it lives, and trains, in the second handle's planner slot -- with that, `_sync_weights`, `update` /
+    # `update_mixed` (the gating is the same code, agent/ldp_hier_agent.py:223-232 / :274-283) and the step itself are LDPAgent's:
+    # plan_loss on every `idm_horizon`-th future state (:111-123), idm_loss of the action U-Net on chunks of `idm_horizon` actions per
+    # (state, state + idm_horizon) pair (:125-137), jax.grad + global_norm over both trees + one optax.adam step per network (:234-272)
+    def _idm_shapes(self):
+        return W.planner_shapes(self._idm_unet_spec)
+
+    def _nets(self):
+        ieng = self._idm_engine
+        return [n if n.key != "idm" else n._replace(eng=ieng, slot="planner", grad=lambda s, a, eps, t, w: ieng.train_planner_grad(a, eps, t, s, w))
+                for n in super()._nets()]
 
     # ---- agent/ldp_hier_agent.py:385-461 -----------------------------------------------------------
     def sample(self, batch, eval_rng, **kw):
@@ -186,9 +175,7 @@ class LDPHierAgent(LDPAgent):
             if obs_emb.shape[1] > oh:                                                                     # :399-400
                 out.append(self._engine.mean_sq_diff(nxt, obs_emb[:, oh:].contiguous()))
             return out
-        rec = self._record(lambda: run() + [None])
-        res = self._guarded(run)
-        rec.seqs = self._seqs()
+        res, rec = self._call(run, lambda: run() + [None])
         action, plan = DeviceArray(res[0], record=rec), DeviceArray(res[1], record=rec)
         metrics = {"plan": plan}
         if len(res) > 2:
@@ -221,9 +208,7 @@ class LDPHierAgent(LDPAgent):
             a = self._idm_engine.plan_sample(trans, x_init=nz.get("a_init"), step_noise=nz.get("a_noise"), seed=seed,
                                              row_offset=row_offset * (plan.shape[1] - 1), sampler=sampler, n_steps=n_steps)
             return [self._apply_norm(a.reshape(B, -1, a.shape[-1]), self.obs_normalization["actions"], False)]   # '(B H) T D -> B (H T) D'
-        rec = self._record(run)
-        res = self._guarded(run)
-        rec.seqs = self._seqs()
+        res, rec = self._call(run)
         return DeviceArray(res[0], record=rec)
 
     # ---- agent/ldp_hier_agent.py:324-343 `get_metrics`: LDPAgent's, forward only, with this agent's three readings of a training batch -----------
@@ -243,119 +228,6 @@ class LDPHierAgent(LDPAgent):
 
     def _idm_eps(self, s, noisy, t):
         return self._idm_engine.unet_forward(noisy, t, s)
-
-    # ---- agent/ldp_hier_agent.py:111-137, 223-322: the training step ------------------------------------------------
-    # `update` / `update_mixed` are LDPAgent's (the gating is the same code, :223-232 / :274-283); what differs is the step:
-    def _update_step(self, batch, mixed_batch, rng, use_planner, use_idm, noise, shard=None):
-        """plan_loss on every `idm_horizon`-th future state (:111-123), idm_loss of the action U-Net on chunks of `idm_horizon` actions per
-        (state, state + idm_horizon) pair (:125-137), jax.grad + global_norm + one optax.adam step per network (:234-272).  Both networks are
-        ConditionalUnet1Ds: each trains in its own engine handle's planner slot (csrc/train.hip's U-Net tape), the two tapes on two streams.
-        noise: optional dict(t_plan (B,), noise_plan (B, Tp, D), t_idm (B K,), noise_idm (B K, ih, A)) for parity runs."""
-        from .agent import _Elem, _HostScalar, _philox_normal
-        if not self._lr_schedules:
-            raise ValueError("update() needs the optimiser settings of LDPHierAgent.create (lr, end_lr, idm_lr, idm_end_lr, warmup_steps, decay_steps)")
-        cfg, eng, ieng = self.config, self._engine, self._idm_engine
-        seed = _seed_of(rng)
-        oh, ih = cfg["obs_horizon"], cfg["idm_horizon"]
-        nz = noise or {}
-        nb = self._postprocess(batch)
-        if "actions" not in nb:
-            raise KeyError("update needs batch['actions'] (utils/data_utils.py:73)")
-        obs_emb = self.get_obs_cond(nb["obs"]).contiguous()
-        action = nb["actions"]
-        emb_i, action_i = obs_emb, action
-        if mixed_batch is not None:                                                     # loss_mixed, :180-203
-            nbm = self._postprocess(mixed_batch)
-            emb_i, action_i = self.get_obs_cond(nbm["obs"]).contiguous(), nbm["actions"]
-        B, Bi = obs_emb.shape[0], emb_i.shape[0]
-        # shard (dist.update_sharded): this rank holds rows [lo, lo + B) of a global batch of n -- global-row timesteps and noise, B / n weighted
-        # losses, one all-reduce per handle's gradient arena (LDPAgent._update_step has the same contract)
-        lo_p, n_p = (0, B) if shard is None else shard["rows"]
-        lo_i, n_i = (0, Bi) if shard is None else (shard.get("mixed_rows", shard["rows"]) if mixed_batch is not None else shard["rows"])
-        w_p, w_i = np.float32(B) / np.float32(n_p), np.float32(Bi) / np.float32(n_i)
-
-        def rows_of(x, lo, n_loc, n_glob, per=1):
-            return x[lo * per:(lo + n_loc) * per] if len(x) == n_glob * per and n_glob != n_loc else x
-        hg = np.random.Generator(np.random.PCG64(seed & (2**63 - 1)))
-        zero = torch.zeros((), dtype=torch.float32, device=self._device)
-        plan_loss = idm_loss = zero
-        if use_planner:
-            self._train_sync("planner", self.planner_state, W.planner_shapes(self._planner_spec))
-        if use_idm:
-            self._train_sync("planner", self.idm_state, W.planner_shapes(self._idm_unet_spec), eng=ieng)
-        main = torch.cuda.current_stream(self._device)
-        side = eng.aux_streams() if eng.get_option("train_streams") else {}
-        idm_stream = side.get("idm") if (use_planner and use_idm) else None
-        stats_stream = side.get("stats")
-        if stats_stream is not None:
-            stats_stream.wait_stream(main)
-        with torch.cuda.stream(stats_stream if stats_stream is not None else main):
-            stats = [eng.reduce_stats(obs_emb), eng.reduce_stats(action)] + [eng.reduce_stats(nb["obs"][k]) for k in nb["obs"]]
-        t_plan = None
-        if use_planner:
-            t_plan = nz.get("t_plan")
-            t_plan = rows_of(np.asarray(hg.integers(0, int(cfg["planner_n_diffusion_steps"]), size=n_p) if t_plan is None else t_plan).reshape(-1), lo_p, B, n_p)
-        if use_idm:                                                                     # :125-137
-            s, a = self._idm_pairs(emb_i, action_i)
-            K = a.shape[0] // Bi                                                        # chunks per sample
-            t_idm = nz.get("t_idm")
-            t_idm = rows_of(np.asarray(hg.integers(0, int(cfg["idm_n_diffusion_steps"]), size=n_i * K) if t_idm is None else t_idm).reshape(-1), lo_i, Bi, n_i, K)
-            eps_i = nz.get("noise_idm")
-            eps_i = (self._t(rows_of(eps_i, lo_i, Bi, n_i, K)) if eps_i is not None
-                     else _philox_normal(seed, lo_i * K * a.shape[1] * a.shape[2], 0, 8, a.numel(), self._device).reshape(a.shape))
-            if idm_stream is not None:
-                idm_stream.wait_stream(main)
-            with torch.cuda.stream(idm_stream if idm_stream is not None else main):
-                idm_loss = ieng.train_planner_grad(a, eps_i, t_idm, s, float(np.float32(self.alpha_idm) * w_i))
-        if use_planner:                                                                 # :111-123
-            nxt = self._planner_targets(obs_emb)
-            eps = nz.get("noise_plan")
-            eps = (self._t(rows_of(eps, lo_p, B, n_p)) if eps is not None
-                   else _philox_normal(seed, lo_p * (nxt.numel() // B), 0, 7, nxt.numel(), self._device).reshape(nxt.shape))
-            cond = obs_emb[:, :oh].reshape(B, -1).contiguous()
-            plan_loss = eng.train_planner_grad(nxt, eps, t_plan, cond, float(np.float32(self.alpha_planner) * w_p))
-        for st in (idm_stream, stats_stream):
-            if st is not None:
-                main.wait_stream(st)
-        if shard is not None:
-            import torch.distributed as tdist
-            if use_planner:
-                tdist.all_reduce(eng.train_arena("planner", eng.TRAIN_GRADS), group=shard.get("group"))
-            if use_idm:
-                tdist.all_reduce(ieng.train_arena("planner", ieng.TRAIN_GRADS), group=shard.get("group"))
-            both = torch.stack([plan_loss.reshape(()), idm_loss.reshape(())])
-            tdist.all_reduce(both, group=shard.get("group"))
-            plan_loss, idm_loss = both[0], both[1]
-        rep = self.lr_schedule
-        new_p, new_i = self.planner_state, self.idm_state
-        m = {}
-        norms = []
-        if use_planner:
-            st = self.planner_state
-            eng.train_apply("planner", float(np.float32(self._lr_schedules["planner"](st.step))))
-            m["planner_lr"], m["planner_step"] = np.float32(rep(st.step)), st.step       # the OLD state's step, the LAST-built schedule (:254-255)
-            new_p = self._trained_state("planner", st, W.planner_shapes(self._planner_spec))
-            norms.append(eng.train_grad_norm(["planner"]))
-        else:
-            m.update(planner_lr=0, planner_step=0, noise_diff=0)
-        if use_idm:
-            st = self.idm_state
-            ieng.train_apply("planner", float(np.float32(self._lr_schedules["idm"](st.step))))
-            m["idm_lr"], m["idm_step"] = np.float32(rep(st.step)), st.step
-            new_i = self._trained_state("planner", st, W.planner_shapes(self._idm_unet_spec), eng=ieng)
-            norms.append(ieng.train_grad_norm(["planner"]))
-        else:
-            m.update(idm_lr=0, idm_step=0)
-        # linear_algebra.global_norm over BOTH gradient trees (:250): the two handles' norms combine as sqrt(a^2 + b^2)
-        g_norm = zero if not norms else norms[0] if len(norms) == 1 else torch.sqrt(norms[0].double() ** 2 + norms[1].double() ** 2).float()
-        arrs = [DeviceArray(x) for x in (plan_loss, idm_loss, g_norm)] + [DeviceArray(x) for x in stats]
-        m.update(plan_loss=_HostScalar(lambda: arrs[0].numpy()), idm_loss=_HostScalar(lambda: arrs[1].numpy()),
-                 loss=_HostScalar(lambda: arrs[0].numpy() + arrs[1].numpy()), g_norm=_HostScalar(lambda: arrs[2].numpy()))
-        m["emb_min"], m["emb_max"], m["emb_mean"], m["emb_std"] = (_Elem(arrs[3], i) for i in range(4))
-        m["action_min"], m["action_max"] = _Elem(arrs[4], 0), _Elem(arrs[4], 1)
-        for j, k in enumerate(nb["obs"]):
-            m[f"{k}_min"], m[f"{k}_max"] = _Elem(arrs[5 + j], 0), _Elem(arrs[5 + j], 1)
-        return self.replace(planner_state=new_p, idm_state=new_i), m
 
     # (the reference's hierarchical class has no sample_action_from_plan)
     def sample_action_from_plan(self, *a, **k):

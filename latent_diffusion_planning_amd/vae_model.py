@@ -26,9 +26,8 @@ import torch
 
 from . import _lib
 from . import weights as W
-from .agent import _Elem, _EngineCalls, _get, _norm_entry, _philox_normal, _seed_of, _versions
+from .agent import DPState, _Elem, _EngineCalls, _get, _norm_entry, _philox_normal, _seed_of
 from .arrays import DeviceArray
-from .dp_vae_agent import DPState
 from .engine import HipEngine
 
 IMAGE_SIZES = (64, 96, 128)               # what the 3x3 conv tiles of csrc/vae.hip are built for (latent side 2 / 3 / 4)
@@ -152,25 +151,25 @@ class StableVAEModel(_EngineCalls):
         """How many times this model (or a .replace copy) put a weight set into the engine."""
         return self._uploads[0]
 
+    _ema_decay = property(lambda self: self.ema_decay)
+
     def _sync_weights(self, use_ema: bool) -> None:
         """The engine's VAE slot must hold `params` (get_metrics) or `ema_params` (reconstruct, sample): each set has its own token."""
         st, eng = self.vae_state, self._engine
         want = st.ema_version if use_ema else st.version
         if eng.loaded["vae"] == want:
             return
-        tokens = getattr(eng, "train_token", {}), getattr(eng, "train_ema_token", {})
-        if not use_ema and tokens[0].get("vae") == st.version:          # a trained state: publish from the arena (no tree passes through Python)
-            eng.train_publish(["vae"], versions={"vae": want})
-            self._uploads[0] += 1
-            return
-        if use_ema and tokens[1].get("vae") == st.ema_version:
-            eng.train_publish_ema(["vae"], versions={"vae": want})
-            self._uploads[0] += 1
-            return
-        tree = st.ema_params if use_ema else st.params
-        W.check_params(tree, W.vae_shapes(self._vae_spec))
-        eng.load_params(vae=tree, versions={"vae": want})
+        tree = self._slot_weights(eng, "vae", st, self._shapes, use_ema)          # None: published from the training arena
+        if tree is not None:
+            eng.load_params(vae=tree, versions={"vae": want})
         self._uploads[0] += 1
+
+    def _shapes(self):
+        return W.vae_shapes(self._vae_spec)
+
+    def _train_sync(self, st: DPState) -> None:
+        """The shared hand-off for the model's one slot: the VAE arenas must hold THIS state (tests and tools warm the arenas through it)."""
+        super()._train_sync("vae", st, self._shapes())
 
     # ---- model/stable_vae_model.py:28 after postprocess_batch (utils/data_utils.py:70-80) ------------------------------------------
     def _frames(self, batch, keys) -> torch.Tensor:
@@ -201,9 +200,7 @@ class StableVAEModel(_EngineCalls):
             self._sync_weights(use_ema=False)
             img = self._frames(batch, self.config["rgb_obs"])
             return [self._engine.vae_metrics(img, use_kl, beta, seed=seed, noise=eps, row_offset=row_offset)[0]]
-        rec = self._record(run)
-        res = self._guarded(run)
-        rec.seqs = self._seqs()
+        res, rec = self._call(run)
         vec = DeviceArray(res[0], record=rec)
         return {k: _Elem(vec, i) for i, k in enumerate(_lib.VAE_METRIC_KEYS)}
 
@@ -218,9 +215,7 @@ class StableVAEModel(_EngineCalls):
             self._sync_weights(use_ema=True)
             img = self._frames(batch, [rgb_key])
             return [self._engine.vae_decode(self._engine.vae_encode(img))]
-        rec = self._record(run)
-        res = self._guarded(run)
-        rec.seqs = self._seqs()
+        res, rec = self._call(run)
         return DeviceArray(res[0], record=rec)
 
     # ---- model/stable_vae_model.py:103-123 -------------------------------------------------------------------------------------------
@@ -243,9 +238,7 @@ class StableVAEModel(_EngineCalls):
             z = z_in if z_in is not None else _philox_normal(seed, 0, 0, PHILOX_STREAM_VAE_SAMPLE, int(np.prod(shape)),
                                                              self._device).reshape(shape)
             return [self._engine.vae_decode(z)]
-        rec = self._record(run)
-        res = self._guarded(run)
-        rec.seqs = self._seqs()
+        res, rec = self._call(run)
         return DeviceArray(res[0], record=rec)
 
     # ---- model/stable_vae_model.py:57-73 ---------------------------------------------------------------------------------------------
@@ -270,6 +263,7 @@ class StableVAEModel(_EngineCalls):
         eps = None if noise is None else self._t(noise)
         st = self.vae_state
         lr = np.float32(self.lr_schedule(st.step))
+        shapes = self._shapes()
 
         def run():
             self._train_sync(st)
@@ -279,43 +273,9 @@ class StableVAEModel(_EngineCalls):
             return [out]
         # the tape runs on exact-fp32 kernels only (no range guard, no in-launch exchange): a later fault poll has nothing to recompute here,
         # and re-running the step would apply it twice
-        rec = self._record(lambda: [None])
-        res = self._guarded(run)
-        rec.seqs = self._seqs()
-        new_state = self._trained_state(st)
+        res, rec = self._call(run, lambda: [None])
+        new_state = self._trained_state("vae", st, shapes)
         vec = DeviceArray(res[0], record=rec)
         metrics = {k: _Elem(vec, i) for i, k in enumerate(_lib.VAE_METRIC_KEYS)}
         metrics["vae_lr"], metrics["vae_step"] = lr, st.step                  # the OLD state's count (:71-72)
         return self.replace(vae_state=new_state), metrics
-
-    def _train_sync(self, st: DPState) -> None:
-        """The engine's VAE arenas must hold THIS state: parameters, Adam moments (fresh after a restore, as train_vae.py:62-75) and the EMA."""
-        eng = self._engine
-        if eng.train_token.get("vae") == st.version and eng.train_ema_token.get("vae") == st.ema_version:
-            return
-        shapes = W.vae_shapes(self._vae_spec)
-        W.check_params(st.params, shapes)
-        ema = None if st.ema_is_params else st.ema_params                    # (read before the arenas are overwritten)
-        o = st.opt_state
-        eng.train_load("vae", st.params, mu=None if o is None else o["mu"], nu=None if o is None else o["nu"], step=st.step, token=st.version)
-        if eng.ema_decay.get("vae") != self.ema_decay:
-            eng.train_ema("vae", self.ema_decay)
-        if ema is not None:
-            W.check_params(ema, shapes)
-            eng.train_write("vae", eng.TRAIN_EMA, ema)
-        eng.train_ema_token["vae"] = st.ema_version
-
-    def _trained_state(self, old: DPState) -> DPState:
-        eng = self._engine
-        shapes = W.vae_shapes(self._vae_spec)
-        token, etoken = next(_versions), next(_versions)
-        eng.train_token["vae"] = token
-        eng.train_ema_token["vae"] = etoken
-        which = {"params": eng.TRAIN_PARAMS, "ema": eng.TRAIN_EMA}
-
-        def fetch(what):
-            if eng.train_token.get("vae") != token or (what == "ema" and eng.train_ema_token.get("vae") != etoken):
-                raise RuntimeError("this StableVAEModel state was superseded by a later update(): its buffers were donated to the next step "
-                                   "(keep the model that update() returned, as train_vae.py does)")
-            return eng.train_read("vae", which[what], shapes)
-        return DPState(None, None, old.step + 1, token, None, fetch, etoken, lambda: fetch("ema"))

@@ -12,6 +12,7 @@ from latent_diffusion_planning_amd.vae_model import StableVAEModel
 from tests import vae_model_oracle as VO
 from tests import vae_train_cases as VC
 from tests import vae_train_oracle as VT
+from tests.train_stub import TrainStub
 from tests.util import rng
 
 KEY, KEY2 = "agentview_image", "robot0_eye_in_hand_image"
@@ -56,46 +57,6 @@ def test_oracle_gradient_matches_central_differences_of_np64():
 
 
 # ---- 2. host logic of update on a stub engine ----------------------------------------------------------------------------------------
-class _TrainStub:
-    """The engine calls update makes, recorded; gradients are not computed here."""
-    TRAIN_PARAMS, TRAIN_GRADS, TRAIN_MU, TRAIN_NU, TRAIN_EMA = 0, 1, 2, 3, 4
-
-    def __init__(self):
-        self.loaded = {"planner": None, "idm": None, "vae": None}
-        self.call_seq, self.fault_upto, self.last_fault_kinds = 0, -1, 0
-        self.train_token, self.train_ema_token, self.ema_decay = {}, {}, {}
-        self.calls = []
-
-    def normalize_bounds(self, x, lo, hi, normalize):
-        return (x - lo[0]) / (hi[0] - lo[0]) * 2 - 1
-
-    def poll_fault_kinds(self):
-        return 0
-
-    def train_load(self, module, params, mu=None, nu=None, step=0, token=None):
-        self.calls.append(("load", module, step, mu is None))
-        self.train_token[module] = token
-
-    def train_ema(self, module, decay):
-        self.calls.append(("ema", module, decay))
-        self.ema_decay[module] = decay
-
-    def train_write(self, module, which, tree):
-        self.calls.append(("write", module, which))
-
-    def train_vae_grad(self, img, use_kl, beta, seed=0, noise=None, row_offset=0):
-        self.calls.append(("grad", tuple(img.shape), use_kl, beta, seed, row_offset))
-        self.frames = img
-        return torch.arange(11, dtype=torch.float32) + seed
-
-    def train_apply(self, module, lr, b1=0.9, b2=0.999, eps=1e-8):
-        self.calls.append(("apply", module, lr))
-
-    def train_read(self, module, which, shapes):
-        self.calls.append(("read", module, which))
-        return {k: np.full((1,), which, np.float32) for k in shapes}
-
-
 @pytest.fixture
 def stub_model(monkeypatch):
     from latent_diffusion_planning_amd import vae_model
@@ -105,7 +66,7 @@ def stub_model(monkeypatch):
         cfg = dict(rgb_obs=list(rgb_obs), name="stable_vae_model", use_kl=use_kl, beta=1e-5, n_downsample=6, data_name="rm_lift")
         sched = warmup_cosine_decay_schedule(1e-6, 1e-4, 1000, 300000, 1e-6)
         p = {"quant_conv/bias": np.zeros(8, np.float32)}
-        return StableVAEModel(DPState(p, None, ema_is_params=True), NORM, cfg, _TrainStub(), W.VAESpec(), image_size, "cpu",
+        return StableVAEModel(DPState(p, None, ema_is_params=True), NORM, cfg, TrainStub(), W.VAESpec(), image_size, "cpu",
                               lr_schedule=sched, ema_decay=0.99)
     return make
 
@@ -128,6 +89,15 @@ def test_update_returns_the_reference_metrics_and_advances_the_step(stub_model):
     assert kinds == ["load", "ema", "grad", "apply", "grad", "apply"]
     assert [c for c in m0._engine.calls if c[0] == "apply"] == [("apply", "vae", float(np.float32(sched(0)))),
                                                                 ("apply", "vae", float(np.float32(sched(1))))]
+
+
+def test_train_sync_of_the_state_warms_the_arenas_for_the_first_update(stub_model):
+    """`model._train_sync(model.vae_state)` is how the GPU suites and tools/vae_train_bench.py load the arenas before a first step."""
+    m = stub_model()
+    m._train_sync(m.vae_state)
+    assert [c[0] for c in m._engine.calls] == ["load", "ema"]
+    m.update({"obs": {KEY: _raw(1, 2)}}, 7, 0)
+    assert [c[0] for c in m._engine.calls] == ["load", "ema", "grad", "apply"]
 
 
 def test_update_concatenates_the_cameras_and_passes_use_kl(stub_model):
