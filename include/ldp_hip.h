@@ -103,7 +103,8 @@ LDP_API int ldp_create(const ldp_config* cfg, ldp_handle** out);
 LDP_API int ldp_destroy(ldp_handle* h);
 
 /* Upload one parameter leaf.  `path` = "<module>/<flax path>/<leaf>" with module in
- * {"planner","idm","vae"}, e.g. "planner/ConditionalResidualBlock1D_3/Conv1dBlock_0/Conv_0/kernel".
+ * {"planner","idm","vae","encoder0".."encoder3"}, e.g. "planner/ConditionalResidualBlock1D_3/Conv1dBlock_0/Conv_0/kernel"
+ * or "encoder0/ResNetBlock_2/conv_proj/kernel" (the ResNet image encoders of DPAgent, below).
  * `host` is a host float32 array in the Flax layout (Conv (k,Cin,Cout); Dense (in,out)).
  * replaces: planner_state.params / idm_state.params / vae_params pytrees
  * (agent/ldp_agent.py:575,614,551; train_bc.py:210-240 load_snapshot). */
@@ -112,7 +113,8 @@ LDP_API int ldp_set_weight(ldp_handle* h, const char* path, const float* host, c
 
 /* Pack weights into the MFMA streaming layout and build the timestep-only tables
  * (time-MLP output, per-block FiLM time parts, IDM cond parts, scheduler coefficients).
- * `modules` is a bitmask: 1 planner, 2 idm, 4 vae.  Synchronises `stream`. */
+ * `modules` is a bitmask: 1 planner, 2 idm, 4 vae, 8 the ResNet encoders (every slot encoder<i> that has leaves: its tree is
+ * checked -- the first missing or mis-shaped leaf is named -- and its kernels are packed).  Synchronises `stream`. */
 LDP_API int ldp_finalize(ldp_handle* h, int32_t modules, void* stream);
 
 /* -- planner ------------------------------------------------------------------------------
@@ -228,6 +230,40 @@ LDP_API int ldp_vae_posterior(ldp_handle* h, const float* moments, const float* 
  * Needs encoder and decoder weights; behind the fault check and the fp16-plane range guard like the two calls above. */
 LDP_API int ldp_vae_metrics(ldp_handle* h, const float* img_nhwc, int32_t N, int32_t use_kl, float beta, const float* eps,
                     uint64_t seed, int64_t row_offset, float* metrics_out, float* z_out, float* rec_out, void* stream);
+
+/* -- ResNet-18 image encoder of the diffusion-policy baseline (agent/dp_agent.py) -----------------
+ * ResNetEncoder.apply (networks/resnet_v1.py:237-346, agent/encoder/bridge_resnet.yaml):
+ * img (N, 64, 64, 3) NHWC in [-1, 1] -> feat_out (N, 1024) = [expected_x (512) | expected_y (512)]
+ * conv_init 7x7 stride 2 -> GroupNorm(4, eps 1e-5) + ReLU -> max-pool 3x3 stride 2 (SAME, -inf padding) -> eight ResNetBlocks
+ * (64 / 128 / 256 / 512 channels at 16 / 8 / 4 / 2 pixels; the first block of stages 1..3 has stride 2 and the conv_proj / norm_proj
+ * residual) -> SpatialSoftmax (temperature 1).  No bias anywhere; every product is exact fp32 (fp32 MFMA).
+ * `slot` 0..3 selects the weight module "encoder<slot>" (ldp_set_weight + ldp_finalize(h, 8)): one handle serves up to four cameras.
+ * Works in chunks of 64 frames (the handle owns the ping-pong buffers: 44 MB), enqueues 39 launches per chunk on `stream` and does not
+ * synchronise.  No atomics: two runs give the same bits, and a frame's features do not depend on N or on the frame's place in the call.
+ * LDP_ESTATE before ldp_finalize(h, 8) of that slot; LDP_EINVAL for a bad slot or N <= 0. */
+LDP_API int ldp_resnet_encode(ldp_handle* h, int32_t slot, const float* img_nhwc, float* feat_out,
+                              int32_t N, void* stream);
+
+/* Unit-testable primitives of the encoder (no handle): host weights in Flax layout, device tensors NHWC; each synchronises `stream`.
+ * conv7x7_s2: conv_init -- 7x7, stride 2, padding (3, 3), cross-correlation; kernel (7, 7, Cin, Cout).  Built for H = W = 64, Cin = 3,
+ *             Cout = 64 (LDP_EINVAL otherwise): x (N, 64, 64, 3) -> y (N, 32, 32, 64).
+ * conv1x1_s2: conv_proj -- y(n, i, j, :) = x(n, 2i, 2j, :) @ kernel (1, 1, Cin, Cout); even H, W; Cin % 4 == 0, Cin <= 512, Cout % 64 == 0.
+ * maxpool3x3_s2: nn.max_pool(x, (3, 3), (2, 2), 'SAME') on even H, W (padding (0, 1), -inf); C % 4 == 0.
+ * gn: y = [relu]( GroupNorm(x) [+ res | + GroupNorm'(res)] ) on (N, HW, C): `groups` groups of C / groups channels (a multiple of 4),
+ *     statistics per sample over (HW, C / groups), two passes (centred variance); res (device, same shape) or NULL; scale2 / bias2 (host,
+ *     both or neither): `res` is then the RAW projection output and is normalised with its own statistics first (the fused norm_proj).
+ *     y may alias x.
+ * spatial_softmax: x (N, H, W, C) -> out (N, 2 C) = [sum_p pos_x(p) softmax_p(x) | sum_p pos_y(p) softmax_p(x)], pos_x = linspace(-1, 1, W)
+ *     by column, pos_y = linspace(-1, 1, H) by row. */
+LDP_API int ldp_resnet_conv7x7_s2_f32(const float* x, const float* kernel_host, float* y, int32_t N, int32_t H, int32_t W, int32_t Cin,
+                                      int32_t Cout, void* stream);
+LDP_API int ldp_resnet_conv1x1_s2_f32(const float* x, const float* kernel_host, float* y, int32_t N, int32_t H, int32_t W, int32_t Cin,
+                                      int32_t Cout, void* stream);
+LDP_API int ldp_resnet_maxpool3x3_s2_f32(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
+LDP_API int ldp_resnet_gn_f32(const float* x, const float* res, float* y, const float* scale_host, const float* bias_host,
+                              const float* scale2_host, const float* bias2_host, int32_t N, int32_t HW, int32_t C, int32_t groups,
+                              float eps, int32_t relu, void* stream);
+LDP_API int ldp_resnet_spatial_softmax_f32(const float* x, float* out, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
 
 /* -- elementwise pre/post-processing (utils/data_utils.py:9-16,61-65) ----------------------
  * y = (x - lo) / (hi - lo) * 2 - 1            (normalize != 0)

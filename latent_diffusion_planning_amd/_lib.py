@@ -18,7 +18,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ldp_hip.h")
 
 LDP_MAX_LEVELS = 4
 SAMPLER_DDPM, SAMPLER_DDIM = 0, 1
-MOD_PLANNER, MOD_IDM, MOD_VAE = 1, 2, 4
+MOD_PLANNER, MOD_IDM, MOD_VAE, MOD_ENCODER = 1, 2, 4, 8
+RESNET_SLOTS, RESNET_FEATURES = 4, 1024       # encoder0 .. encoder3 of a handle; [expected_x (512) | expected_y (512)] per frame
+RESNET_CHUNK = 64                             # frames per pass of ldp_resnet_encode (csrc/resnet.hip RN_CHUNK)
 PHILOX_STREAM_VAE_EPS = 9          # LDP_PHILOX_STREAM_VAE_EPS: eps of the StableVAE posterior draw
 # LDP_VAE_METRIC_*: the keys of StableVAEModel.loss (model/stable_vae_model.py:42-53) in the order ldp_vae_metrics writes them
 VAE_METRIC_KEYS = ("img_min", "img_max", "img_mean", "img_std", "loss", "loss_mse", "loss_kl", "z_min", "z_max", "z_mean", "z_std")
@@ -76,6 +78,13 @@ SIGNATURES: Dict[str, tuple] = {
     "ldp_vae_moments": (C.c_int, [_H, _FP, _FP, C.c_int32, C.c_void_p]),
     "ldp_vae_posterior": (C.c_int, [_H, _FP, _FP, C.c_uint64, C.c_int64, _FP, _FP, _FP, _FP, C.c_int32, C.c_void_p]),
     "ldp_vae_metrics": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_float, _FP, C.c_uint64, C.c_int64, _FP, _FP, _FP, C.c_void_p]),
+    "ldp_resnet_encode": (C.c_int, [_H, C.c_int32, _FP, _FP, C.c_int32, C.c_void_p]),
+    "ldp_resnet_conv7x7_s2_f32": (C.c_int, [_FP, C.c_void_p, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ldp_resnet_conv1x1_s2_f32": (C.c_int, [_FP, C.c_void_p, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ldp_resnet_maxpool3x3_s2_f32": (C.c_int, [_FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ldp_resnet_gn_f32": (C.c_int, [_FP, _FP, _FP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_float, C.c_int32, C.c_void_p]),
+    "ldp_resnet_spatial_softmax_f32": (C.c_int, [_FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ldp_conv2d_3x3_f32": (C.c_int, [_FP, C.c_void_p, C.c_void_p, _FP, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ldp_conv2d_3x3_bf16x3": (C.c_int, [_FP, C.c_void_p, C.c_void_p, _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32,

@@ -137,6 +137,27 @@ def param_trees(raw_restored: dict, keys: Optional[Iterable[str]] = None) -> Dic
     return out
 
 
+def _restored_encoders(agent, flat) -> dict:
+    """train_bc.py:216-229 on a DPAgent: `encoder_params` holds one tree per encoder under `<camera key>_params` (`shared_params` for a
+    shared encoder); the '_params' suffix is stripped and each tree replaces that encoder's params AND ema_params."""
+    trees: Dict[str, OrderedDict] = OrderedDict()
+    for path, arr in flat.items():
+        head, _, rest = path.partition("/")
+        trees.setdefault(head, OrderedDict())[rest] = arr
+    esd = agent.encoder_state_dict
+    if bool(agent.config.get("shared_encoder")):
+        if "shared_params" not in trees:
+            raise CheckpointError(f"the agent has a shared encoder but encoder_params holds {sorted(trees)} (no shared_params)")
+        return {"shared": esd["shared"].replace(params=trees["shared_params"], ema_params=trees["shared_params"])}
+    out = {}
+    for name, tree in trees.items():
+        key = name.replace("_params", "")
+        if key not in esd:
+            raise CheckpointError(f"encoder_params holds {name} but the agent's encoders are {sorted(esd)}")
+        out[key] = esd[key].replace(params=tree, ema_params=tree)
+    return out
+
+
 def load_snapshot(agent, path: str, restore_keys: Iterable[str] = ()):
     """train_bc.py:210-240 on this agent: every restored `<prefix>_params` replaces `<prefix>_state`'s params and
     ema_params (`vae_params` replaces the agent's VAE tree); returns the new agent (flax-style, the old one is untouched)."""
@@ -158,6 +179,9 @@ def load_snapshot(agent, path: str, restore_keys: Iterable[str] = ()):
             continue
         state_name = f"{prefix}_state"
         state = getattr(agent, state_name, None)
+        if prefix == "encoder" and getattr(agent, "encoder_state_dict", None) is not None:
+            fields["encoder_state_dict"] = _restored_encoders(agent, flat)
+            continue
         if state is None:
             if prefix == "encoder":          # LDP agents have no learned encoder state (train_bc.py:216-229 is the BC agents')
                 continue
@@ -186,7 +210,11 @@ def save(path: str, tree: dict) -> str:
     """Write `tree` as `<path>/checkpoint`.  Values may be nested dicts or this package's flat `{"a/b/kernel": array}`
     parameter trees (nested first, so the file holds what `agent.get_params()` holds in the reference)."""
     msgpack = _msgpack()
-    nested = {k: (W.unflatten(v) if isinstance(v, dict) and any("/" in str(q) for q in v) else v) for k, v in tree.items()}
+    def nest(v):                             # flat trees at any depth (DPAgent's encoder_params: {"<key>_params": flat tree})
+        if not isinstance(v, dict):
+            return v
+        return W.unflatten(v) if any("/" in str(q) for q in v) else {q: nest(x) for q, x in v.items()}
+    nested = {k: nest(v) for k, v in tree.items()}
     os.makedirs(path, exist_ok=True)
     f = os.path.join(path, "checkpoint")
     with open(f, "wb") as fh:

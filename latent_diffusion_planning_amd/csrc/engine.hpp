@@ -214,6 +214,7 @@ struct ldp_handle {
   int64_t stat_train_gemm[17] = {};
   void* vae = nullptr;                   // VaeState (vae.hip)
   void* train = nullptr;                 // Trainer (train.hip): master parameters, gradients, Adam moments, launch tables; created by ldp_train_init
+  void* resnet = nullptr;                // RnState (resnet.hip): the ResNet-18 image encoders of DPAgent (weight modules encoder0 .. encoder3)
 };
 
 namespace ldp {
@@ -265,6 +266,9 @@ int planner_forward_launch(ldp_handle* h, int B, const int* k_dev, int k, bool s
 int idm_finalize(ldp_handle* h, hipStream_t s);
 int vae_finalize(ldp_handle* h, hipStream_t s);
 void vae_destroy(ldp_handle* h);
+int resnet_finalize(ldp_handle* h, hipStream_t s);         // resnet.hip: every encoder slot that has leaves
+void resnet_invalidate(ldp_handle* h, int slot);
+void resnet_destroy(ldp_handle* h);
 void train_destroy(ldp_handle* h);
 void betas_squaredcos(int n, std::vector<float>& betas, std::vector<float>& alphas, std::vector<float>& acp);
 }  // namespace ldp

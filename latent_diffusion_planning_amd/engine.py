@@ -13,7 +13,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (LDPHipError, LDPHipFault, LdpConfig, MOD_IDM, MOD_PLANNER, MOD_VAE, SAMPLER_DDIM, SAMPLER_DDPM, check)
+from ._lib import (LDPHipError, LDPHipFault, LdpConfig, MOD_ENCODER, MOD_IDM, MOD_PLANNER, MOD_VAE, RESNET_FEATURES, RESNET_SLOTS,
+                   SAMPLER_DDIM, SAMPLER_DDPM, check)
 
 _SAMPLERS = {"ddpm": SAMPLER_DDPM, "ddim": SAMPLER_DDIM}
 
@@ -67,6 +68,8 @@ class HipEngine:
         # version token of the parameter tree last uploaded per module (LDPAgent compares it with its
         # ParamState.version: agents sharing one engine can never run on each other's weights)
         self.loaded = {"planner": None, "idm": None, "vae": None}
+        self.loaded.update({f"encoder{i}": None for i in range(RESNET_SLOTS)})      # the ResNet image encoders of DPAgent
+        self.encoder_uploads = [0] * RESNET_SLOTS     # load_encoder calls per slot (tests: an unchanged encoder is not uploaded again)
         # likewise for the training arenas (ldp_train_*): the token of the ParamState they currently represent
         self.train_token = {"planner": None, "idm": None}
         # and of the EMA arenas (ldp_train_ema): the token of the EMA tree they hold
@@ -119,6 +122,33 @@ class HipEngine:
         for name, tree in (("planner", planner), ("idm", idm), ("vae", vae)):
             if tree is not None:
                 self.loaded[name] = (versions or {}).get(name, object())
+
+    # -- ResNet image encoders (csrc/resnet.hip) ---------------------------------------------------
+    def load_encoder(self, slot: int, params: Dict[str, np.ndarray], version=None) -> None:
+        """Upload one ResNetEncoder tree (weights.resnet_shapes) into weight module encoder<slot> and pack it.  Only the slots given since
+        the last finalize are re-packed on the device side; `version` is recorded in self.loaded["encoder<slot>"]."""
+        if not 0 <= int(slot) < RESNET_SLOTS:
+            raise ValueError(f"encoder slot {slot}: a handle has slots 0..{RESNET_SLOTS - 1}")
+        name = f"encoder{int(slot)}"
+        for path, arr in params.items():
+            a = np.ascontiguousarray(np.asarray(arr), dtype=np.float32)
+            shape = (C.c_int64 * a.ndim)(*a.shape)
+            check(self.lib.ldp_set_weight(self._h, f"{name}/{path}".encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim))
+        self.loaded[name] = None
+        with torch.cuda.device(self.device):
+            check(self.lib.ldp_finalize(self._h, MOD_ENCODER, self._stream()))
+        self.loaded[name] = version if version is not None else object()
+        self.encoder_uploads[int(slot)] += 1
+
+    def resnet_encode(self, slot: int, img_nhwc: torch.Tensor) -> torch.Tensor:
+        """ResNetEncoder.apply of encoder<slot>: (N, 64, 64, 3) NHWC frames in [-1, 1] -> (N, 1024) = [expected_x | expected_y]."""
+        img = _f32(img_nhwc, self.device)
+        n = img.shape[0]
+        _want("img_nhwc", img, (n, 64, 64, 3))
+        out = torch.empty((n, RESNET_FEATURES), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_resnet_encode(self._h, int(slot), _ptr(img), _ptr(out), n, self._stream()))
+        self.call_seq += 1
+        return out
 
     # -- options / fault protocol (include/ldp_hip.h) -----------------------------------------------
     def set_option(self, name: str, value: int) -> None:
@@ -661,6 +691,77 @@ def conv2d_3x3_split(x: torch.Tensor, kernel, bias, res: Optional[torch.Tensor] 
                                     _ptr(st) if st is not None else None, n, h, w, cin, cout, 2 if dual == 2 else 1 if dual else 0,
                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return (y, st) if with_stats else y
+
+
+# ---- primitives of the ResNet image encoder (csrc/resnet.hip) ----
+def _cur():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def resnet_conv7x7_s2(x: torch.Tensor, kernel) -> torch.Tensor:
+    """conv_init: 7x7, stride 2, padding (3, 3); x (N, 64, 64, 3), kernel (7, 7, 3, 64) -> (N, 32, 32, 64)."""
+    x = x.contiguous().float()
+    n, h, w, cin = x.shape
+    k, kp = _host(kernel)
+    if k.shape[:3] != (7, 7, cin):
+        raise ValueError(f"kernel {k.shape} does not match x {tuple(x.shape)}")
+    y = torch.empty((n, h // 2, w // 2, k.shape[3]), device=x.device, dtype=torch.float32)
+    check(_lib.load().ldp_resnet_conv7x7_s2_f32(_ptr(x), kp, _ptr(y), n, h, w, cin, k.shape[3], _cur()))
+    return y
+
+
+def resnet_conv1x1_s2(x: torch.Tensor, kernel) -> torch.Tensor:
+    """conv_proj: 1x1, stride 2; x (N, H, W, Cin), kernel (1, 1, Cin, Cout) -> (N, H / 2, W / 2, Cout)."""
+    x = x.contiguous().float()
+    n, h, w, cin = x.shape
+    k, kp = _host(kernel)
+    if k.shape[:3] != (1, 1, cin):
+        raise ValueError(f"kernel {k.shape} does not match x {tuple(x.shape)}")
+    y = torch.empty((n, h // 2, w // 2, k.shape[3]), device=x.device, dtype=torch.float32)
+    check(_lib.load().ldp_resnet_conv1x1_s2_f32(_ptr(x), kp, _ptr(y), n, h, w, cin, k.shape[3], _cur()))
+    return y
+
+
+def resnet_maxpool3x3_s2(x: torch.Tensor) -> torch.Tensor:
+    x = x.contiguous().float()
+    n, h, w, c = x.shape
+    y = torch.empty((n, h // 2, w // 2, c), device=x.device, dtype=torch.float32)
+    check(_lib.load().ldp_resnet_maxpool3x3_s2_f32(_ptr(x), _ptr(y), n, h, w, c, _cur()))
+    return y
+
+
+def resnet_gn(x: torch.Tensor, scale, bias, groups: int = 4, eps: float = 1e-5, relu: bool = False, res: Optional[torch.Tensor] = None,
+              scale2=None, bias2=None) -> torch.Tensor:
+    """y = [relu](GN(x) [+ res | + GN'(res)]) on (N, ..., C); scale2 / bias2: `res` is normalised with its own statistics first."""
+    x = x.contiguous().float()
+    n, c = x.shape[0], x.shape[-1]
+    hw = x.numel() // (n * c)
+    s, sp = _host(scale)
+    b, bp = _host(bias)
+    if s.shape != (c,) or b.shape != (c,):
+        raise ValueError(f"scale / bias must have shape ({c},)")
+    s2p = b2p = None
+    if scale2 is not None:
+        s2, s2p = _host(scale2)
+        b2, b2p = _host(bias2)
+        if s2.shape != (c,) or b2.shape != (c,):
+            raise ValueError(f"scale2 / bias2 must have shape ({c},)")
+    r = None
+    if res is not None:
+        r = res.contiguous().float()
+        _want("res", r, x.shape)
+    y = torch.empty_like(x)
+    check(_lib.load().ldp_resnet_gn_f32(_ptr(x), _ptr(r), _ptr(y), sp, bp, s2p, b2p, n, hw, c, int(groups), C.c_float(float(eps)),
+                                       int(bool(relu)), _cur()))
+    return y
+
+
+def resnet_spatial_softmax(x: torch.Tensor) -> torch.Tensor:
+    x = x.contiguous().float()
+    n, h, w, c = x.shape
+    out = torch.empty((n, 2 * c), device=x.device, dtype=torch.float32)
+    check(_lib.load().ldp_resnet_spatial_softmax_f32(_ptr(x), _ptr(out), n, h, w, c, _cur()))
+    return out
 
 
 def downsample1d(x: torch.Tensor, kernel, bias) -> torch.Tensor:

@@ -1,4 +1,4 @@
-"""Parameter trees of the LDP denoising hot path (planner U-Net, IDM MLP, StableVAE).
+"""Parameter trees of the LDP denoising hot path (planner U-Net, IDM MLP, StableVAE, ResNet image encoder).
 
 Host-side logic only (numpy): names, shapes and the synthetic initialiser used by
 `LDPAgent.create`, `bench.py` and the tests.  Every tree is a *flat* dict
@@ -92,9 +92,56 @@ class VAESpec:
     norm_num_groups: int = 32
 
 
+@dataclass(frozen=True)
+class ResNetSpec:
+    """ResNetEncoder configuration (agent/encoder/bridge_resnet.yaml): the values that change the arithmetic."""
+    stage_sizes: Tuple[int, ...] = (2, 2, 2, 2)
+    n_filters: int = 64
+    image_size: int = 64
+    groups: int = 4                     # MyGroupNorm(num_groups=4, epsilon=1e-5), networks/resnet_v1.py:258
+    eps: float = 1e-5
+
+    def blocks(self) -> List[Tuple[int, int, int, bool]]:
+        """(Cin, Cout, stride, projected residual) of ResNetBlock_0..N (networks/resnet_v1.py:273-283, 173-177)."""
+        out, cin = [], self.n_filters
+        for i, n in enumerate(self.stage_sizes):
+            for j in range(n):
+                cout, stride = self.n_filters * 2 ** i, 2 if i > 0 and j == 0 else 1
+                out.append((cin, cout, stride, stride != 1 or cin != cout))
+                cin = cout
+        return out
+
+    @property
+    def feature_dim(self) -> int:
+        """SpatialSoftmax output: [expected_x | expected_y] over the last stage's channels."""
+        return 2 * self.n_filters * 2 ** (len(self.stage_sizes) - 1)
+
+
 # --------------------------------------------------------------------------------------
 # shape tables
 # --------------------------------------------------------------------------------------
+def resnet_shapes(spec: ResNetSpec = ResNetSpec()) -> "OrderedDict[str, Tuple[int, ...]]":
+    """ResNetEncoder's tree (networks/resnet_v1.py:237-346): no bias on any conv, scale / bias on every norm."""
+    s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    f = spec.n_filters
+    s["conv_init/kernel"] = (7, 7, 3, f)
+    s["norm_init/scale"] = (f,)
+    s["norm_init/bias"] = (f,)
+    for i, (cin, cout, _, proj) in enumerate(spec.blocks()):
+        p = f"ResNetBlock_{i}"
+        s[f"{p}/Conv_0/kernel"] = (3, 3, cin, cout)
+        s[f"{p}/MyGroupNorm_0/scale"] = (cout,)
+        s[f"{p}/MyGroupNorm_0/bias"] = (cout,)
+        s[f"{p}/Conv_1/kernel"] = (3, 3, cout, cout)
+        s[f"{p}/MyGroupNorm_1/scale"] = (cout,)
+        s[f"{p}/MyGroupNorm_1/bias"] = (cout,)
+        if proj:
+            s[f"{p}/conv_proj/kernel"] = (1, 1, cin, cout)
+            s[f"{p}/norm_proj/scale"] = (cout,)
+            s[f"{p}/norm_proj/bias"] = (cout,)
+    return s
+
+
 def planner_shapes(spec: PlannerSpec) -> "OrderedDict[str, Tuple[int, ...]]":
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
     e = spec.diffusion_step_embed_dim
@@ -293,6 +340,35 @@ def init_idm_params(spec: IDMSpec, seed: int = 1, perturb: bool = True) -> Param
 def init_vae_params(spec: VAESpec = VAESpec(), seed: int = 2, perturb: bool = True,
                     decoder: bool = True) -> Params:
     return init_from_shapes(vae_shapes(spec, decoder), seed, perturb)
+
+
+def init_resnet_params(spec: ResNetSpec = ResNetSpec(), seed: int = 3, perturb: bool = True) -> Params:
+    """kaiming_normal conv kernels (normal, variance 2 / fan_in; networks/resnet_v1.py:253), scale 1 / bias 0 norms; `perturb` as above."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    out: Params = OrderedDict()
+    for path, shape in resnet_shapes(spec).items():
+        leaf = path.rsplit("/", 1)[1]
+        if leaf == "kernel":
+            w = rng.standard_normal(size=shape) * np.sqrt(2.0 / _fans(shape)[0])
+        elif leaf == "scale":
+            w = np.ones(shape) + (0.1 * rng.standard_normal(size=shape) if perturb else 0.0)
+        else:
+            w = 0.02 * rng.standard_normal(size=shape) if perturb else np.zeros(shape)
+        out[path] = np.ascontiguousarray(w, dtype=np.float32)
+    return out
+
+
+def check_resnet_params(params: Params, spec: ResNetSpec = ResNetSpec()) -> None:
+    """Raise naming the FIRST missing or mis-shaped leaf of a ResNetEncoder tree (in construction order), or the first leaf it does not have."""
+    shapes = resnet_shapes(spec)
+    for k, shp in shapes.items():
+        if k not in params:
+            raise KeyError(f"encoder parameter tree: leaf '{k}' {tuple(shp)} is missing")
+        if tuple(np.shape(params[k])) != tuple(shp):
+            raise ValueError(f"encoder parameter tree: leaf '{k}' has shape {tuple(np.shape(params[k]))}, expected {tuple(shp)}")
+    for k in params:
+        if k not in shapes:
+            raise KeyError(f"encoder parameter tree: unexpected leaf '{k}'")
 
 
 def check_params(params: Params, shapes) -> None:
