@@ -220,6 +220,26 @@ __host__ __device__ constexpr int valid_pairs(int mode, int to_n) {
   return n;
 }
 
+// Exact-fp32 k = 5 convs over TWO positions (the lowest U-Net level): with zero padding the conv is the 2 x 2 Toeplitz product
+//   out0 = W2 x0 + W3 x1,   out1 = W1 x0 + W2 x1        (four products per k-step: valid_pairs(MODE_K5, 2))
+// which is computed from THREE products with a shared one,
+//   S = W2 (x0 + x1),   out0 = S + (W3 - W2) x1,   out1 = S + (W1 - W2) x0.
+// The differences depend on the weights alone: pack_conv_t2 (t2pack.hpp) stores [W2, fl(W3 - W2), fl(W1 - W2)] (+ the projection) per chunk
+// where the five taps stood; x0 + x1 is one VALU add per activation fragment element.  The form belongs to (mode, TO, SPLIT) -- every tile of
+// it reads the one packed buffer of its layer -- and is rounded differently from the four-product form, within fp32 round-off.
+// LDP_T2_DIRECT (A/B build only, `make t2direct`): the four-product loop on the five-tap packing.
+#ifndef LDP_T2_DIRECT
+#define LDP_T2_DIRECT 0
+#endif
+__host__ __device__ constexpr bool t2_shared(int mode, int to_n, int split) {
+  return !LDP_T2_DIRECT && mode == MODE_K5 && to_n == 2 && split == 0;
+}
+constexpr int T2_SLOTS = 3;      // weight fragments per chunk of the shared form: W2, W3 - W2, W1 - W2
+// matrix instructions per k-step per wave and row block (without the projection)
+__host__ __device__ constexpr int conv_products(int mode, int to_n, int split) {
+  return t2_shared(mode, to_n, split) ? T2_SLOTS : valid_pairs(mode, to_n);
+}
+
 // 16-byte-slot swizzle of a 16x16 f32 sub-tile: slot' = slot ^ H(row >> 2), H = {0,3,2,1}
 __device__ __forceinline__ int swz(int row, int slot) { return slot ^ ((4 - (row >> 2)) & 3); }
 
@@ -501,8 +521,20 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
   if LDP_ABL(64) return;
   LDP_TL(0);
 
+  constexpr bool T2S = t2_shared(MODE, TO, SPLIT);
   f32x4 acc[MB][TO];
   f32x4 racc[MB][RES_OUT ? TO : 1];
+  f32x4 sacc[T2S ? MB : 1];      // shared form: S = W2 (x0 + x1); acc[.][0] / acc[.][1] collect (W3 - W2) x1 / (W1 - W2) x0 until the loop ends
+  // One K slice per work-group (the whole-group tiles): a wave's accumulators would each take the layer's whole K range as ONE sequential
+  // fp32 chain -- twice the chain of the two-slice tiles -- and out = S + D adds the round-off of two such chains (three where the W2 terms
+  // cancel).  The odd sub-chunks of an iteration go to a second accumulator set, added behind the loop: the chain length of the KS = 2 tiles,
+  // the same matrix instructions.
+  constexpr bool T2S2 = T2S && KS == 1 && CPI % 2 == 0;
+  f32x4 sacc_b[T2S2 ? MB : 1], acc_b[T2S2 ? MB : 1][2];
+#pragma unroll
+  for (int m = 0; m < (T2S ? MB : 1); ++m) sacc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int m = 0; m < (T2S2 ? MB : 1); ++m) sacc_b[m] = acc_b[m][0] = acc_b[m][1] = f32x4{0.f, 0.f, 0.f, 0.f};
   f32x4 acc_lo[C::F16 ? MB : 1][C::F16 ? TO : 1], racc_lo[C::F16 ? MB : 1][C::F16 && RES_OUT ? TO : 1];    // fp16 planes: the h l' + l' h products (x 2^11)
 #pragma unroll
   for (int m = 0; m < (C::F16 ? MB : 1); ++m) {
@@ -625,7 +657,8 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
   // The projection's fragments live in the conv's own buffer, right behind the taps of their chunk: a
   // second weight stream from a separate allocation cost 20-25 % of the loop time of these layers.
   constexpr bool SKIPZ = MODE == MODE_K5 && RES_OUT && SPLIT == 0 && TO >= 8 && KS > 1;
-  constexpr int NJW = NJ + (RES_OUT ? 1 : 0);
+  constexpr int NJW = (T2S ? T2_SLOTS : NJ) + (RES_OUT ? 1 : 0);      // fragments per chunk in the packed buffer
+  constexpr int NJR = T2S ? T2_SLOTS : NJ;                            // slot of the projection
   // 16-row split tiles: an iteration is NSTEP 32-channel steps; a register buffer holds ONE step and the two buffers roll step by
   // step (the LDS stage + barrier of an iteration then amortises over NSTEP steps without more weight registers)
   constexpr int NSTEP = S16 ? CPI / 2 : 1;
@@ -651,7 +684,8 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
           }
         } else
         if (tap_used(MODE, TO, j)) {
-          const size_t off = (((size_t)gc * NJW + j) * nblk_total + nblk) * 256 + lane * 4;
+          // shared form: slots 0, 1, 2 = W2, W3 - W2, W1 - W2 travel in the register rows of taps 1, 2, 3
+          const size_t off = (((size_t)gc * NJW + (T2S ? j - 1 : j)) * nblk_total + nblk) * 256 + lane * 4;
           // LDP_W_NT (A/B build only, round 4): non-temporal weight loads in the small-batch (KWS) instantiations, where one
           // CU reads its weight slice once per launch (MI355X_MICROARCH.md row nt-weights); measured, see DESIGN 4.1
           b[j][ci] = (LDP_W_NT && KWS) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.w + off))
@@ -666,7 +700,7 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
         }
       } else
       if (RES_OUT) {
-        const size_t off = (((size_t)gc * NJW + NJ) * nblk_total + nblk) * 256 + lane * 4;
+        const size_t off = (((size_t)gc * NJW + NJR) * nblk_total + nblk) * 256 + lane * 4;
         rb[ci] = (LDP_W_NT && KWS) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.w + off))
                                    : *reinterpret_cast<const f32x4*>(a.w + off);
       }
@@ -905,6 +939,44 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
     // 32 stored channels, so the K-slice waves behind them would multiply exact zeros.  They skip their MFMAs (their
     // accumulators stay +0, which is what the zero products add up to) and all waves share the epilogue.
     const bool dead_slice = SKIPZ && a.ca_real > 0 && (it * C::CH_IT + ks * CPI * 16) >= a.ca_real;
+    if constexpr (T2S) {
+      // three products per k-step: S on the sum fragment, the two differences on x1 and x0; every accumulator takes its products in
+      // K order whatever the tile, consecutive matrix instructions write different accumulators
+      f32x4 asum[MB][CPI];
+#pragma unroll
+      for (int m = 0; m < MB; ++m)
+#pragma unroll
+        for (int ci = 0; ci < CPI; ++ci) asum[m][ci] = areg[m][0][ci] + areg[m][1][ci];
+#pragma unroll
+      for (int ci = 0; ci < CPI; ++ci) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const bool odd = T2S2 && (ci & 1);      // (ci is an unrolled constant: no select at run time)
+#pragma unroll
+          for (int m = 0; m < MB; ++m) {
+            f32x4& d = odd ? sacc_b[m] : sacc[m];
+            d = __builtin_amdgcn_mfma_f32_16x16x4f32(asum[m][ci][s], bc[1][ci][s], d, 0, 0, 0);
+          }
+#pragma unroll
+          for (int m = 0; m < MB; ++m) {
+            f32x4& d = odd ? acc_b[m][0] : acc[m][0];
+            d = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[m][1][ci][s], bc[2][ci][s], d, 0, 0, 0);
+          }
+#pragma unroll
+          for (int m = 0; m < MB; ++m) {
+            f32x4& d = odd ? acc_b[m][1] : acc[m][1];
+            d = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[m][0][ci][s], bc[3][ci][s], d, 0, 0, 0);
+          }
+          if (RES_OUT) {
+#pragma unroll
+            for (int to = 0; to < TO; ++to)
+#pragma unroll
+              for (int m = 0; m < MB; ++m)
+                racc[m][to] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[m][to][ci][s], rc[ci][s], racc[m][to], 0, 0, 0);
+          }
+        }
+      }
+    } else
     if (!dead_slice) {
 #pragma unroll
     for (int ci = 0; ci < CPI; ++ci) {
@@ -945,7 +1017,7 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
                             (NJ > 2 && tap_used(MODE, TO, 2) ? 1 : 0) + (NJ > 3 && tap_used(MODE, TO, 3) ? 1 : 0) +
                             (NJ > 4 && tap_used(MODE, TO, 4) ? 1 : 0);
       constexpr int NLOADS = C::NLD + (NUSED + (RES_OUT ? 1 : 0)) * CPI;
-      constexpr int NMFMA = MB * CPI * 4 * (valid_pairs(MODE, TO) + (RES_OUT ? TO : 0));
+      constexpr int NMFMA = MB * CPI * 4 * (conv_products(MODE, TO, SPLIT) + (RES_OUT ? TO : 0));
       // loads are spread evenly over the whole MFMA stream: each is consumed at the same position of the
       // next iteration, i.e. every load gets exactly one iteration of prefetch distance (bunching them
       // into the first half or third of the stream measured 1.5 % / 4 % slower)
@@ -1012,6 +1084,18 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
     }
   }
 
+  if constexpr (T2S) {      // out0 = S + (W3 - W2) x1, out1 = S + (W1 - W2) x0: from here on the tile is any other TO = 2 tile
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+      if constexpr (T2S2) {
+        sacc[m] = sacc[m] + sacc_b[m];
+        acc[m][0] = acc[m][0] + acc_b[m][0];
+        acc[m][1] = acc[m][1] + acc_b[m][1];
+      }
+      acc[m][0] = sacc[m] + acc[m][0];
+      acc[m][1] = sacc[m] + acc[m][1];
+    }
+  }
   if constexpr (C::F16 && S32) {
 #pragma unroll
     for (int t = 0; t < TO; ++t)
