@@ -219,6 +219,31 @@ LDP_API int ldp_vae_moments(ldp_handle* h, const float* img_nhwc, float* moments
 LDP_API int ldp_vae_posterior(ldp_handle* h, const float* moments, const float* eps, uint64_t seed, int64_t row_offset,
                       float* z_out, float* std_out, float* kl_out, float* stats_out, int32_t N, void* stream);
 
+/* Test hook: ONE chunk (N <= 256) of the encoder (decode == 0: in = frames (N, S, S, 3), out = moments exactly as ldp_vae_moments) or of the
+ * decoder (decode != 0: in = z, out = image exactly as ldp_vae_decode) through the same code as those calls, with every stage's output
+ * tensor copied out behind the stage (hipMemcpyAsync device-to-device on `stream`) into `taps`, and one row of `table` per stage
+ * (LDP_VAE_TRACE_COLS int64 each; host memory, valid on return):
+ *   [0] offset into taps (floats)  [1] N  [2] H  [3] W  [4] stored channel stride  [5] real channels  [6] LDP_VAE_STAGE_*
+ *   [7], [8] the stage(s) whose output it read (-1: the call's input / none)  [9] LDP_VAE_FAM_* of its convolution
+ *   [10..12] (nwn, ks, cpi) of a tconv tile  [13] LDP_VAE_STATS_* of its GroupNorm  [14] 1: its conv left column sums for the next GroupNorm
+ *   [15] 1: the tensor is (N, C, H, W), 0: (N, H, W, stride)
+ * Stages -- encoder: conv_in; per ResnetBlock2D conv1(swish(norm1 x)), the 1x1 shortcut where present, conv2(swish(norm2 h)) + skip; each
+ * Downsample2D; the attention block; conv_norm_out + conv_out; quant_conv.  Decoder: post_quant_conv (into the 64-channel padded tensor),
+ * conv_in, the same block stages, upsample + conv (preceded by an auxiliary row LDP_VAE_STAGE_UPSAMPLED: the replicated tensor the conv
+ * read), conv_norm_out + conv_out, the NCHW transpose.
+ * With taps == NULL the chunk runs untapped and only *n_stages / *floats_needed are set (table may be NULL); they are set on every call.
+ * Not for captured graphs; the product paths never call it. */
+#define LDP_VAE_TRACE_COLS 16
+enum { LDP_VAE_STAGE_CONV_IN = 0, LDP_VAE_STAGE_RES1, LDP_VAE_STAGE_SHORTCUT, LDP_VAE_STAGE_RES2, LDP_VAE_STAGE_DOWN, LDP_VAE_STAGE_ATTN,
+       LDP_VAE_STAGE_CONV_OUT, LDP_VAE_STAGE_QUANT, LDP_VAE_STAGE_POST_QUANT, LDP_VAE_STAGE_UP, LDP_VAE_STAGE_NCHW, LDP_VAE_STAGE_UPSAMPLED };
+/* none (VALU kernels) / exact-fp32 tconv tile / sconv3 on three bf16 planes, six products / sconv3 on two fp16 planes, three products /
+ * tconv tile on two fp16 planes, three products */
+enum { LDP_VAE_FAM_NONE = 0, LDP_VAE_FAM_TCONV_F32, LDP_VAE_FAM_SCONV_BF16X6, LDP_VAE_FAM_SCONV_F16X3, LDP_VAE_FAM_TCONV_F16X3 };
+/* no GroupNorm / column sums of the producing 3x3 conv / row sums of conv_in / gn_part + gn_final */
+enum { LDP_VAE_STATS_NONE = 0, LDP_VAE_STATS_CONV, LDP_VAE_STATS_CONV_IN, LDP_VAE_STATS_GN_PART };
+LDP_API int ldp_vae_trace(ldp_handle* h, int32_t decode, const float* in, float* out, int32_t N, float* taps, int64_t taps_floats,
+                  int64_t* table, int32_t table_rows, int32_t* n_stages, int64_t* floats_needed, void* stream);
+
 /* StableVAEModel.loss, forward only (model/stable_vae_model.py:25-55; get_metrics_step :78-87 after postprocess_batch):
  *   moments -> posterior draw -> decode -> mse = mean((img - pred_img)^2), kl = mean_n kl[n] (exactly 0 when use_kl == 0),
  *   loss = mse + beta * kl (== mse when use_kl == 0), and min / max / mean / population std of img and of z.
@@ -391,7 +416,8 @@ LDP_API int ldp_upsample1d_f32(const float* x, const float* kernel_host, const f
                        float* y, int32_t B, int32_t T, int32_t C, void* stream);
 
 /* y = Conv3x3(x) of the StableVAE on NHWC images: stride 1 => pad 1 (ResnetBlock2D / conv_out),
- * stride 2 => pad (0,1),(0,1) + VALID (Downsample2D).  kernel (3,3,Cin,Cout) Flax layout, host. */
+ * stride 2 => pad (0,1),(0,1) + VALID (Downsample2D).  kernel (3,3,Cin,Cout) Flax layout, host.
+ * Runs the exact-fp32 tile the engine's own plan picks for the shape with default options (one function decides both). */
 LDP_API int ldp_conv2d_3x3_f32(const float* x, const float* kernel_host, const float* bias_host, float* y,
                        int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t stride,
                        void* stream);

@@ -76,6 +76,8 @@ SIGNATURES: Dict[str, tuple] = {
     "ldp_vae_encode": (C.c_int, [_H, _FP, _FP, C.c_int32, C.c_void_p]),
     "ldp_vae_decode": (C.c_int, [_H, _FP, _FP, C.c_int32, C.c_void_p]),
     "ldp_vae_moments": (C.c_int, [_H, _FP, _FP, C.c_int32, C.c_void_p]),
+    "ldp_vae_trace": (C.c_int, [_H, C.c_int32, _FP, _FP, C.c_int32, _FP, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int64), C.c_void_p]),
     "ldp_vae_posterior": (C.c_int, [_H, _FP, _FP, C.c_uint64, C.c_int64, _FP, _FP, _FP, _FP, C.c_int32, C.c_void_p]),
     "ldp_vae_metrics": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_float, _FP, C.c_uint64, C.c_int64, _FP, _FP, _FP, C.c_void_p]),
     "ldp_resnet_encode": (C.c_int, [_H, C.c_int32, _FP, _FP, C.c_int32, C.c_void_p]),

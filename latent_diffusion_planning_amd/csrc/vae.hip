@@ -5,7 +5,7 @@
 // Toeplitz f32-MFMA kernel as the planner (tconv.hpp, MODE_K3H / MODE_K3S: a "sample" is a row tile
 // of TO pixels, the three image rows are folded into K); GroupNorm(32, eps 1e-6)+swish is applied by
 // HBM-bound element-wise kernels between convolutions (statistics: coalesced two-stage reduction,
-// deterministic order); the 4-token single-head attention of the mid block is a tiny VALU kernel.
+// deterministic order); the 4-token single-head attention of the mid block is a tiny VALU kernel between two MFMA 1x1 convs.
 #include "engine.hpp"
 #include "sconv.hpp"
 
@@ -19,8 +19,7 @@ struct GnW { DevBuf scale, bias; int c = 0; };
 struct Res2dW { GnW n1, n2; ConvW c1, c2, sc; bool has_sc = false; int cin = 0, cout = 0; };
 struct AttnW {
   GnW gn;
-  DevBuf wq, bq, wk, bk, wv, bv, wo, bo;     // Flax layout (VALU path: odd row counts)
-  ConvW qkv, proj;                            // MFMA path: [query | key | value] as one (C -> 3C) 1x1 conv, proj_attn
+  ConvW qkv, proj;                            // [query | key | value] as one (C -> 3C) 1x1 conv, proj_attn
   int c = 0;
 };
 struct MidW { Res2dW r0, r1; AttnW at; };
@@ -47,7 +46,7 @@ struct VaeState {
   ConvW dconv_out;                     // C0 -> 3 (padded to 32 columns)
   // workspaces for `ws_n` images
   int ws_n = 0;
-  DevBuf b0, b1, b2, b3, b4, part, part2, stats, small[5], qkv;
+  DevBuf b0, b1, b2, b3, b4, part, part2, stats, attn_o, qkv;
   DevBuf planes, zero;                 // split-operand convs: the normalised input as three bf16 planes; a zero page
   int eout_cols = 32;                  // padded column count of the encoder's conv_out (2 LC real)
   // loss head (ldp_vae_posterior / ldp_vae_metrics): homes outside the ping-pong buffers b0..b4, which encoder and decoder share
@@ -359,26 +358,14 @@ int load_res(ldp_handle* h, const std::string& p, int cin, int cout, Res2dW& r, 
   return LDP_OK;
 }
 
-int load_dense(ldp_handle* h, const std::string& p, int cin, int cout, DevBuf& w, DevBuf& b) {
-  const HostTensor *k = nullptr, *bb = nullptr;
-  LDP_TRY(get_weight(h, p + "/kernel", &k, {cin, cout}));
-  LDP_TRY(get_weight(h, p + "/bias", &bb, {cout}));
-  LDP_TRY(upload(w, k->data.data(), k->data.size() * 4, nullptr));
-  return upload(b, bb->data.data(), bb->data.size() * 4, nullptr);
-}
-
 int load_mid(ldp_handle* h, const std::string& p, int c, MidW& m) {
   LDP_TRY(load_res(h, p + "/resnets_0", c, c, m.r0));
   LDP_TRY(load_res(h, p + "/resnets_1", c, c, m.r1));
   m.at.c = c;
   const std::string a = p + "/attentions_0";
   LDP_TRY(load_gn(h, a + "/group_norm", c, m.at.gn));
-  LDP_TRY(load_dense(h, a + "/query", c, c, m.at.wq, m.at.bq));
-  LDP_TRY(load_dense(h, a + "/key", c, c, m.at.wk, m.at.bk));
-  LDP_TRY(load_dense(h, a + "/value", c, c, m.at.wv, m.at.bv));
-  LDP_TRY(load_dense(h, a + "/proj_attn", c, c, m.at.wo, m.at.bo));
   {
-    // MFMA path: q, k, v as ONE 1x1 conv with 3C output columns, proj_attn as another
+    // q, k, v as ONE 1x1 conv with 3C output columns, proj_attn as another
     const HostTensor *kq, *kk, *kv, *bq, *bk, *bv, *ko, *bo;
     LDP_TRY(get_weight(h, a + "/query/kernel", &kq, {c, c}));
     LDP_TRY(get_weight(h, a + "/key/kernel", &kk, {c, c}));
@@ -413,6 +400,73 @@ int load_mid(ldp_handle* h, const std::string& p, int c, MidW& m) {
 // ---------------------------------------------------------------------------------------------
 // layer launches
 // ---------------------------------------------------------------------------------------------
+// The exact-fp32 tile of a 3x3 conv (stride 1: MODE_K3H, stride 2: MODE_K3S) with rows of `Wo` output pixels: the one place that decides
+// it, for Run::conv3 and for the primitive ldp_conv2d_3x3_f32.  Whether the four-wave 64-column tile then runs on fp16 planes (SPLIT = 3)
+// is the engine's decision, not the plan's.
+int conv3_plan(int stride, int Wo, int cin_p, int cout_p, bool no_mb2, ConvPlan& p) {
+  // row tiles of 8 / 4 / 2 output pixels, whichever is the widest that divides the row (64- and 128-pixel frames: 8 down to 2; 96-pixel
+  // frames: 96 / 48 / 24 -> 8, 12 -> 4, 6 -> 2, and 3 -> the 3-pixel tile)
+  const int to = Wo % 8 == 0 ? 8 : Wo % 4 == 0 ? 4 : Wo % 2 == 0 ? 2 : Wo == 3 ? 3 : 0;
+  if (to == 0)
+    return fail(LDP_EINVAL, "unsupported image width %d for the 3x3 conv tiles", Wo);
+  p = ConvPlan{stride == 1 ? MODE_K3H : MODE_K3S, to, 2, 4, 1, 0};
+  if (to == 3) {                          // 64-column tiles only (3 x 64 = three 64-lane epilogue rows)
+    if (cout_p % 64 != 0 || cin_p % 64 != 0)
+      return fail(LDP_EINVAL, "3-pixel conv tile: %d -> %d channels must both be multiples of 64", cin_p, cout_p);
+    p.nwn = 4; p.ks = 1; p.cpi = stride == 1 ? 4 : 2;
+  }
+  // 64-column tiles (4 column waves, 32-channel sub-chunks) where the shape allows: the activation tile is staged once per 64
+  // instead of per 32 output channels (+21 % on the encoder; stride 2 as well: 18-pixel input tile),
+  // as FOUR-wave work-groups without a K split over waves (40 KB of LDS, 154 VGPRs: three of them share a CU, one's barrier / LDS phase
+  // runs under the others' MFMAs, no K combine in the epilogue; round 3: encode 27.05 -> 26.03 ms at 256 frames against the eight-wave
+  // 4 x 2 tiles, which are no longer built)
+  if (to == 8 && cout_p % 64 == 0 && cin_p % 64 == 0 && (stride == 1 || !no_mb2)) { p.nwn = 4; p.ks = 1; p.cpi = 2; }
+  if (cin_p % p.chunk() != 0 || cout_p % p.bn() != 0)
+    return fail(LDP_EINVAL, "3x3 conv %d->%d does not tile (chunk %d, block %d)", cin_p, cout_p, p.chunk(), p.bn());
+  return LDP_OK;
+}
+
+// Test hook (ldp_vae_trace): when a Run carries one, every stage's output tensor is copied out behind the stage, and a table row says
+// what it is, which stages it read, which kernel family ran its convolution and where its GroupNorm took its statistics from.
+// Stage kinds, kernel families and statistics routes are the LDP_VAE_* constants of include/ldp_hip.h.
+struct VaeTap {
+  float* buf = nullptr;                   // nullptr: count stages and floats only
+  int64_t cap = 0, used = 0;              // floats
+  int64_t* table = nullptr;               // [rows][LDP_VAE_TRACE_COLS]
+  int max_rows = 0, n = 0;
+  // what the launches of the current stage reported
+  int fam = LDP_VAE_FAM_NONE, nwn = 0, ks = 0, cpi = 0, route = LDP_VAE_STATS_NONE, fused_out = 0;
+  std::vector<std::pair<const float*, int>> owner;       // buffer -> the last stage tapped from it
+  int stage_of(const float* p) const {
+    for (const auto& o : owner) if (o.first == p) return o.second;
+    return -1;                                            // the call's own input
+  }
+  void conv(int family, const ConvPlan* p, bool fused) {
+    fam = family; nwn = p ? p->nwn : 0; ks = p ? p->ks : 0; cpi = p ? p->cpi : 0; fused_out = fused ? 1 : 0;
+  }
+  // stage output x: (N, H, W, ld) NHWC with C real channels, or (N, C, H, W) when nchw; read from the buffers in0 / in1 (nullptr: none)
+  int stage(int kind, const float* x, int N, int H, int W, int ld, int C, const float* in0, const float* in1, bool has_in,
+            bool nchw, hipStream_t s) {
+    const int64_t floats = (int64_t)N * H * W * (nchw ? C : ld);
+    if (buf) {
+      if (n >= max_rows || used + floats > cap)
+        return fail(LDP_EINVAL, "vae trace: stage %d does not fit (%lld + %lld of %lld floats, %d rows)", n, (long long)used,
+                    (long long)floats, (long long)cap, max_rows);
+      LDP_HIP(hipMemcpyAsync(buf + used, x, (size_t)floats * 4, hipMemcpyDeviceToDevice, s));
+      int64_t* r = table + (size_t)n * LDP_VAE_TRACE_COLS;
+      r[0] = used; r[1] = N; r[2] = H; r[3] = W; r[4] = nchw ? C : ld; r[5] = C; r[6] = kind;
+      r[7] = has_in ? stage_of(in0) : -1; r[8] = in1 ? stage_of(in1) : -1;
+      r[9] = fam; r[10] = nwn; r[11] = ks; r[12] = cpi; r[13] = route; r[14] = fused_out; r[15] = nchw ? 1 : 0;
+    }
+    bool found = false;
+    for (auto& o : owner) if (o.first == x) { o.second = n; found = true; }
+    if (!found) owner.emplace_back(x, n);
+    used += floats; ++n;
+    fam = LDP_VAE_FAM_NONE; nwn = ks = cpi = 0; route = LDP_VAE_STATS_NONE; fused_out = 0;
+    return LDP_OK;
+  }
+};
+
 struct Run {
   ldp_handle* h;
   VaeState& S;
@@ -424,6 +478,10 @@ struct Run {
   const float* part_for = nullptr;
   int part_nchunk = 0, part_c = 0;
   void wrote(const float* p) { if (fused_for == p) fused_for = nullptr; if (part_for == p) part_for = nullptr; }      // any other writer of that buffer
+  VaeTap* tap = nullptr;                  // ldp_vae_trace only
+  int stage(int kind, const float* x, int N, int H, int W, int ld, int C, const float* in0, const float* in1 = nullptr) {
+    return tap->stage(kind, x, N, H, W, ld, C, in0, in1, true, false, s);
+  }
 
   // GroupNorm statistics of x -> S.stats (N, G, {mean, rstd})
   int gn_stats(const GnW& g, const float* x, int N, int HW) {
@@ -431,13 +489,16 @@ struct Run {
     const int nchunk = (HW + PCH - 1) / PCH;
     if (x == fused_for && C == fused_c && !h->opt.vae_no_conv_stats) {
       // the conv that wrote x summed its columns on the way out: no second pass over x for the statistics
+      if (tap) tap->route = LDP_VAE_STATS_CONV;
       hipLaunchKernelGGL(gn_final_fused_kernel, dim3(nblk((int64_t)N * G)), dim3(256), 0, s, S.part2.f(), S.stats.f(), N,
                          fused_sbpi, C, G, HW);
     } else if (x == part_for && C == part_c) {
+      if (tap) tap->route = LDP_VAE_STATS_CONV_IN;
       hipLaunchKernelGGL(gn_final_kernel, dim3(nblk((int64_t)N * G)), dim3(256), 0, s, S.part.f(), S.stats.f(), N,
                          part_nchunk, C, G, HW);
       part_for = nullptr;                                  // S.part is scratch for every other GroupNorm
     } else {
+      if (tap) tap->route = LDP_VAE_STATS_GN_PART;
       part_for = nullptr;
       int threads = 256;
       while (threads % (C / 4) != 0) threads += 64;          // whole pixel rows per pass
@@ -478,6 +539,7 @@ struct Run {
     if (r != 0) return fail(r == -100 ? LDP_EINVAL : LDP_EHIP, "split-operand 3x3 conv launch failed (%d)", r);
     wrote(y);
     if (fuse) { fused_for = y; fused_sbpi = tpi; fused_c = w.cout_p; }
+    if (tap) tap->conv(npl == 2 ? LDP_VAE_FAM_SCONV_F16X3 : LDP_VAE_FAM_SCONV_BF16X6, nullptr, fuse);
     return LDP_OK;
   }
   bool split_ok(const ConvW& w, int N, int H, int W) const {
@@ -491,25 +553,9 @@ struct Run {
     if (stride == 1 && split_ok(w, N, Hin, Win) && !h->opt.vae_split_gn_only)
       return split_conv3(w, nullptr, x, y, N, Hin, Win, res);
     const int Ho = Hin / stride, Wo = Win / stride;
-    // row tiles of 8 / 4 / 2 output pixels, whichever is the widest that divides the row (64- and 128-pixel frames: 8 down to 2; 96-pixel
-    // frames: 96 / 48 / 24 -> 8, 12 -> 4, 6 -> 2, and 3 -> the 3-pixel tile)
-    const int to = Wo % 8 == 0 ? 8 : Wo % 4 == 0 ? 4 : Wo % 2 == 0 ? 2 : Wo == 3 ? 3 : 0;
-    if (to == 0)
-      return fail(LDP_EINVAL, "unsupported image width %d for the 3x3 conv tiles", Wo);
-    ConvPlan p{stride == 1 ? MODE_K3H : MODE_K3S, to, 2, 4, 1, 0};
-    if (to == 3) {                          // 64-column tiles only (3 x 64 = three 64-lane epilogue rows)
-      if (w.cout_p % 64 != 0 || w.cin_p % 64 != 0)
-        return fail(LDP_EINVAL, "3-pixel conv tile: %d -> %d channels must both be multiples of 64", w.cin_p, w.cout_p);
-      p.nwn = 4; p.ks = 1; p.cpi = stride == 1 ? 4 : 2;
-    }
-    // 64-column tiles (4 column waves, 32-channel sub-chunks) where the shape allows: the activation tile is staged once per 64
-    // instead of per 32 output channels (+21 % on the encoder; stride 2 as well: 18-pixel input tile),
-    // as FOUR-wave work-groups without a K split over waves (40 KB of LDS, 154 VGPRs: three of them share a CU, one's barrier / LDS phase
-    // runs under the others' MFMAs, no K combine in the epilogue; round 3: encode 27.05 -> 26.03 ms at 256 frames against the eight-wave
-    // 4 x 2 tiles, which are no longer built)
-    if (to == 8 && w.cout_p % 64 == 0 && w.cin_p % 64 == 0 && (stride == 1 || !h->opt.no_mb2)) { p.nwn = 4; p.ks = 1; p.cpi = 2; }
-    if (w.cin_p % p.chunk() != 0 || w.cout_p % p.bn() != 0)
-      return fail(LDP_EINVAL, "3x3 conv %d->%d does not tile (chunk %d, block %d)", w.cin_p, w.cout_p, p.chunk(), p.bn());
+    ConvPlan p{};
+    LDP_TRY(conv3_plan(stride, Wo, w.cin_p, w.cout_p, h->opt.no_mb2 != 0, p));
+    const int to = p.to;
     ConvArgs a{};
     a.xa = x; a.ca = w.cin_p; a.w = w.w.f(); a.bias = w.bias.f();
     a.out = y; a.cout = w.cout_p; a.res_in = res; a.flags = res ? EP_RESIN : 0;
@@ -533,6 +579,7 @@ struct Run {
     if (r != 0) return fail(r == -100 ? LDP_EINVAL : LDP_EHIP, "3x3 conv launch failed (%d)", r);
     if (fused_for == y) fused_for = nullptr;               // y rewritten: older sums are stale
     if (fuse) { fused_for = y; fused_sbpi = tpi / 16; fused_c = w.cout_p; }
+    if (tap) tap->conv(p.split == 3 ? LDP_VAE_FAM_TCONV_F16X3 : LDP_VAE_FAM_TCONV_F32, &p, fuse);
     return LDP_OK;
   }
 
@@ -551,61 +598,57 @@ struct Run {
     return conv3(w, tmp, y, N, H, W, 1, res);
   }
 
-  // 1x1 conv over pixels (rows grouped by 8)
+  // 1x1 conv over pixels (rows grouped by 8).  A last group of fewer than 8 pixels runs as a whole group: x, y and res must hold
+  // (pixels + 7) / 8 * 8 rows (what lies behind the real ones is read, and its results are written behind the real ones; a row of the
+  // product depends on its own input row only)
   int conv1(const ConvW& w, const float* x, float* y, int64_t pixels, const float* res = nullptr) {
-    if (pixels % 8 != 0) return fail(LDP_EINVAL, "1x1 conv needs a multiple of 8 pixels");
     ConvPlan p{MODE_P1, 8, 2, 4, 1, 0};
     ConvArgs a{};
     a.xa = x; a.ca = w.cin_p; a.w = w.w.f(); a.bias = w.bias.f(); a.out = y; a.cout = w.cout_p;
     a.res_in = res; a.flags = res ? EP_RESIN : 0;
     wrote(y);
-    a.B = (int)(pixels / 8); a.rows_valid = (int)pixels;
+    a.B = (int)((pixels + 7) / 8); a.rows_valid = (int)pixels;
     const int r = tconv_launch(p, a, s);
     if (r != 0) return fail(r == -100 ? LDP_EINVAL : LDP_EHIP, "1x1 conv launch failed (%d)", r);
+    if (tap) tap->conv(LDP_VAE_FAM_TCONV_F32, &p, false);
     return LDP_OK;
   }
 
   // ResnetBlock2D: x -> out (tmp buffers t0, t1; sc buffer for the projected shortcut)
   int res(const Res2dW& r, const float* x, float* out, float* t0, float* t1, float* scb, int N, int H, int W) {
     LDP_TRY(gn_conv3(r.n1, r.c1, x, t1, t0, N, H, W, nullptr));
+    if (tap) LDP_TRY(stage(LDP_VAE_STAGE_RES1, t1, N, H, W, r.c1.cout_p, r.c1.cout, x));
     const float* skip = x;
     if (r.has_sc) {
       LDP_TRY(conv1(r.sc, x, scb, (int64_t)N * H * W));
+      if (tap) LDP_TRY(stage(LDP_VAE_STAGE_SHORTCUT, scb, N, H, W, r.sc.cout_p, r.sc.cout, x));
       skip = scb;
     }
-    return gn_conv3(r.n2, r.c2, t1, out, t0, N, H, W, skip);
+    LDP_TRY(gn_conv3(r.n2, r.c2, t1, out, t0, N, H, W, skip));
+    if (tap) LDP_TRY(stage(LDP_VAE_STAGE_RES2, out, N, H, W, r.c2.cout_p, r.c2.cout, t1, skip));
+    return LDP_OK;
   }
 
   int attn(const AttnW& at, const float* x, float* out, float* t0, int N, int T) {
     const int C = at.c;
     const int R = N * T;
-    float *q = S.small[0].f(), *k = S.small[1].f(), *v = S.small[2].f(), *o = S.small[3].f(), *pr = S.small[4].f();
+    float* o = S.attn_o.f();
     LDP_TRY(gn(at.gn, x, t0, N, T, 0));
-    if (R % 8 == 0) {
-      // the four Dense layers on the MFMA 1x1 kernel: q|k|v in one launch (small[0..2] are contiguous slices
-      // of one allocation: see workspace), proj_attn with the residual add fused into its epilogue
-      float* qkv = S.qkv.f();
-      LDP_TRY(conv1(at.qkv, t0, qkv, R));
-      hipLaunchKernelGGL(attn_small_kernel, dim3(N), dim3(C), T * T * 4, s, qkv, qkv + C, qkv + 2 * C, o, T, C, 3 * C);
-      LDP_HIP(hipGetLastError());
-      return conv1(at.proj, o, out, R, x);
-    }
-    LDP_TRY(dense_launch(t0, C, at.wq.f(), C, at.bq.f(), q, C, R, C, C, 0, 0, s));
-    LDP_TRY(dense_launch(t0, C, at.wk.f(), C, at.bk.f(), k, C, R, C, C, 0, 0, s));
-    LDP_TRY(dense_launch(t0, C, at.wv.f(), C, at.bv.f(), v, C, R, C, C, 0, 0, s));
-    hipLaunchKernelGGL(attn_small_kernel, dim3(N), dim3(C), T * T * 4, s, q, k, v, o, T, C, C);
-    LDP_TRY(dense_launch(o, C, at.wo.f(), C, at.bo.f(), pr, C, R, C, C, 0, 0, s));
-    const int64_t n4 = (int64_t)R * C / 4;
-    hipLaunchKernelGGL(add_kernel, dim3(nblk(n4)), dim3(256), 0, s, pr, x, out, n4);
-    wrote(out);
+    // the four Dense layers on the MFMA 1x1 kernel at every row count (a row's bits do not depend on the batch it is in): q|k|v in one
+    // launch, proj_attn with the residual add fused into its epilogue.  N * T rows rounded up to 8 fit t0 / x / out (whole-frame buffers)
+    // and S.qkv / S.attn_o (16 rows per image: T <= 16, and 9 N + 7 <= 16 N)
+    float* qkv = S.qkv.f();
+    LDP_TRY(conv1(at.qkv, t0, qkv, R));
+    hipLaunchKernelGGL(attn_small_kernel, dim3(N), dim3(C), T * T * 4, s, qkv, qkv + C, qkv + 2 * C, o, T, C, 3 * C);
     LDP_HIP(hipGetLastError());
-    return LDP_OK;
+    return conv1(at.proj, o, out, R, x);
   }
 
   int mid(const MidW& m, float*& cur, float*& o1, float* t0, float* t1, int N, int H, int W) {
     LDP_TRY(res(m.r0, cur, o1, t0, t1, nullptr, N, H, W));
     std::swap(cur, o1);
     LDP_TRY(attn(m.at, cur, o1, t0, N, H * W));
+    if (tap) LDP_TRY(stage(LDP_VAE_STAGE_ATTN, o1, N, H, W, m.at.c, m.at.c, cur));
     std::swap(cur, o1);
     LDP_TRY(res(m.r1, cur, o1, t0, t1, nullptr, N, H, W));
     std::swap(cur, o1);
@@ -627,7 +670,7 @@ int workspace(ldp_handle* h, int n) {
   LDP_TRY(S.part2.alloc((size_t)n * (S.S * S.S / 8 / 16) * 256 * 2 * 4));      // [sample block][C <= 256][2]
   LDP_TRY(S.planes.alloc((size_t)n * S.S * S.S * std::max(S.ch[0], S.ch[1]) * 6));     // three bf16 planes of the largest conv input
   if (!S.zero.p) { LDP_TRY(S.zero.alloc(256)); LDP_HIP(hipMemset(S.zero.p, 0, 256)); }
-  for (auto& b : S.small) LDP_TRY(b.alloc((size_t)n * 16 * 256 * 4));
+  LDP_TRY(S.attn_o.alloc((size_t)n * 16 * 256 * 4));
   LDP_TRY(S.qkv.alloc((size_t)n * 16 * 3 * 256 * 4));
   S.ws_n = n;
   return LDP_OK;
@@ -727,11 +770,12 @@ using namespace ldp;
 // One chunk (n <= 256 images) of the encoder: img (n, S, S, 3) -> the first `nout` quant_conv channels, out (n, hl, hl, nout).
 // nout = LC keeps the mean (ldp_vae_encode), nout = 2 LC the mean and the log-variance (ldp_vae_moments): column j is the same fmaf
 // chain either way, so the mean channels of the two are the same bits.
-static int encode_chunk(ldp_handle* h, VaeState& S, hipStream_t s, const float* img, int n, float* out, int nout) {
+static int encode_chunk(ldp_handle* h, VaeState& S, hipStream_t s, const float* img, int n, float* out, int nout, VaeTap* tap = nullptr) {
   const int NB = (int)S.ch.size();
   const int hl = S.S >> (NB - 1);                          // latent side (2 for 64x64)
   LDP_TRY(workspace(h, n));
   Run R{h, S, s};
+  R.tap = tap;
   float *cur = S.b0.f(), *o1 = S.b1.f(), *t0 = S.b2.f(), *t1 = S.b3.f();
   int H = S.S, C = S.ch[0];
   {
@@ -746,6 +790,7 @@ static int encode_chunk(ldp_handle* h, VaeState& S, hipStream_t s, const float* 
     // stage-1 GroupNorm sums of `cur` are in S.part (one chunk per image row) when the kernel could write them there
     if (stats_fit) { R.part_for = cur; R.part_nchunk = H; R.part_c = C; }
     LDP_HIP(hipGetLastError());
+    if (tap) LDP_TRY(tap->stage(LDP_VAE_STAGE_CONV_IN, cur, n, H, H, C, C, nullptr, nullptr, false, false, s));
   }
   for (int i = 0; i < NB; ++i) {
     for (int j = 0; j < 2; ++j) {
@@ -754,26 +799,30 @@ static int encode_chunk(ldp_handle* h, VaeState& S, hipStream_t s, const float* 
     }
     if (S.down[i].has_ds) {
       LDP_TRY(R.conv3(S.down[i].ds, cur, o1, n, H, H, 2, nullptr));
+      if (tap) LDP_TRY(R.stage(LDP_VAE_STAGE_DOWN, o1, n, H / 2, H / 2, S.down[i].ds.cout_p, S.down[i].ds.cout, cur));
       std::swap(cur, o1);
       H /= 2;
     }
   }
   LDP_TRY(R.mid(S.emid, cur, o1, t0, t1, n, H, H));
   LDP_TRY(R.gn_conv3(S.enorm, S.econv_out, cur, t1, t0, n, H, H, nullptr));          // (n, hl, hl, 32): first 2*LC real
+  if (tap) LDP_TRY(R.stage(LDP_VAE_STAGE_CONV_OUT, t1, n, H, H, S.eout_cols, 2 * S.LC, cur));
   // quant_conv 1x1 (2LC -> 2LC), keep the first nout channels
   const int64_t rows = (int64_t)n * hl * hl;
   hipLaunchKernelGGL(tiny_dense_kernel, dim3(nblk(rows * nout)), dim3(256), 0, s, t1, S.eout_cols, S.quant_w.f(),
                      S.quant_b.f(), out, nout, rows, 2 * S.LC, 2 * S.LC, nout);
   LDP_HIP(hipGetLastError());
+  if (tap) LDP_TRY(R.stage(LDP_VAE_STAGE_QUANT, out, n, hl, hl, nout, nout, t1));
   return LDP_OK;
 }
 
 // One chunk of the decoder: z (n, hl, hl, LC) -> img_out (n, 3, S, S)
-static int decode_chunk(ldp_handle* h, VaeState& S, hipStream_t s, const float* z, int n, float* img_out) {
+static int decode_chunk(ldp_handle* h, VaeState& S, hipStream_t s, const float* z, int n, float* img_out, VaeTap* tap = nullptr) {
   const int NB = (int)S.ch.size();
   const int hl = S.S >> (NB - 1);
   LDP_TRY(workspace(h, n));
   Run R{h, S, s};
+  R.tap = tap;
   float *cur = S.b0.f(), *o1 = S.b1.f(), *t0 = S.b2.f(), *t1 = S.b3.f();
   int H = hl;
   const int64_t rows = (int64_t)n * hl * hl;
@@ -782,7 +831,9 @@ static int decode_chunk(ldp_handle* h, VaeState& S, hipStream_t s, const float* 
   R.wrote(t0);
   hipLaunchKernelGGL(tiny_dense_kernel, dim3(nblk(rows * S.LC)), dim3(256), 0, s, z,
                      S.LC, S.pq_w.f(), S.pq_b.f(), t0, 64, rows, S.LC, S.LC, S.LC);
+  if (tap) LDP_TRY(tap->stage(LDP_VAE_STAGE_POST_QUANT, t0, n, H, H, 64, S.LC, nullptr, nullptr, false, false, s));
   LDP_TRY(R.conv3(S.dconv_in, t0, cur, n, H, H, 1, nullptr));
+  if (tap) LDP_TRY(R.stage(LDP_VAE_STAGE_CONV_IN, cur, n, H, H, S.dconv_in.cout_p, S.dconv_in.cout, t0));
   LDP_TRY(R.mid(S.dmid, cur, o1, t0, t1, n, H, H));
   for (int i = 0; i < NB; ++i) {
     for (int j = 0; j < 3; ++j) {
@@ -795,14 +846,18 @@ static int decode_chunk(ldp_handle* h, VaeState& S, hipStream_t s, const float* 
       hipLaunchKernelGGL(upsample2_kernel, dim3(nblk(tot)), dim3(256), 0, s, cur, t0, n, H, H, C);
       R.wrote(t0);
       H *= 2;
+      if (tap) LDP_TRY(R.stage(LDP_VAE_STAGE_UPSAMPLED, t0, n, H, H, C, C, cur));      // auxiliary row: the replicated input of the next stage
       LDP_TRY(R.conv3(S.up[i].us, t0, o1, n, H, H, 1, nullptr));
+      if (tap) LDP_TRY(R.stage(LDP_VAE_STAGE_UP, o1, n, H, H, S.up[i].us.cout_p, S.up[i].us.cout, cur, t0));
       std::swap(cur, o1);
     }
   }
   LDP_TRY(R.gn_conv3(S.dnorm, S.dconv_out, cur, t1, t0, n, H, H, nullptr));          // (n, S, S, 32): first 3 real
+  if (tap) LDP_TRY(R.stage(LDP_VAE_STAGE_CONV_OUT, t1, n, H, H, 32, 3, cur));
   const int64_t tot = (int64_t)n * 3 * H * H;
   hipLaunchKernelGGL(nhwc_to_nchw3_kernel, dim3(nblk(tot)), dim3(256), 0, s, t1, img_out, n, H * H, 32);
   LDP_HIP(hipGetLastError());
+  if (tap) LDP_TRY(tap->stage(LDP_VAE_STAGE_NCHW, img_out, n, H, H, 3, 3, t1, nullptr, true, true, s));
   return LDP_OK;
 }
 
@@ -843,6 +898,23 @@ int ldp_vae_decode(ldp_handle* h, const float* z, float* img_out, int32_t N, voi
     LDP_TRY(decode_chunk(h, S, (hipStream_t)stream, z + (size_t)n0 * hl * hl * S.LC, std::min(VAE_CHUNK, N - n0),
                          img_out + (size_t)n0 * 3 * S.S * S.S));
   return LDP_OK;
+}
+
+int ldp_vae_trace(ldp_handle* h, int32_t decode, const float* in, float* out, int32_t N, float* taps, int64_t taps_floats,
+                  int64_t* table, int32_t table_rows, int32_t* n_stages, int64_t* floats_needed, void* stream) {
+  if (!h || !in || !out || N <= 0 || N > VAE_CHUNK || !n_stages || !floats_needed || (taps && (!table || table_rows <= 0 || taps_floats <= 0)))
+    return fail(LDP_EINVAL, "bad argument");
+  if (!h->vae || !V(h)->enc_ready) return fail(LDP_ESTATE, "vae weights not finalized");
+  if (decode && !V(h)->dec_ready) return fail(LDP_ESTATE, "vae decoder weights not finalized");
+  LDP_TRY(entry_fault_check(h));
+  VaeState& S = *V(h);
+  VaeTap tap;
+  tap.buf = taps; tap.cap = taps ? taps_floats : 0; tap.table = table; tap.max_rows = taps ? table_rows : 0;
+  const int r = decode ? decode_chunk(h, S, (hipStream_t)stream, in, N, out, &tap)
+                       : encode_chunk(h, S, (hipStream_t)stream, in, N, out, 2 * S.LC, &tap);
+  *n_stages = tap.n;
+  *floats_needed = tap.used;
+  return r;
 }
 
 int ldp_vae_posterior(ldp_handle* h, const float* moments, const float* eps, uint64_t seed, int64_t row_offset, float* z_out,
@@ -920,9 +992,9 @@ extern "C" int ldp_conv2d_3x3_f32(const float* x, const float* kernel_host, cons
   LDP_TRY(upload(dw_, packed.data(), packed.size() * 4, s));
   LDP_TRY(upload(db_, bias_host, (size_t)Cout * 4, s));
   const int Ho = H / stride, Wo = W / stride;
-  const int to = Wo >= 8 ? 8 : Wo;
-  ConvPlan p{stride == 1 ? MODE_K3H : MODE_K3S, to, 2, 4, 1, 0};
-  if (stride == 1 && to == 8 && Cout % 64 == 0 && Cin % 64 == 0) { p.nwn = 4; p.ks = 1; p.cpi = 2; }      // the tile the engine's convs run on
+  ConvPlan p{};
+  LDP_TRY(conv3_plan(stride, Wo, Cin, Cout, false, p));      // the tile the engine's convs run on by default (exact-fp32 form)
+  const int to = p.to;
   ConvArgs a{};
   a.xa = x; a.ca = Cin; a.w = dw_.f(); a.bias = db_.f(); a.out = y; a.cout = Cout;
   a.h_out = Ho; a.w_tiles = Wo / to; a.h_in = H; a.w_in = W;

@@ -376,6 +376,42 @@ class HipEngine:
         self.call_seq += 1
         return out
 
+    # LDP_VAE_STAGE_* / LDP_VAE_FAM_* / LDP_VAE_STATS_* of include/ldp_hip.h, by value
+    VAE_STAGE_KINDS = ("conv_in", "res1", "shortcut", "res2", "down", "attn", "conv_out", "quant", "post_quant", "up", "nchw", "upsampled")
+    VAE_FAMILIES = ("none", "tconv_f32", "sconv_bf16x6", "sconv_f16x3", "tconv_f16x3")
+    VAE_STATS_ROUTES = ("none", "conv", "conv_in", "gn_part")
+
+    def vae_trace(self, x: torch.Tensor, decode: bool = False):
+        """Test hook (ldp_vae_trace): one chunk of the encoder (x = frames (N, S, S, 3) -> moments) or of the decoder (x = z -> image)
+        through the code of vae_moments / vae_decode, every stage's output tapped.  -> (out, rows): rows[k] is a dict with the stage's
+        `kind`, `inputs` (stage indices, -1 = x), `family`, `tile` (nwn, ks, cpi), `stats` route, `fused_out`, `channels` and `t`, the
+        stored tensor on the device: (N, H, W, channel stride) -- padding included -- or (N, C, H, W) for the final transpose."""
+        x = _f32(x, self.device)
+        n, s, lc = x.shape[0], int(self.image_size), self.latent_channels
+        if decode:
+            _want("z_nhwc", x, (n, s // 32, s // 32, lc))
+            out = torch.empty((n, 3, s, s), device=self.device, dtype=torch.float32)
+        else:
+            _want("img_nhwc", x, (n, s, s, 3))
+            out = torch.empty((n, s // 32, s // 32, 2 * lc), device=self.device, dtype=torch.float32)
+        ns, nf = C.c_int32(), C.c_int64()
+        check(self.lib.ldp_vae_trace(self._h, int(decode), _ptr(x), _ptr(out), n, None, 0, None, 0, C.byref(ns), C.byref(nf), self._stream()))
+        taps = torch.empty(nf.value, device=self.device, dtype=torch.float32)
+        cols = 16                                                                   # LDP_VAE_TRACE_COLS
+        table = np.full((ns.value, cols), -7, np.int64)
+        check(self.lib.ldp_vae_trace(self._h, int(decode), _ptr(x), _ptr(out), n, _ptr(taps), nf.value, table.ctypes.data_as(C.c_void_p), ns.value,
+                                     C.byref(ns), C.byref(nf), self._stream()))
+        self.call_seq += 2
+        assert ns.value == len(table) and nf.value == taps.numel()
+        rows = []
+        for r in table:
+            off, N, H, W, ld, ch, kind, in0, in1, fam, nwn, ks, cpi, route, fused, nchw = (int(v) for v in r)
+            shape = (N, ch, H, W) if nchw else (N, H, W, ld)
+            rows.append(dict(kind=self.VAE_STAGE_KINDS[kind], inputs=tuple(i for i in (in0, in1) if i >= 0) or (-1,), family=self.VAE_FAMILIES[fam],
+                             tile=(nwn, ks, cpi), stats=self.VAE_STATS_ROUTES[route], fused_out=bool(fused), channels=ch, nchw=bool(nchw),
+                             t=taps[off:off + int(np.prod(shape))].view(shape)))
+        return out, rows
+
     def _vae_noise_args(self, noise, n, seed, row_offset):
         s = self.image_size // 32
         eps = None if noise is None else _f32(noise, self.device)

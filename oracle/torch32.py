@@ -236,15 +236,33 @@ def _gn2(P, x, prefix, groups=32):
     return F.group_norm(x, groups, P.t(f"{prefix}/scale"), P.t(f"{prefix}/bias"), eps=1e-6)
 
 
+def _conv3(P, x, prefix):
+    return F.conv2d(x, P.conv2d_w(f"{prefix}/kernel"), P.t(f"{prefix}/bias"), padding=1)
+
+
+def _conv1(P, x, prefix):
+    return F.conv2d(x, P.conv2d_w(f"{prefix}/kernel"), P.t(f"{prefix}/bias"))
+
+
+def _res_first(P, x, prefix):
+    """conv1(swish(norm1 x))"""
+    return _conv3(P, F.silu(_gn2(P, x, f"{prefix}/norm1")), f"{prefix}/conv1")
+
+
+def _res_shortcut(P, x, prefix):
+    return _conv1(P, x, f"{prefix}/conv_shortcut")
+
+
+def _res_second(P, h, skip, prefix):
+    """conv2(swish(norm2 h)) + skip"""
+    return _conv3(P, F.silu(_gn2(P, h, f"{prefix}/norm2")), f"{prefix}/conv2") + skip
+
+
 def _resnet2d(P, x, prefix):
-    h = F.conv2d(F.silu(_gn2(P, x, f"{prefix}/norm1")), P.conv2d_w(f"{prefix}/conv1/kernel"),
-                 P.t(f"{prefix}/conv1/bias"), padding=1)
-    h = F.conv2d(F.silu(_gn2(P, h, f"{prefix}/norm2")), P.conv2d_w(f"{prefix}/conv2/kernel"),
-                 P.t(f"{prefix}/conv2/bias"), padding=1)
+    h = _res_first(P, x, prefix)
     if P.has(f"{prefix}/conv_shortcut/kernel"):
-        x = F.conv2d(x, P.conv2d_w(f"{prefix}/conv_shortcut/kernel"),
-                     P.t(f"{prefix}/conv_shortcut/bias"))
-    return h + x
+        x = _res_shortcut(P, x, prefix)
+    return _res_second(P, h, x, prefix)
 
 
 def _attn(P, x, prefix):
@@ -264,35 +282,109 @@ def _mid(P, x, prefix):
     return _resnet2d(P, x, f"{prefix}/resnets_1")
 
 
+def _downsample(P, x, prefix):
+    return F.conv2d(F.pad(x, (0, 1, 0, 1)), P.conv2d_w(f"{prefix}/kernel"), P.t(f"{prefix}/bias"), stride=2)
+
+
+def _upsample(x):
+    return F.interpolate(x, scale_factor=2.0, mode="nearest")
+
+
+def _up_conv(P, x, prefix):
+    return _conv3(P, _upsample(x), prefix)
+
+
+def _norm_out_conv(P, x, side):
+    return _conv3(P, F.silu(_gn2(P, x, f"{side}/conv_norm_out")), f"{side}/conv_out")
+
+
 @torch.no_grad()
 def vae_encode_mean(P, img_nhwc, n_blocks=6, layers=2, latent_channels=4):
     x = img_nhwc.to(P.dtype).permute(0, 3, 1, 2)
-    x = F.conv2d(x, P.conv2d_w("encoder/conv_in/kernel"), P.t("encoder/conv_in/bias"), padding=1)
+    x = _conv3(P, x, "encoder/conv_in")
     for i in range(n_blocks):
         for j in range(layers):
             x = _resnet2d(P, x, f"encoder/down_blocks_{i}/resnets_{j}")
         if i != n_blocks - 1:
-            p = f"encoder/down_blocks_{i}/downsamplers_0/conv"
-            x = F.conv2d(F.pad(x, (0, 1, 0, 1)), P.conv2d_w(f"{p}/kernel"), P.t(f"{p}/bias"), stride=2)
+            x = _downsample(P, x, f"encoder/down_blocks_{i}/downsamplers_0/conv")
     x = _mid(P, x, "encoder/mid_block")
-    x = F.silu(_gn2(P, x, "encoder/conv_norm_out"))
-    x = F.conv2d(x, P.conv2d_w("encoder/conv_out/kernel"), P.t("encoder/conv_out/bias"), padding=1)
-    x = F.conv2d(x, P.conv2d_w("quant_conv/kernel"), P.t("quant_conv/bias"))
+    x = _norm_out_conv(P, x, "encoder")
+    x = _conv1(P, x, "quant_conv")
     return x[:, :latent_channels].permute(0, 2, 3, 1).contiguous()
 
 
 @torch.no_grad()
 def vae_decode(P, z_nhwc, n_blocks=6, layers=2):
     x = z_nhwc.to(P.dtype).permute(0, 3, 1, 2)
-    x = F.conv2d(x, P.conv2d_w("post_quant_conv/kernel"), P.t("post_quant_conv/bias"))
-    x = F.conv2d(x, P.conv2d_w("decoder/conv_in/kernel"), P.t("decoder/conv_in/bias"), padding=1)
+    x = _conv1(P, x, "post_quant_conv")
+    x = _conv3(P, x, "decoder/conv_in")
     x = _mid(P, x, "decoder/mid_block")
     for i in range(n_blocks):
         for j in range(layers + 1):
             x = _resnet2d(P, x, f"decoder/up_blocks_{i}/resnets_{j}")
         if i != n_blocks - 1:
-            x = F.interpolate(x, scale_factor=2.0, mode="nearest")
+            x = _up_conv(P, x, f"decoder/up_blocks_{i}/upsamplers_0/conv")
+    return _norm_out_conv(P, x, "decoder")
+
+
+# The same two computations as ordered lists of stages (tests/test_hip_vae_stages.py checks every stage of the engine on its own):
+# (kind, name, inputs, fn) with `inputs` the indices of the stages whose outputs `fn(P, *inputs)` takes (-1: the call's input, NCHW)
+# and every tensor NCHW in P.dtype.  Built from the functions above, so chaining them IS vae_encode_mean / vae_decode
+# (tests/test_oracle_vae_stages.py).  The kinds are the engine's (include/ldp_hip.h LDP_VAE_STAGE_*).
+def _resnet_stages(P, st, prefix, x_idx):
+    st.append(("res1", f"{prefix}/conv1", (x_idx,), lambda P, x, p=prefix: _res_first(P, x, p)))
+    h_idx, skip = len(st) - 1, x_idx
+    if P.has(f"{prefix}/conv_shortcut/kernel"):
+        st.append(("shortcut", f"{prefix}/conv_shortcut", (x_idx,), lambda P, x, p=prefix: _res_shortcut(P, x, p)))
+        skip = len(st) - 1
+    st.append(("res2", f"{prefix}/conv2", (h_idx, skip), lambda P, h, s, p=prefix: _res_second(P, h, s, p)))
+    return len(st) - 1
+
+
+def _mid_stages(P, st, prefix, x_idx):
+    x_idx = _resnet_stages(P, st, f"{prefix}/resnets_0", x_idx)
+    st.append(("attn", f"{prefix}/attentions_0", (x_idx,), lambda P, x, p=prefix: _attn(P, x, f"{p}/attentions_0")))
+    return _resnet_stages(P, st, f"{prefix}/resnets_1", len(st) - 1)
+
+
+def vae_encode_stages(P, n_blocks=6, layers=2):
+    """Input: frames NCHW.  The last stage is quant_conv with all 2 * latent_channels moments (vae_encode_mean keeps the first half)."""
+    st = [("conv_in", "encoder/conv_in", (-1,), lambda P, x: _conv3(P, x, "encoder/conv_in"))]
+    cur = 0
+    for i in range(n_blocks):
+        for j in range(layers):
+            cur = _resnet_stages(P, st, f"encoder/down_blocks_{i}/resnets_{j}", cur)
+        if i != n_blocks - 1:
+            p = f"encoder/down_blocks_{i}/downsamplers_0/conv"
+            st.append(("down", p, (cur,), lambda P, x, p=p: _downsample(P, x, p)))
+            cur = len(st) - 1
+    cur = _mid_stages(P, st, "encoder/mid_block", cur)
+    st.append(("conv_out", "encoder/conv_out", (cur,), lambda P, x: _norm_out_conv(P, x, "encoder")))
+    st.append(("quant", "quant_conv", (len(st) - 1,), lambda P, x: _conv1(P, x, "quant_conv")))
+    return st
+
+
+def vae_decode_stages(P, n_blocks=6, layers=2):
+    """Input: z NCHW.  The last stage is the engine's NCHW transpose: the identity here."""
+    st = [("post_quant", "post_quant_conv", (-1,), lambda P, x: _conv1(P, x, "post_quant_conv")),
+          ("conv_in", "decoder/conv_in", (0,), lambda P, x: _conv3(P, x, "decoder/conv_in"))]
+    cur = _mid_stages(P, st, "decoder/mid_block", 1)
+    for i in range(n_blocks):
+        for j in range(layers + 1):
+            cur = _resnet_stages(P, st, f"decoder/up_blocks_{i}/resnets_{j}", cur)
+        if i != n_blocks - 1:
             p = f"decoder/up_blocks_{i}/upsamplers_0/conv"
-            x = F.conv2d(x, P.conv2d_w(f"{p}/kernel"), P.t(f"{p}/bias"), padding=1)
-    x = F.silu(_gn2(P, x, "decoder/conv_norm_out"))
-    return F.conv2d(x, P.conv2d_w("decoder/conv_out/kernel"), P.t("decoder/conv_out/bias"), padding=1)
+            st.append(("up", p, (cur,), lambda P, x, p=p: _up_conv(P, x, p)))
+            cur = len(st) - 1
+    st.append(("conv_out", "decoder/conv_out", (cur,), lambda P, x: _norm_out_conv(P, x, "decoder")))
+    st.append(("nchw", "sample", (len(st) - 1,), lambda P, x: x))
+    return st
+
+
+@torch.no_grad()
+def run_stages(P, stages, x_nchw):
+    """Every stage's output, chained from the call's input."""
+    outs = []
+    for kind, name, inputs, fn in stages:
+        outs.append(fn(P, *[x_nchw.to(P.dtype) if i < 0 else outs[i] for i in inputs]))
+    return outs

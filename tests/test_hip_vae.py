@@ -35,8 +35,12 @@ def eng(vae_params):
                                                  (8, 256, 256, 1, 2), (4, 256, 256, 1, 5), (2, 256, 256, 1, 9),
                                                  (2, 256, 32, 1, 3), (64, 128, 128, 2, 1), (32, 256, 256, 2, 2),
                                                  (16, 256, 256, 2, 2), (8, 256, 256, 2, 3), (4, 256, 256, 2, 7),
-                                                 (64, 128, 32, 1, 1), (2, 64, 256, 1, 2)])
+                                                 (64, 128, 32, 1, 1), (2, 64, 256, 1, 2),
+                                                 (6, 256, 256, 2, 3), (3, 256, 256, 1, 5), (8, 128, 256, 1, 2), (8, 256, 128, 1, 3)])
 def test_conv3x3_primitive(S, cin, cout, stride, N):
+    """The primitive launches the exact-fp32 tile the engine's own plan picks (one function, csrc/vae.hip conv3_plan): stride 2 at 64 / 32 / 16
+    pixels the four-wave 64-column tile; the last four cases the 3-pixel tile of 96-pixel frames (6 -> 3 pixels stride 2, 3 pixels stride 1) and
+    Cin != Cout at stride 1 on 8 pixels."""
     from latent_diffusion_planning_amd.engine import conv2d_3x3
     g = rng(S * 7 + cin + stride)
     x = g.standard_normal((N, S, S, cin))
