@@ -337,6 +337,29 @@ LDP_API int ldp_train_init(ldp_handle* h, int32_t modules, void* stream);
 LDP_API int ldp_train_planner_grad(ldp_handle* h, const float* x0, const float* noise, const int32_t* t_dev, const float* cond,
                                    float alpha, float* loss_out, int32_t B, void* stream);
 
+/* ldp_train_planner_grad plus d loss / d cond: dcond_out (B, global_cond_dim), device, receives the gradient w.r.t. the condition -- what
+ * the diffusion policy's image encoders are trained with (agent/dp_agent.py:87-110: obs_cond is a function of the encoder parameters).
+ * The launches are those of ldp_train_planner_grad plus one copy inside the tape: loss and gradient arena are bitwise the same.
+ * LDP_EINVAL on a handle with global_cond_dim = 0. */
+LDP_API int ldp_train_planner_grad_cond(ldp_handle* h, const float* x0, const float* noise, const int32_t* t_dev, const float* cond,
+                                        float alpha, float* loss_out, float* dcond_out, int32_t B, void* stream);
+
+/* The ResNet-18 image encoders as training modules: bit 8 << slot (slot 0..3 = weight module "encoder<slot>") is accepted by
+ * ldp_train_init / _apply / _ema / _step_count / _read / _write / _arena / _grad_norm / _publish(_ema) like bits 1, 2 and 4.
+ * ldp_train_init(h, 8 << slot) before the slot has its 60 leaves: LDP_ESTATE.  Publishing repacks that slot's sampling weights, as
+ * ldp_finalize(h, 8) does.  conv_init/kernel lies in the arena as [160][64] (K = 7 * 7 * 3 = 147 padded with 13 zero rows).
+ *
+ * ldp_train_encoder_forward: ResNetEncoder.apply (see ldp_resnet_encode) on the slot's MASTER parameters with every activation kept:
+ *   img (N, 64, 64, 3) NHWC in [-1, 1] -> feat_out (N, 1024), both on the device.  1 <= N <= 1024 per call (LDP_EINVAL otherwise, with
+ *   the limit in the message).  Each slot has its own tape workspace (about 4 MB per frame), so the tapes of several slots are alive at once.
+ * ldp_train_encoder_backward: the VJP of the slot's last forward: the gradients of <dfeat, features> w.r.t. all 60 leaves REPLACE the
+ *   slot's gradient arena (padding written as zeros).  dfeat (N, 1024) on the device, N that of the forward; LDP_ESTATE without a
+ *   matching forward (none yet, another N, or ldp_train_init of the slot since).
+ * Exact fp32 products (csrc/resnet_train.hpp); no atomics: the same state and batch give the same arena bit for bit; rows are padded
+ * to 32 with zero frames, which contribute exactly zero.  Neither call synchronises. */
+LDP_API int ldp_train_encoder_forward(ldp_handle* h, int32_t slot, const float* img_nhwc, float* feat_out, int32_t N, void* stream);
+LDP_API int ldp_train_encoder_backward(ldp_handle* h, int32_t slot, const float* dfeat, int32_t N, void* stream);
+
 /* alpha * idm_loss (agent/ldp_agent.py:129-140, 154) and its gradient: s (R, 2D) = s_sprime rows, a0 / noise (R, A), t_dev (R). */
 LDP_API int ldp_train_idm_grad(ldp_handle* h, const float* s, const float* a0, const float* noise, const int32_t* t_dev, float alpha,
                                float* loss_out, int32_t R, void* stream);

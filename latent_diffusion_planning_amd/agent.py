@@ -373,13 +373,14 @@ class _EngineCalls:
         W.check_params(tree, shapes())
         return tree
 
-    def _train_sync(self, slot, state, shapes, eng=None):
+    def _train_sync(self, slot, state, shapes, eng=None, decay=None):
         """Training side: the arenas of `eng` (default: the first handle) must hold THIS state -- parameters, Adam moments (fresh when the
-        state has none) and, for a class with an EMA, the EMA arena: enabled with the class's decay, re-seeded from the parameters by the
-        (re)load, then overwritten with a distinct EMA tree.  Another model sharing the engine, a load_snapshot or a fresh create may have left
-        something else there.  A (re)load synchronises the device: call it before anything of the step is in flight."""
+        state has none) and, for a class with an EMA, the EMA arena: enabled with the class's decay (`decay`: this slot's own, for a class
+        whose states have different ones), re-seeded from the parameters by the (re)load, then overwritten with a distinct EMA tree.  Another
+        model sharing the engine, a load_snapshot or a fresh create may have left something else there.  A (re)load synchronises the device:
+        call it before anything of the step is in flight."""
         eng = self._engine if eng is None else eng
-        decay = self._ema_decay
+        decay = self._ema_decay if decay is None else decay
         if eng.train_token.get(slot) == state.version and (decay is None or eng.train_ema_token.get(slot) == state.ema_version):
             return
         W.check_params(state.params, shapes)

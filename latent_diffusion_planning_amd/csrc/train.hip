@@ -1144,6 +1144,11 @@ struct Lane {
 
 struct ProjPlan { int f_b0 = 0, f_nb = 0, f_minseg = 0, d_b0 = 0, d_nb = 0, d_minseg = 0; };      // plan_proj below
 
+constexpr int RNT_SLOTS = 4;       // ResNet image encoders per handle (weight modules encoder0 .. encoder3, module bits 8 << slot)
+constexpr int32_t MOD_ALL = 7 | (15 << 3);
+#define LDP_MODS_MSG "modules must be a mask of 1 (planner), 2 (idm), 4 (vae) and 8 << slot (encoder0 .. encoder3)"
+inline int enc_slot_of(int32_t bit) { return bit == 8 ? 0 : bit == 16 ? 1 : bit == 32 ? 2 : bit == 64 ? 3 : -1; }
+
 struct Trainer {
   int D = 0, DP = 0, A = 0, AP = 0, G = 0, T = 0, L = 0, E = 0, CP = 0;       // CP = padded width of [temb | cond]
   int IH = 0, INP = 0, NB = 0, TD = 0;                                           // IDM hidden, padded input width, blocks, time dim
@@ -1151,6 +1156,9 @@ struct Trainer {
   Module pl, idm;
   Module vae;                      // StableVAE (vae_train.hpp): described by the first ldp_train_init that asks for bit 4
   bool vae_described = false;
+  Module enc[RNT_SLOTS];           // the ResNet-18 image encoders (resnet_train.hpp): described by the first ldp_train_init that asks for their bit
+  bool enc_described[RNT_SLOTS] = {false, false, false, false};
+  int enc_fwd_n[RNT_SLOTS] = {0, 0, 0, 0};      // frames of the slot's last ldp_train_encoder_forward (0: none its backward could use)
   std::map<std::string, ConvPlan> vconvs;      // its 2-D convolutions' tables, built on the first call for a frame size
   bool tables_dirty = false;       // h_segs / h_batches grew since the last upload
   // launch tables
@@ -1170,6 +1178,7 @@ struct Trainer {
   // tables and workspaces
   DevBuf sintab_p, sintab_i;       // (n_train, E) sin|cos and (n_train, TD) cos|sin
   Lane lane[3];                    // [0] the planner's tape, [1] the IDM's, [2] the VAE's: nothing mutable is shared, they may be enqueued on different streams
+  Lane enc_lane[RNT_SLOTS];        // one per encoder slot: a slot's forward activations live until its backward, several slots' tapes at once
 };
 
 Trainer* trainer(ldp_handle* h) { return static_cast<Trainer*>(h->train); }
@@ -1603,6 +1612,9 @@ Module* module_of(ldp_handle* h, int32_t module, const char** prefix) {
   if (module == 1) { if (prefix) *prefix = "planner/"; return &t->pl; }
   if (module == 2) { if (prefix) *prefix = "idm/"; return &t->idm; }
   if (module == 4 && t->vae_described) { if (prefix) *prefix = "vae/"; return &t->vae; }
+  static const char* const enc_prefix[RNT_SLOTS] = {"encoder0/", "encoder1/", "encoder2/", "encoder3/"};
+  const int slot = enc_slot_of(module);
+  if (slot >= 0 && t->enc_described[slot]) { if (prefix) *prefix = enc_prefix[slot]; return &t->enc[slot]; }
   return nullptr;
 }
 
@@ -1678,7 +1690,7 @@ struct BlockSave {                 // what a ConditionalResidualBlock1D keeps fo
 };
 
 // ---- planner: loss + gradients (agent/ldp_agent.py:113-127; networks/diffusion_nets_v2.py:66-169) ----------------------------------
-int planner_tape(Ctx& c, const float* x0, const float* noise, const int* tdev, const float* cond, float alpha, float* loss_out, int B) {
+int planner_tape(Ctx& c, const float* x0, const float* noise, const int* tdev, const float* cond, float alpha, float* loss_out, int B, float* dcond_out = nullptr) {
   Trainer& t = *c.t;
   Module& m = t.pl;
   const int Bp = rup(B, RP), T = t.T, DP = t.DP, E = t.E, CP = t.CP, NG = c.h->cfg.n_groups;
@@ -1963,6 +1975,7 @@ int planner_tape(Ctx& c, const float* x0, const float* noise, const int* tdev, c
   float* dg = take((size_t)Bp * CP);
   LDP_TRY(fork(c, &w, 1, 1));
   LDP_TRY(act_bwd(w, dgm, CP, gbuf, CP, dg, CP, Bp, CP, 1));
+  if (dcond_out && t.G > 0) LDP_TRY(copy_cols(w, dg + E, CP, dcond_out, t.G, B, t.G));      // d loss / d cond (ldp_train_planner_grad_cond): the columns behind the time embedding
   LDP_TRY(dense_wgrad(w, md0, 4 * E, dg, CP, Gd("Dense_1/kernel"), E, Bp, 4 * E, E));
   LDP_TRY(colsum(w, dg, CP, Bp, E, Gd("Dense_1/bias")));
   float* dmd0 = take((size_t)Bp * 4 * E);
@@ -2080,6 +2093,7 @@ int idm_tape(Ctx& c, const float* s_in, const float* a0, const float* noise, con
 }
 
 #include "vae_train.hpp"
+#include "resnet_train.hpp"
 
 // size the workspace with a dry walk of the tape, then enqueue it
 template <class F>
@@ -2112,7 +2126,8 @@ int need_module(ldp_handle* h, int32_t module, Module** out) {
   if (!h) return fail(LDP_EINVAL, "null handle");
   if (!h->train) return fail(LDP_ESTATE, "ldp_train_init was not called");
   Module* m = module_of(h, module, nullptr);
-  if (!m) return fail(module == 4 ? LDP_ESTATE : LDP_EINVAL, module == 4 ? "ldp_train_init was not called for module %d" : "module must be 1 (planner), 2 (idm) or 4 (vae), got %d", module);
+  const bool known = module == 4 || enc_slot_of(module) >= 0;
+  if (!m) return fail(known ? LDP_ESTATE : LDP_EINVAL, known ? "ldp_train_init was not called for module %d" : "module must be 1 (planner), 2 (idm), 4 (vae) or 8 << slot (encoder0 .. encoder3), got %d", module);
   if (!m->ready) return fail(LDP_ESTATE, "ldp_train_init was not called for module %d", module);
   *out = m;
   return LDP_OK;
@@ -2133,7 +2148,7 @@ extern "C" {
 
 int ldp_train_init(ldp_handle* h, int32_t modules, void* stream) {
   if (!h) return fail(LDP_EINVAL, "null handle");
-  if (!(modules & 7) || (modules & ~7)) return fail(LDP_EINVAL, "modules must be a mask of 1 (planner), 2 (idm) and 4 (vae)");
+  if (!(modules & MOD_ALL) || (modules & ~MOD_ALL)) return fail(LDP_EINVAL, LDP_MODS_MSG);
   if ((modules & 4) && h->cfg.image_size <= 0) return fail(LDP_EINVAL, "module 4 (vae): this handle was created with image_size = 0, it has no StableVAE");
   LDP_HIP(hipSetDevice(h->cfg.device));
   LDP_TRY(ensure_trainer(h));
@@ -2142,10 +2157,24 @@ int ldp_train_init(ldp_handle* h, int32_t modules, void* stream) {
     describe_vae(*trainer(h), h->cfg.vae_latent_channels);
     trainer(h)->vae_described = true;
   }
-  for (int bit = 1; bit <= 4; bit <<= 1) {
+  for (int s = 0; s < RNT_SLOTS; ++s) {
+    if (!(modules & (8 << s))) continue;
+    Trainer& tr = *trainer(h);
+    if (!tr.enc_described[s]) {
+      Module probe;                                                      // (a slot that lacks a leaf is refused before it is described: LDP_ESTATE, nothing changes)
+      describe_encoder(probe);
+      for (const Leaf& l : probe.leaves)
+        if (h->weights.find("encoder" + std::to_string(s) + "/" + l.path) == h->weights.end())
+          return fail(LDP_ESTATE, "weight 'encoder%d/%s' was never set", s, l.path.c_str());
+      describe_encoder(tr.enc[s]);
+      tr.enc_described[s] = true;
+    }
+    tr.enc_fwd_n[s] = 0;                                                 // (a kept forward belongs to the parameters it ran on)
+  }
+  for (int bit = 1; bit <= (8 << (RNT_SLOTS - 1)); bit <<= 1) {
     if (!(modules & bit)) continue;
     {
-      Lane& t = trainer(h)->lane[bit == 4 ? 2 : bit - 1];
+      Lane& t = bit >= 8 ? trainer(h)->enc_lane[enc_slot_of(bit)] : trainer(h)->lane[bit == 4 ? 2 : bit - 1];
       LDP_TRY(t.gemm_cnt.alloc(CNT_TILES * 4));
       LDP_HIP(hipMemset(t.gemm_cnt.p, 0, CNT_TILES * 4));
       for (int k = 0; k < Lane::NS; ++k) {
@@ -2203,6 +2232,48 @@ int ldp_train_planner_grad(ldp_handle* h, const float* x0, const float* noise, c
   return run_tape(h, 0, (hipStream_t)stream, [&](Ctx& c) { return planner_tape(c, x0, noise, t_dev, cond, alpha, loss_out, B); });
 }
 
+int ldp_train_planner_grad_cond(ldp_handle* h, const float* x0, const float* noise, const int32_t* t_dev, const float* cond, float alpha,
+                                float* loss_out, float* dcond_out, int32_t B, void* stream) {
+  Module* m = nullptr;
+  LDP_TRY(need_module(h, 1, &m));
+  if (!x0 || !noise || !t_dev || !loss_out || !dcond_out || !cond || B <= 0) return fail(LDP_EINVAL, "bad argument");
+  if (h->cfg.global_cond_dim <= 0) return fail(LDP_EINVAL, "ldp_train_planner_grad_cond: this handle has global_cond_dim = 0, there is no condition to differentiate");
+  LDP_HIP(hipSetDevice(h->cfg.device));
+  m->gpart_fresh = false;
+  return run_tape(h, 0, (hipStream_t)stream, [&](Ctx& c) { return planner_tape(c, x0, noise, t_dev, cond, alpha, loss_out, B, dcond_out); });
+}
+
+int ldp_train_encoder_forward(ldp_handle* h, int32_t slot, const float* img_nhwc, float* feat_out, int32_t N, void* stream) {
+  if (!h) return fail(LDP_EINVAL, "null handle");
+  if (slot < 0 || slot >= RNT_SLOTS) return fail(LDP_EINVAL, "encoder slot %d: a handle has slots 0..%d", slot, RNT_SLOTS - 1);
+  Module* m = nullptr;
+  LDP_TRY(need_module(h, 8 << slot, &m));
+  if (!img_nhwc || !feat_out) return fail(LDP_EINVAL, "bad argument");
+  if (N < 1 || N > RNT_MAX_FRAMES)
+    return fail(LDP_EINVAL, "ldp_train_encoder_forward: %d frames, 1 to %d per call (the tape keeps every activation of the batch)", N, RNT_MAX_FRAMES);
+  LDP_HIP(hipSetDevice(h->cfg.device));
+  Trainer& tr = *trainer(h);
+  tr.enc_fwd_n[slot] = 0;
+  LDP_TRY(run_lane_tape(h, tr.enc_lane[slot], (hipStream_t)stream, [&](Ctx& c) { return encoder_tape(c, slot, img_nhwc, feat_out, nullptr, N, false); }));
+  tr.enc_fwd_n[slot] = N;
+  return LDP_OK;
+}
+
+int ldp_train_encoder_backward(ldp_handle* h, int32_t slot, const float* dfeat, int32_t N, void* stream) {
+  if (!h) return fail(LDP_EINVAL, "null handle");
+  if (slot < 0 || slot >= RNT_SLOTS) return fail(LDP_EINVAL, "encoder slot %d: a handle has slots 0..%d", slot, RNT_SLOTS - 1);
+  Module* m = nullptr;
+  LDP_TRY(need_module(h, 8 << slot, &m));
+  if (!dfeat) return fail(LDP_EINVAL, "bad argument");
+  if (N < 1 || N > RNT_MAX_FRAMES) return fail(LDP_EINVAL, "ldp_train_encoder_backward: %d frames, 1 to %d per call", N, RNT_MAX_FRAMES);
+  Trainer& tr = *trainer(h);
+  if (tr.enc_fwd_n[slot] != N)
+    return fail(LDP_ESTATE, "ldp_train_encoder_backward: encoder%d has no forward of %d frames to differentiate (its last forward kept %d)", slot, N, tr.enc_fwd_n[slot]);
+  LDP_HIP(hipSetDevice(h->cfg.device));
+  m->gpart_fresh = false;
+  return run_lane_tape(h, tr.enc_lane[slot], (hipStream_t)stream, [&](Ctx& c) { return encoder_tape(c, slot, nullptr, nullptr, dfeat, N, true); });
+}
+
 int ldp_train_idm_grad(ldp_handle* h, const float* s, const float* a0, const float* noise, const int32_t* t_dev, float alpha, float* loss_out,
                        int32_t R, void* stream) {
   Module* m = nullptr;
@@ -2232,13 +2303,13 @@ int ldp_train_vae_grad(ldp_handle* h, const float* img_nhwc, int32_t N, int32_t 
 
 int ldp_train_grad_norm(ldp_handle* h, int32_t modules, float* out, void* stream) {
   if (!h || !out) return fail(LDP_EINVAL, "bad argument");
-  if (!(modules & 7) || (modules & ~7)) return fail(LDP_EINVAL, "modules must be a mask of 1 (planner), 2 (idm) and 4 (vae)");
-  if (modules == 7) return fail(LDP_EINVAL, "ldp_train_grad_norm takes at most two modules per call");
+  if (!(modules & MOD_ALL) || (modules & ~MOD_ALL)) return fail(LDP_EINVAL, LDP_MODS_MSG);
+  if (__builtin_popcount((unsigned)modules) > 2) return fail(LDP_EINVAL, "ldp_train_grad_norm takes at most two modules per call");
   hipStream_t s = (hipStream_t)stream;
   const float* pa[2] = {nullptr, nullptr};
   long long na[2] = {0, 0};
   int k = 0;
-  for (int bit = 1; bit <= 4; bit <<= 1) {
+  for (int bit = 1; bit <= (8 << (RNT_SLOTS - 1)); bit <<= 1) {
     if (!(modules & bit)) continue;
     Module* m = nullptr;
     LDP_TRY(need_module(h, bit, &m));
@@ -2336,16 +2407,18 @@ int ldp_train_arena(ldp_handle* h, int32_t module, int32_t which, float** dev_ou
 // master parameters (or their EMA) -> the handle's weight store -> finalize of the listed modules
 static int publish(ldp_handle* h, int32_t modules, bool ema, void* stream) {
   if (!h) return fail(LDP_EINVAL, "null handle");
-  if (!(modules & 7) || (modules & ~7)) return fail(LDP_EINVAL, "modules must be a mask of 1 (planner), 2 (idm) and 4 (vae)");
+  if (!(modules & MOD_ALL) || (modules & ~MOD_ALL)) return fail(LDP_EINVAL, LDP_MODS_MSG);
   hipStream_t s = (hipStream_t)stream;
   LDP_HIP(hipSetDevice(h->cfg.device));
   LDP_HIP(hipStreamSynchronize(s));
-  for (int bit = 1; bit <= 4; bit <<= 1) {
+  for (int bit = 1; bit <= (8 << (RNT_SLOTS - 1)); bit <<= 1) {
     if (!(modules & bit)) continue;
     Module* m = nullptr;
     LDP_TRY(need_module(h, bit, &m));
     if (ema && !m->ema_on) return fail(LDP_ESTATE, "module %d keeps no EMA (ldp_train_ema was not called)", bit);
-    const char* prefix = bit == 1 ? "planner/" : bit == 2 ? "idm/" : "vae/";
+    const char* prefix = nullptr;
+    (void)module_of(h, bit, &prefix);
+    if (bit >= 8) resnet_invalidate(h, enc_slot_of(bit));               // (the slot's packed sampling weights are rebuilt below)
     std::vector<float> img(m->total);
     LDP_HIP(hipMemcpy(img.data(), ema ? m->E.p : m->P.p, m->total * 4, hipMemcpyDeviceToHost));
     for (const Leaf& l : m->leaves) {
@@ -2360,6 +2433,7 @@ static int publish(ldp_handle* h, int32_t modules, bool ema, void* stream) {
   if (modules & 1) LDP_TRY(planner_finalize(h, s));
   if (modules & 2) LDP_TRY(idm_finalize(h, s));
   if (modules & 4) LDP_TRY(vae_finalize(h, s));
+  if (modules & (15 << 3)) LDP_TRY(resnet_finalize(h, s));              // repacks the slots invalidated above, as ldp_finalize(h, 8) does
   LDP_HIP(hipStreamSynchronize(s));
   return LDP_OK;
 }

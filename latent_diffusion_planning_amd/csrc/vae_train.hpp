@@ -23,7 +23,7 @@
 constexpr int VAE_NG = 32;                  // norm_num_groups
 constexpr int VAE_ATT_T = 16;               // most mid-block attention tokens a work-group holds (4 / 9 / 16 at 64 / 96 / 128 px)
 constexpr int VAE_TRAIN_MAX_FRAMES = 256;   // frames per ldp_train_vae_grad call (the tape keeps every activation: ~175 MB per 64-px frame)
-enum { VC_S1 = 0, VC_S2 = 1, VC_UP = 2, VC_P1 = 3 };      // 3x3 pad 1, 3x3 stride 2 pad (0, 1), nearest x2 then 3x3, 1x1
+enum { VC_S1 = 0, VC_S2 = 1, VC_UP = 2, VC_P1 = 3, VC_P2 = 4 };      // 3x3 pad 1, 3x3 stride 2 pad (0, 1), nearest x2 then 3x3, 1x1, 1x1 stride 2
 
 __device__ __forceinline__ float vae_silu(float x) { return x / (1.0f + expf(-x)); }
 __device__ __forceinline__ float vae_silu_dx(float x) {
@@ -330,6 +330,7 @@ int vae_tap_in(int mode, int Sin, int Sout, int po, int j) {
       iy = uy >> 1; ix = ux >> 1;
       break;
     }
+    case VC_P2: return j == 0 ? 2 * y * Sin + 2 * x : -1;
     default: return j == 0 ? po : -1;
   }
   return (iy < 0 || ix < 0 || iy >= Sin || ix >= Sin) ? -1 : iy * Sin + ix;
@@ -338,7 +339,7 @@ int vae_tap_in(int mode, int Sin, int Sout, int po, int j) {
 // the three launch tables of one 2-D convolution (cin / cout padded), appended to the Trainer's (plan_conv's layout, z = pixel)
 ConvPlan plan_conv2d(Trainer& t, int mode, int Sin, int Sout, int cin, int cout) {
   ConvPlan c;
-  c.mode = mode; c.Tin = Sin * Sin; c.Tout = Sout * Sout; c.cin = cin; c.cout = cout; c.ntaps = mode == VC_P1 ? 1 : 9;
+  c.mode = mode; c.Tin = Sin * Sin; c.Tout = Sout * Sout; c.cin = cin; c.cout = cout; c.ntaps = (mode == VC_P1 || mode == VC_P2) ? 1 : 9;
   const long long wtap = (long long)cin * cout;
   c.f_b0 = (int)t.h_batches.size();
   for (int to = 0; to < c.Tout; ++to) {
@@ -677,10 +678,9 @@ int vae_tape(Ctx& c, const float* img, int B, int use_kl, float beta, const floa
   return LDP_OK;
 }
 
-// dry walk (sizes the workspace and builds the missing conv tables), table upload, then the real enqueue on the VAE's lane
-int run_vae_tape(ldp_handle* h, hipStream_t s, const std::function<int(Ctx&)>& tape) {
+// dry walk (sizes the workspace and builds the missing conv tables), table upload, then the real enqueue on the given lane
+int run_lane_tape(ldp_handle* h, Lane& t, hipStream_t s, const std::function<int(Ctx&)>& tape) {
   Trainer& tr = *trainer(h);
-  Lane& t = tr.lane[2];
   Ctx c{h, &tr, &t, s, true};
   t.colsum_need = 0;
   t.part_need = 0;
@@ -710,3 +710,4 @@ int run_vae_tape(ldp_handle* h, hipStream_t s, const std::function<int(Ctx&)>& t
   LDP_TRY(tape(c));
   return join(c);
 }
+int run_vae_tape(ldp_handle* h, hipStream_t s, const std::function<int(Ctx&)>& tape) { return run_lane_tape(h, trainer(h)->lane[2], s, tape); }

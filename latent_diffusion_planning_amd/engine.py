@@ -517,6 +517,7 @@ class HipEngine:
 
     # -- training step (include/ldp_hip.h "training step"; agent/ldp_agent.py:113-180, 223-323) -----------------------
     _MODS = {"planner": MOD_PLANNER, "idm": MOD_IDM, "vae": MOD_VAE}
+    _MODS.update({f"encoder{i}": MOD_ENCODER << i for i in range(RESNET_SLOTS)})      # the ResNet image encoders as training modules
 
     def _mask(self, modules) -> int:
         if isinstance(modules, str):
@@ -572,6 +573,41 @@ class HipEngine:
         check(self.lib.ldp_train_planner_grad(self._h, _ptr(x0), _ptr(noise), _ptr(td), _ptr(cond_t), C.c_float(alpha), _ptr(loss), B, self._stream()))
         self._keep = (x0, noise, td, cond_t)           # the launches are asynchronous: the inputs must outlive them
         return loss
+
+    def train_planner_grad_cond(self, x0: torch.Tensor, noise: torch.Tensor, t, cond: torch.Tensor, alpha: float = 1.0):
+        """train_planner_grad plus d loss / d cond (ldp_train_planner_grad_cond) -> (loss device scalar, dcond (B, G)): what DPTrainAgent
+        trains its image encoders with.  Loss and gradient arena are bitwise train_planner_grad's."""
+        x0, noise, cond_t = _f32(x0, self.device), _f32(noise, self.device), _f32(cond, self.device)
+        B = x0.shape[0]
+        td = self._timesteps(t, self.planner_train_steps, "planner")
+        _want("x0", x0, (B, self.T, self.D)); _want("noise", noise, (B, self.T, self.D)); _want("t", td, (B,)); _want("cond", cond_t, (B, self.G))
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        dcond = torch.empty((B, self.G), dtype=torch.float32, device=self.device)
+        check(self.lib.ldp_train_planner_grad_cond(self._h, _ptr(x0), _ptr(noise), _ptr(td), _ptr(cond_t), C.c_float(alpha), _ptr(loss), _ptr(dcond), B,
+                                                   self._stream()))
+        self._keep = (x0, noise, td, cond_t)
+        return loss, dcond
+
+    def train_encoder_forward(self, slot: int, img_nhwc: torch.Tensor) -> torch.Tensor:
+        """ResNetEncoder.apply on the MASTER parameters of training module encoder<slot>, every activation kept for train_encoder_backward:
+        (N, 64, 64, 3) NHWC frames in [-1, 1] -> (N, 1024).  1 <= N <= 1024."""
+        img = _f32(img_nhwc, self.device)
+        n = img.shape[0]
+        _want("img_nhwc", img, (n, 64, 64, 3))
+        out = torch.empty((n, RESNET_FEATURES), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_train_encoder_forward(self._h, int(slot), _ptr(img), _ptr(out), n, self._stream()))
+        self._keep_e = getattr(self, "_keep_e", {})
+        self._keep_e[int(slot)] = img
+        return out
+
+    def train_encoder_backward(self, slot: int, dfeat: torch.Tensor) -> None:
+        """The VJP of the slot's last train_encoder_forward: the gradients of <dfeat, features> replace the gradient arena of encoder<slot>."""
+        d = _f32(dfeat, self.device)
+        n = d.shape[0]
+        _want("dfeat", d, (n, RESNET_FEATURES))
+        check(self.lib.ldp_train_encoder_backward(self._h, int(slot), _ptr(d), n, self._stream()))
+        self._keep_d = getattr(self, "_keep_d", {})
+        self._keep_d[int(slot)] = d
 
     def train_idm_grad(self, s: torch.Tensor, a0: torch.Tensor, noise: torch.Tensor, t, alpha: float = 1.0) -> torch.Tensor:
         """alpha * idm_loss and its gradients (agent/ldp_agent.py:129-140): s (R, 2D), a0 / noise (R, A), t (R,) -> device scalar."""

@@ -1,0 +1,166 @@
+"""Test helper (not a product path): DPAgent's training step (agent/dp_agent.py:87-136) restated on the CPU with autograd.
+
+  * the ResNet-18 encoder of tests/dp_resnet_oracle.py a second time with torch LEAF tensors, so that autograd reaches the weights.  The
+    max-pool and the spatial softmax are RO.t_maxpool / RO.t_spatial_softmax as they are; the convolutions and the GroupNorm are RO's
+    formulas on tensors (RO.t_conv* / RO.t_gn turn their weights into constants with np.asarray) -- tests/test_dp_train_cpu.py checks that
+    the restatement reproduces RO.encode and RO.loss
+  * the DP loss through oracle.train.GradParams / oracle.torch32.unet_forward with a differentiable condition
+  * adam_apply + the parameter EMA (utils/flax_utils.py:22-27) from oracle/train.py
+
+dtype float64 is the reference; float32 is what the number format alone costs (err32 of the error rule).
+"""
+from __future__ import annotations
+
+from collections import OrderedDict
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from latent_diffusion_planning_amd import weights as W
+from oracle import np64, torch32
+from oracle import train as OT
+from tests import dp_resnet_oracle as RO
+
+F64 = np.float64
+SPEC = RO.SPEC
+
+
+def leaves_of(params, dtype=torch.float64):
+    """{path: leaf tensor (requires_grad) in the Flax layout}."""
+    return OrderedDict((k, torch.tensor(np.asarray(v, F64), dtype=dtype, requires_grad=True)) for k, v in params.items())
+
+
+def grad_params(params, dtype=torch.float64):
+    """oracle.train.GradParams at a chosen dtype (its leaves are float64)."""
+    P = OT.GradParams(params)
+    if dtype != torch.float64:
+        P.dtype = dtype
+        P.leaves = leaves_of(params, dtype)
+    return P
+
+
+def grads_of(leaves):
+    return OrderedDict((k, (v.grad if v.grad is not None else torch.zeros_like(v)).detach().to(torch.float64).numpy().copy())
+                       for k, v in leaves.items())
+
+
+def _w(k):                          # Flax (kh, kw, Cin, Cout) -> torch (Cout, Cin, kh, kw)
+    return k.permute(3, 2, 0, 1).contiguous()
+
+
+def _conv3x3(x, k, stride):
+    if stride == 1:
+        return F.conv2d(x, _w(k), padding=1)
+    return F.conv2d(F.pad(x, (0, 1, 0, 1)), _w(k), stride=2)
+
+
+def _gn(x, scale, bias, groups, eps):
+    n, c, h, w = x.shape
+    g = x.reshape(n, groups, -1)
+    d = g - g.mean(dim=2, keepdim=True)
+    var = (d * d).mean(dim=2, keepdim=True)
+    return (d * torch.rsqrt(var + eps)).reshape(n, c, h, w) * scale.reshape(1, c, 1, 1) + bias.reshape(1, c, 1, 1)
+
+
+def encode_t(L, img_nhwc, return_maps=False):
+    """ResNetEncoder.apply on leaf tensors: img (N, 64, 64, 3) tensor of the leaves' dtype -> (N, 1024) tensor (autograd attached).
+    return_maps: also (stem map after GroupNorm + ReLU, last feature map), both NCHW."""
+    x = img_nhwc.permute(0, 3, 1, 2)
+    x = F.conv2d(x, _w(L["conv_init/kernel"]), stride=2, padding=3)
+    stem = torch.relu(_gn(x, L["norm_init/scale"], L["norm_init/bias"], SPEC.groups, SPEC.eps))
+    x = RO.t_maxpool(stem)
+    for i, (_, _, stride, proj) in enumerate(SPEC.blocks()):
+        p = f"ResNetBlock_{i}"
+        y = _conv3x3(x, L[f"{p}/Conv_0/kernel"], stride)
+        y = torch.relu(_gn(y, L[f"{p}/MyGroupNorm_0/scale"], L[f"{p}/MyGroupNorm_0/bias"], SPEC.groups, SPEC.eps))
+        y = _conv3x3(y, L[f"{p}/Conv_1/kernel"], 1)
+        y = _gn(y, L[f"{p}/MyGroupNorm_1/scale"], L[f"{p}/MyGroupNorm_1/bias"], SPEC.groups, SPEC.eps)
+        r = x
+        if proj:
+            r = F.conv2d(x, _w(L[f"{p}/conv_proj/kernel"]), stride=2)
+            r = _gn(r, L[f"{p}/norm_proj/scale"], L[f"{p}/norm_proj/bias"], SPEC.groups, SPEC.eps)
+        x = torch.relu(r + y)
+    out = RO.t_spatial_softmax(x)
+    return (out, stem, x) if return_maps else out
+
+
+def encoder_vjp(params, img_nhwc, dfeat, dtype=torch.float64):
+    """-> (features (N, 1024) float64 array, {path: d <dfeat, features> / d leaf} float64 arrays, last feature map NHWC)."""
+    L = leaves_of(params, dtype)
+    feat, _, last = encode_t(L, torch.as_tensor(np.asarray(img_nhwc), dtype=dtype), return_maps=True)
+    (feat * torch.as_tensor(np.asarray(dfeat), dtype=dtype)).sum().backward()
+    return feat.detach().to(torch.float64).numpy(), grads_of(L), last.detach().permute(0, 2, 3, 1).to(torch.float64).numpy()
+
+
+def pool_ties(stem_nchw):
+    """Max-pool windows (3x3 stride 2, (0, 1) padding) of the stem map whose POSITIVE maximum is attained more than once: where the backward's
+    tie rule would matter (a tie at 0 gets no gradient through the ReLU)."""
+    x = F.pad(stem_nchw.detach(), (0, 1, 0, 1), value=float("-inf"))
+    win = x.unfold(2, 3, 2).unfold(3, 3, 2)
+    win = win.reshape(*win.shape[:4], 9)
+    m = win.max(dim=-1, keepdim=True).values
+    return int((((win == m).sum(dim=-1) > 1) & (m[..., 0] > 0)).sum())
+
+
+# ---- the training step ----------------------------------------------------------------------------------------------------------------
+def cond_t(data, nobs, feats, obs_horizon, shared, dtype):
+    """RO.obs_cond_from_features on tensors (agent/dp_agent.py:31-52)."""
+    low = torch.cat([torch.as_tensor(np.asarray(nobs[k][:, :obs_horizon]), dtype=dtype) for k in data["lowdim_obs"]], dim=-1)
+    B = low.shape[0]
+    img = feats["shared"].reshape(B, -1) if shared else torch.cat([feats[k].reshape(B, -1) for k in data["rgb_obs"]], dim=-1)
+    return torch.cat([img, low.reshape(B, -1)], dim=-1)
+
+
+def loss_and_grads(data, p, enc, obs, actions, t, noise, obs_horizon, shared=False, n_train=100, dtype=torch.float64):
+    """jax.grad(loss) (agent/dp_agent.py:87-110, 112-120), t and noise explicit -> dict(loss, cond, dcond, g_planner, g_enc {key: tree})."""
+    nobs = RO.normalized_obs(data, obs)
+    ins = RO.encoder_inputs(data, nobs, obs_horizon, shared)
+    EL = {k: leaves_of(enc[k], dtype) for k in ins}
+    feats = {k: encode_t(EL[k], torch.as_tensor(np.asarray(v), dtype=dtype)) for k, v in ins.items()}
+    cond = cond_t(data, nobs, feats, obs_horizon, shared, dtype)
+    cond.retain_grad()
+    a = np64.apply_norm(np.asarray(actions, np.float32), data["obs_normalization"]["actions"], True).astype(np.float32)
+    P = grad_params(p, dtype)
+    nz = torch.tensor(np.asarray(noise), dtype=dtype)
+    noisy = OT._add_noise(torch.tensor(a, dtype=dtype), nz, t, n_train).to(dtype)
+    pred = torch32.unet_forward(P, noisy, torch.as_tensor(np.asarray(t).reshape(-1)), cond)
+    loss = ((pred - nz) ** 2).mean()
+    loss.backward()
+    return dict(loss=float(loss.detach()), cond=cond.detach().to(torch.float64).numpy(), dcond=cond.grad.detach().to(torch.float64).numpy(),
+                g_planner=grads_of(P.leaves), g_enc={k: grads_of(EL[k]) for k in EL})
+
+
+def schedule(kw):
+    return OT.warmup_cosine_decay_schedule(float(kw["end_lr"]), float(kw["lr"]), int(kw["warmup_steps"]), int(kw["decay_steps"]), float(kw["end_lr"]))
+
+
+class DPTrainOracle:
+    """update (agent/dp_agent.py:112-136): one Adam step per state at lr = schedule(that state's step), then the EMA of each."""
+
+    def __init__(self, data, kw, planner_params, enc_params):
+        self.data, self.kw = data, kw
+        self.oh, self.shared = int(kw["obs_horizon"]), bool(kw["shared_encoder"])
+        self.sched = schedule(kw)
+        f = lambda tree: OrderedDict((k, np.asarray(v, F64)) for k, v in tree.items())
+        self.p, self.enc = f(planner_params), {k: f(v) for k, v in enc_params.items()}
+        self.p_ema, self.enc_ema = f(planner_params), {k: f(v) for k, v in enc_params.items()}
+        self.p_opt, self.enc_opt = OT.adam_init(self.p), {k: OT.adam_init(v) for k, v in self.enc.items()}
+
+    @staticmethod
+    def _ema(ema, new, decay):
+        return OrderedDict((k, ema[k] * decay + new[k] * (1.0 - decay)) for k in new)
+
+    def update(self, obs, actions, t, noise):
+        p32 = {k: np.asarray(v, np.float32) for k, v in self.p.items()}
+        e32 = {key: {k: np.asarray(v, np.float32) for k, v in tree.items()} for key, tree in self.enc.items()}
+        r = loss_and_grads(self.data, p32, e32, obs, actions, t, noise, self.oh, self.shared, int(self.kw["n_diffusion_steps"]))
+        m = dict(loss=r["loss"], planner_lr=np.float32(self.sched(self.p_opt["count"])), planner_step=self.p_opt["count"])
+        for key in self.enc:
+            m[f"enc_{key}_lr"], m[f"enc_{key}_step"] = np.float32(self.sched(self.enc_opt[key]["count"])), self.enc_opt[key]["count"]
+        self.p, self.p_opt = OT.adam_apply(self.p, r["g_planner"], self.p_opt, self.sched)
+        self.p_ema = self._ema(self.p_ema, self.p, float(self.kw["planner_ema_decay"]))
+        for key in self.enc:
+            self.enc[key], self.enc_opt[key] = OT.adam_apply(self.enc[key], r["g_enc"][key], self.enc_opt[key], self.sched)
+            self.enc_ema[key] = self._ema(self.enc_ema[key], self.enc[key], float(self.kw["encoder_ema_decay"]))
+        return r, m
