@@ -63,32 +63,37 @@ def _gn(x, scale, bias, groups, eps):
     return (d * torch.rsqrt(var + eps)).reshape(n, c, h, w) * scale.reshape(1, c, 1, 1) + bias.reshape(1, c, 1, 1)
 
 
-def encode_t(L, img_nhwc, return_maps=False):
+def encode_t(L, img_nhwc, return_maps=False, pool=None, taps=None):
     """ResNetEncoder.apply on leaf tensors: img (N, 64, 64, 3) tensor of the leaves' dtype -> (N, 1024) tensor (autograd attached).
-    return_maps: also (stem map after GroupNorm + ReLU, last feature map), both NCHW."""
+    return_maps: also (stem map after GroupNorm + ReLU, last feature map), both NCHW.  pool: a replacement of RO.t_maxpool (pool_with_rule).
+    taps: a list that receives every ReLU input (17 tensors, NCHW) in the order of the network."""
+    def relu(v):
+        if taps is not None:
+            taps.append(v.detach())
+        return torch.relu(v)
     x = img_nhwc.permute(0, 3, 1, 2)
     x = F.conv2d(x, _w(L["conv_init/kernel"]), stride=2, padding=3)
-    stem = torch.relu(_gn(x, L["norm_init/scale"], L["norm_init/bias"], SPEC.groups, SPEC.eps))
-    x = RO.t_maxpool(stem)
+    stem = relu(_gn(x, L["norm_init/scale"], L["norm_init/bias"], SPEC.groups, SPEC.eps))
+    x = (pool or RO.t_maxpool)(stem)
     for i, (_, _, stride, proj) in enumerate(SPEC.blocks()):
         p = f"ResNetBlock_{i}"
         y = _conv3x3(x, L[f"{p}/Conv_0/kernel"], stride)
-        y = torch.relu(_gn(y, L[f"{p}/MyGroupNorm_0/scale"], L[f"{p}/MyGroupNorm_0/bias"], SPEC.groups, SPEC.eps))
+        y = relu(_gn(y, L[f"{p}/MyGroupNorm_0/scale"], L[f"{p}/MyGroupNorm_0/bias"], SPEC.groups, SPEC.eps))
         y = _conv3x3(y, L[f"{p}/Conv_1/kernel"], 1)
         y = _gn(y, L[f"{p}/MyGroupNorm_1/scale"], L[f"{p}/MyGroupNorm_1/bias"], SPEC.groups, SPEC.eps)
         r = x
         if proj:
             r = F.conv2d(x, _w(L[f"{p}/conv_proj/kernel"]), stride=2)
             r = _gn(r, L[f"{p}/norm_proj/scale"], L[f"{p}/norm_proj/bias"], SPEC.groups, SPEC.eps)
-        x = torch.relu(r + y)
+        x = relu(r + y)
     out = RO.t_spatial_softmax(x)
     return (out, stem, x) if return_maps else out
 
 
-def encoder_vjp(params, img_nhwc, dfeat, dtype=torch.float64):
+def encoder_vjp(params, img_nhwc, dfeat, dtype=torch.float64, pool=None):
     """-> (features (N, 1024) float64 array, {path: d <dfeat, features> / d leaf} float64 arrays, last feature map NHWC)."""
     L = leaves_of(params, dtype)
-    feat, _, last = encode_t(L, torch.as_tensor(np.asarray(img_nhwc), dtype=dtype), return_maps=True)
+    feat, _, last = encode_t(L, torch.as_tensor(np.asarray(img_nhwc), dtype=dtype), return_maps=True, pool=pool)
     (feat * torch.as_tensor(np.asarray(dfeat), dtype=dtype)).sum().backward()
     return feat.detach().to(torch.float64).numpy(), grads_of(L), last.detach().permute(0, 2, 3, 1).to(torch.float64).numpy()
 
@@ -101,6 +106,84 @@ def pool_ties(stem_nchw):
     win = win.reshape(*win.shape[:4], 9)
     m = win.max(dim=-1, keepdim=True).values
     return int((((win == m).sum(dim=-1) > 1) & (m[..., 0] > 0)).sum())
+
+
+# ---- the max-pool tie case ------------------------------------------------------------------------------------------------------------------
+def tie_stem_kernel():
+    """conv_init/kernel (7, 7, 3, 64) that is zero but for the centre tap: k[3, 3, o % 3, o] = +-2^-(o % 4).  The stem's output is then one
+    pixel times a power of two: exact in every precision and under every accumulation order, so equal pixels stay EQUAL through the
+    convolution, and through GroupNorm + ReLU (one value in, one value out, per sample and channel)."""
+    k = np.zeros((7, 7, 3, SPEC.n_filters), np.float32)
+    for o in range(SPEC.n_filters):
+        k[3, 3, o % 3, o] = (-1.0 if (o // 4) % 2 else 1.0) * 2.0 ** -(o % 4)
+    return k
+
+
+def tie_frames(n, seed):
+    """uint8 frames (n, 64, 64, 3) whose pixels are drawn independently from four levels: flat regions everywhere, as in rendered simulator
+    frames, so that most 3x3 pool windows hold their maximum more than once."""
+    from tests.util import rng
+    return (rng(seed).integers(0, 4, size=(n, 64, 64, 3)) * 85).astype(np.uint8)
+
+
+def tie_case(n=3, seed=960):
+    """-> (the perturbed parameters of `seed` with tie_stem_kernel as their stem, tie_frames(n, seed)): the case of the tie tests."""
+    p = {k: np.asarray(v, np.float32) for k, v in W.init_resnet_params(SPEC, seed=seed, perturb=True).items()}
+    p["conv_init/kernel"] = tie_stem_kernel()
+    return p, tie_frames(n, seed)
+
+
+# ---- frames whose gates float32 cannot move ---------------------------------------------------------------------------------------------------
+def gate_margins(params, img_nhwc):
+    """The two places where the encoder's VJP is discontinuous in its activations: a ReLU input near zero, and a max-pool window whose two
+    largest values (the largest positive) are near each other.  Float32 round-off moves such a gate the other way than float64 has it, and
+    with it that element's whole contribution to every gradient upstream -- about 1 / sqrt(terms) of a leaf maximum, no error of a kernel and
+    not comparable at 1e-4.  -> (margin (N,): per frame, the smallest |ReLU input| and pool gap in float64; roundoff: the largest
+    |float32 - float64| of any ReLU input of the frames)."""
+    x, t64, t32 = np.asarray(img_nhwc), [], []
+    with torch.no_grad():
+        _, stem, _ = encode_t(leaves_of(params, torch.float64), torch.as_tensor(x, dtype=torch.float64), return_maps=True, taps=t64)
+        encode_t(leaves_of(params, torch.float32), torch.as_tensor(x, dtype=torch.float32), taps=t32)
+        win = F.pad(stem, (0, 1, 0, 1), value=float("-inf")).unfold(2, 3, 2).unfold(3, 3, 2)
+        top = win.reshape(*win.shape[:4], 9).topk(2, dim=-1).values
+        gap = torch.where(top[..., 0] > 0, top[..., 0] - top[..., 1], torch.full_like(top[..., 0], float("inf")))
+        margin = torch.stack([t.abs().flatten(1).min(dim=1).values for t in t64] + [gap.flatten(1).min(dim=1).values]).min(dim=0).values
+        roundoff = max(float((a.double() - b).abs().max()) for a, b in zip(t32, t64))
+    assert len(t64) == 17
+    return margin.numpy(), roundoff
+
+
+GATE_MARGIN_OVER_ROUNDOFF = 3.0      # the factor the gradient rule gives float32's own error (DESIGN 4.11), here between a gate and any float32 deviation seen
+
+
+def clear_frames(params, keep, pool, seed):
+    """`keep` of the `pool` frames RO.synth_frames(pool, seed) whose gates stay clearest of float32 round-off (those with the largest
+    gate_margins; GroupNorm is per sample, so a frame's margin does not depend on its batch) -> (frames uint8 (keep, 64, 64, 3),
+    dict(kept_min, roundoff, ratio)).  The tests tile a batch from them with distinct feature gradients per row."""
+    from tests.golden.make_golden_dp_resnet import frames_to_input
+    frames = RO.synth_frames(pool, seed)
+    margin, roundoff = gate_margins(params, frames_to_input(frames))
+    idx = np.sort(np.argsort(-margin, kind="stable")[:keep])
+    info = dict(kept_min=float(margin[idx].min()), roundoff=roundoff)
+    info["ratio"] = info["kept_min"] / roundoff
+    return frames[idx], info
+
+
+def pool_with_rule(rule):
+    """RO.t_maxpool with an explicit rule for a maximum attained more than once, value-identical to it: "first" / "last" take the gradient to
+    the first / last maximum of the window in row-major order, "split" divides it evenly among them."""
+    def pool(x_nchw):
+        x = F.pad(x_nchw, (0, 1, 0, 1), value=float("-inf"))
+        win = x.unfold(2, 3, 2).unfold(3, 3, 2)
+        win = win.reshape(*win.shape[:4], 9)                          # (n, c, Ho, Wo, dy * 3 + dx)
+        eq = win == win.max(dim=-1, keepdim=True).values
+        if rule == "split":
+            return torch.where(eq, win, torch.zeros_like(win)).sum(dim=-1) / eq.sum(dim=-1)
+        rank = torch.arange(9, 0, -1) if rule == "first" else torch.arange(1, 10)
+        idx = (eq * rank).argmax(dim=-1, keepdim=True)
+        return win.gather(-1, idx)[..., 0]
+    assert rule in ("first", "last", "split"), rule
+    return pool
 
 
 # ---- the training step ----------------------------------------------------------------------------------------------------------------

@@ -62,6 +62,64 @@ def test_pool_ties_counts_only_positive_repeated_maxima():
     assert TO.pool_ties(x) == 0
 
 
+def test_tie_case_separates_the_first_maximum_rule_from_a_wrong_one():
+    """The case tests/test_hip_resnet_train_shapes.py runs the GPU's max-pool backward on (TO.tie_case): most pool windows hold their positive
+    maximum more than once, identically in float64 and float32; F.max_pool2d's gradient is that of "the first maximum in row-major order";
+    and a kernel that took the last maximum, or split the gradient among the tied entries, would miss conv_init/kernel's gradient by at
+    least 100 x the GPU rule's bound (1e-4 leafmax): a wrong rule cannot pass there."""
+    from tests.golden.make_golden_dp_resnet import frames_to_input
+    p, frames = TO.tie_case()
+    x = frames_to_input(frames)
+    d = rng(960 + 77).standard_normal((3, RO.FEAT)).astype(np.float32)
+    ties, taps = [], {}
+    for dt in (torch.float64, torch.float32):
+        _, stem, _ = TO.encode_t(TO.leaves_of(p, dt), torch.as_tensor(x, dtype=dt), return_maps=True, taps=taps.setdefault(dt, []))
+        ties.append(TO.pool_ties(stem))
+    assert ties[0] == ties[1] >= 10000 and ties[0] <= 3 * 64 * 16 * 16, ties
+    # and no ReLU input of the case lies where float32 round-off could gate it the other way (the pool's equal values are exactly equal)
+    gate = min(float(a.abs().min()) for a in taps[torch.float64])
+    roundoff = max(float((b.double() - a).abs().max()) for a, b in zip(taps[torch.float64], taps[torch.float32]))
+    assert gate >= TO.GATE_MARGIN_OVER_ROUNDOFF * roundoff, (gate, roundoff)
+    f64, g64, _ = TO.encoder_vjp(p, x, d)
+    _, g32, _ = TO.encoder_vjp(p, x, d, torch.float32)
+    key = "conv_init/kernel"
+    leafmax = float(np.abs(g64[key]).max())
+    err32 = float(np.abs(g32[key] - g64[key]).max())
+    bound = max(1e-4 * leafmax, 3.0 * err32) + 1e-12              # the GPU rule on this leaf
+    got = {}
+    for rule in ("first", "last", "split"):
+        f, g, _ = TO.encoder_vjp(p, x, d, pool=TO.pool_with_rule(rule))
+        np.testing.assert_allclose(f, f64, rtol=0, atol=1e-12)     # the rules differ in the backward only
+        got[rule] = g
+    print(f"tie case: {ties[0]} of {3 * 64 * 16 * 16} windows tied; err32 {err32 / leafmax:.1e} leafmax; conv_init/kernel off by "
+          f"{np.abs(got['last'][key] - g64[key]).max() / leafmax:.2f} (last) and {np.abs(got['split'][key] - g64[key]).max() / leafmax:.2f} (split) leafmax")
+    assert bound == pytest.approx(1e-4 * leafmax, rel=1e-6), "float32's own error sets the bound: the margin below would not be the rule's"
+    for k, ref in g64.items():
+        assert np.abs(got["first"][k] - ref).max() <= 1e-12 * np.abs(ref).max(), k
+    for rule in ("last", "split"):
+        assert np.abs(got[rule][key] - g64[key]).max() >= 100.0 * bound, rule
+
+
+def test_clear_frames_keep_every_gate_clear_of_float32_round_off():
+    """What the batches of tests/test_hip_resnet_train_shapes.py rest on (same seeds): the kept frames' smallest |ReLU input| and pool gap is
+    at least 3 x the largest |float32 - float64| of any ReLU input of the pool, exactly the frames with the largest margins are kept, a
+    frame's margin does not depend on its batch -- and 129 frames as they come do hold a gate inside that round-off."""
+    from tests.golden.make_golden_dp_resnet import frames_to_input
+    from tests.test_hip_resnet_train import _params
+    from tests.test_hip_resnet_train_shapes import DISTINCT, POOL, SEED
+    p = _params("perturbed", SEED)
+    frames, info = TO.clear_frames(p, DISTINCT, POOL, SEED)
+    print(f"clear frames: {DISTINCT} of {POOL}, smallest kept margin {info['kept_min']:.2e}, round-off {info['roundoff']:.2e}, ratio {info['ratio']:.1f}")
+    assert frames.shape == (DISTINCT, 64, 64, 3) and info["ratio"] >= TO.GATE_MARGIN_OVER_ROUNDOFF, info
+    pool = RO.synth_frames(POOL, SEED)
+    margin, roundoff = TO.gate_margins(p, frames_to_input(pool[:129]))
+    print(f"129 frames as they come: smallest margin {margin.min():.2e}, round-off {roundoff:.2e}")
+    assert margin.min() < roundoff
+    kept, _ = TO.gate_margins(p, frames_to_input(frames))
+    assert kept.min() == pytest.approx(info["kept_min"], rel=1e-6)                    # alone or in the pool: the same margin
+    assert sum(1 for f in pool[:129] if any(np.array_equal(f, k) for k in frames)) == int((margin >= info["kept_min"] * (1 - 1e-6)).sum())
+
+
 def test_encoder_vjp_is_linear_in_dfeat_and_matches_finite_differences():
     small = {k: np.asarray(v, np.float32) for k, v in W.init_resnet_params(RO.SPEC, seed=5, perturb=True).items()}
     x = (rng(6).uniform(-1, 1, (1, 64, 64, 3))).astype(np.float32)

@@ -1,7 +1,7 @@
 """CPU checks of the training-step oracle and host logic (oracle/train.py, latent_diffusion_planning_amd/schedule.py): analytic known answers for
 optax.adam and warmup_cosine_decay_schedule as restated, the autograd definition against central differences, the product's schedule against the
-oracle's, the digests the goldens keep; and what tests/test_hip_train_shapes.py rests on (tests/train_cases.py): the batch decomposition, the IDM
-row selection, the restated launch-shape rule."""
+oracle's, the digests the goldens keep; and what tests/test_hip_train_shapes.py and tests/test_hip_resnet_train_shapes.py rest on
+(tests/train_cases.py): the batch decomposition, the IDM row selection, the restated launch-shape rule, the encoder tape's restated launches."""
 import math
 
 import numpy as np
@@ -216,3 +216,51 @@ def test_the_shape_cases_reach_every_training_gemm_instantiation():
     assert {"nn_32_ki2", "nt_32_ki2", "tn_32_ki2"} <= TC.expected("planner", 32, "ki2_32")[0]
     assert {"nn_64_ki2", "nt_64_ki2", "tn_64_ki2"} <= TC.expected("planner", 32, "ki2_64")[0] and {"nn_64_ki2", "nt_64_ki2", "tn_64_ki2"} <= TC.expected("idm", 320, "ki2_64")[0]
     assert "fused" in TC.expected("planner", 64, "deep")[0] and "reduce" in TC.expected("idm", 32, "reduce")[0]
+
+
+def test_the_encoder_cases_reach_every_training_gemm_instantiation():
+    """tests/test_hip_resnet_train_shapes.py, part A: the ResNet-18 tape's 59 GEMM launches as tests/train_cases.py restates them from the
+    convolution tables (vae_tap_in / plan_conv2d), the launch-table facts the restatement rests on worked out by hand, and the counters the
+    (case, configuration) pairs require covering all 15 instantiations, the in-launch finish and the reduce launch."""
+    from tests import train_cases as TC
+    from tests.test_hip_resnet_train_shapes import CASES, WORKLOAD
+    # a 3x3 at 2x2 pixels: every output pixel sees 4 live taps, every input pixel is read 4 times, the centre tap is live at all 4 pixels and a corner tap at 1
+    assert TC.conv_plan(TC.VC_S1, 2, 2) == dict(f_nb=4, f_minseg=4, d_nb=4, d_minseg=4, w_nb=9, w_minseg=1)
+    # 3x3 stride 2 pad (0, 1), 4 -> 2: the last output row / column loses a tap row / column; input pixel (0, 0) is read once
+    assert TC.conv_plan(TC.VC_S2, 4, 2) == dict(f_nb=4, f_minseg=4, d_nb=16, d_minseg=1, w_nb=9, w_minseg=1)
+    # the stride-2 1x1: the pixels it skips have data-gradient batches without segments
+    assert TC.conv_plan(TC.VC_P2, 16, 8) == dict(f_nb=64, f_minseg=1, d_nb=256, d_minseg=0, w_nb=1, w_minseg=64)
+    assert TC.conv_plan(TC.VC_P1, 32, 32) == dict(f_nb=1024, f_minseg=1, d_nb=1024, d_minseg=1, w_nb=1, w_minseg=1024)
+    convs = TC.encoder_convs()
+    assert len(convs) == 20 and sum(1 for c in convs if c[0] == TC.VC_P2) == 3 and convs[0] == (TC.VC_P1, 32, 32, 160, 64, False)
+    assert convs[-1] == (TC.VC_S1, 2, 2, 512, 512, True)
+    for rows in (32, 64, 160, 512, 1024):
+        L = TC.known_launches("encoder", rows)
+        assert [f for f, *_ in L] == ["nn"] * 20 + ["nt"] * 19 + ["tn"] * 20
+        assert L[0] == ("nn", rows, 64, 1024, 5) and L[39] == ("tn", 160, 64, 1, 1024 * (rows // 32))      # the K = 160 stem and its weight gradient
+        assert all(M % 32 == 0 for _, M, *_ in L)
+        assert ("nt", rows, 64, 256, 0) in L                                                                # VC_P2's data gradient never splits
+    seen = set()
+    for name, (n, cfgs) in CASES.items():
+        for cfg in cfgs:
+            must, never = TC.expected("encoder", -(-n // 32) * 32, cfg)
+            assert must | never == set(TC.KERNELS) | {"fused", "reduce"}          # exact for this tape
+            seen |= must
+    assert seen == set(TC.KERNELS) | {"fused", "reduce"}, sorted((set(TC.KERNELS) | {"fused", "reduce"}) - seen)
+    at = lambda rows, cfg: TC.expected("encoder", rows, cfg)[0]          # noqa: E731
+    assert at(64, "t32") == {"nn_32", "nt_32", "tn_32", "fused"} == at(64, "deep") == at(64, "shallow")
+    assert at(64, "t64") == {"nn_64", "nt_64", "tn_64", "fused"}
+    assert at(64, "t128") == at(64, "t32") | {"tn_128"} and at(160, "t128") == at(64, "t128") | {"nn_128", "nt_128"}
+    assert {"nn_32_ki2", "nt_32_ki2", "tn_32_ki2"} <= at(64, "ki2_32") and {"nn_64_ki2", "nt_64_ki2", "tn_64_ki2"} <= at(64, "ki2_64")
+    assert at(64, "nosplit") == {"nn_32", "nt_32", "tn_32"} and at(64, "reduce") == {"nn_32", "nt_32", "tn_32", "reduce"}
+    # small frame counts split K in the forward and data-gradient GEMMs of the 4x4 and 2x2 stages; workload frame counts do not
+    opt = TC.options("t32")
+    split = lambda rows: {(f, N) for f, M, N, nb, st in TC.known_launches("encoder", rows) if f != "tn" and TC.gemm_shape(M, N, nb, st, opt)[1] > 1}      # noqa: E731
+    assert ("nn", 512) in split(64) and ("nt", 256) in split(64) and not split(512) and not split(1024)
+    for n, cfg in WORKLOAD:
+        assert "fused" in at(n, cfg) and "reduce" not in at(n, cfg)               # (the weight gradients still split)
+    # fused_part_bytes: ks blocks of one tile per output tile; 0 beyond 65536 tiles or 2^31 bytes
+    assert TC.fused_part_bytes(64, 512, 4, 32, 8) == 8 * 2 * 4 * 8 * 32 * 64 * 4
+    assert TC.fused_part_bytes(160, 256, 8, 128, 8) == 2 * 2 * 8 * 8 * 128 * 128 * 4
+    assert TC.fused_part_bytes(1024, 64, 4096, 32, 2) == 0 and TC.fused_part_bytes(1024, 64, 2048, 32, 2) == 65536 * 2 * 32 * 64 * 4
+    assert TC.fused_part_bytes(1024, 64, 2048, 32, 4) == 0

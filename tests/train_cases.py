@@ -1,6 +1,7 @@
-"""Fixtures of the training-GEMM launch-shape tests (tests/test_hip_train_shapes.py on the GPU, the conditions they rest on in
-tests/test_train_cpu.py): the option sets that reach each of the 15 instantiations of csrc/train.hip's kernel family, the `gemm_shape` rule
-restated, the batches, the IDM row selection and the per-entry gradient rule.  Test infrastructure, NOT a product path."""
+"""Fixtures of the training-GEMM launch-shape tests (tests/test_hip_train_shapes.py and tests/test_hip_resnet_train_shapes.py on the GPU, the
+conditions they rest on in tests/test_train_cpu.py): the option sets that reach each of the 15 instantiations of csrc/train.hip's kernel
+family, the `gemm_shape` and `fused_part_bytes` rules restated, the launches of the ResNet-18 encoder's tape restated from its convolution
+tables, the batches, the IDM row selection and the per-entry gradient rule.  Test infrastructure, NOT a product path."""
 from collections import OrderedDict
 
 import numpy as np
@@ -68,10 +69,95 @@ def kernel_of(form, tile, ki):
     return f"{form}_{tile}" + ("_ki2" if ki == 2 else "")
 
 
+CNT_TILES = 1 << 16                        # csrc/train.hip: tickets of one launch
+
+
+def fused_part_bytes(M, N, nbatch, tile, ks):
+    """csrc/train.hip fused_part_bytes, restated: the workspace of the in-launch split-K finish (ks blocks of one tile per output tile), or 0
+    where the launch cannot use it (more tiles than tickets, offsets beyond 2^31) and falls back to the separate reduce launch."""
+    cdiv = lambda a, b: -(-a // b)          # noqa: E731
+    tiles = cdiv(N, 128) * cdiv(M, 128) * nbatch if tile == 128 else cdiv(N, 64) * cdiv(M, tile) * nbatch
+    size = tiles * ks * (128 * 128 if tile == 128 else tile * 64) * 4
+    return size if tiles <= CNT_TILES and size < 1 << 31 else 0
+
+
+# ---- csrc/vae_train.hpp vae_tap_in / plan_conv2d, restated for the modes the encoder's tape uses ------------------------------------------------
+VC_S1, VC_S2, VC_P1, VC_P2 = 0, 1, 3, 4   # 3x3 pad 1, 3x3 stride 2 pad (0, 1), 1x1, 1x1 stride 2
+
+
+def tap_in(mode, Sin, Sout, po, j):
+    """Input pixel that tap j of output pixel po reads, or -1 (padding)."""
+    y, x, dy, dx = po // Sout, po % Sout, j // 3, j % 3
+    if mode == VC_S1:
+        iy, ix = y + dy - 1, x + dx - 1
+    elif mode == VC_S2:
+        iy, ix = 2 * y + dy, 2 * x + dx
+    elif mode == VC_P2:
+        return 2 * y * Sin + 2 * x if j == 0 else -1
+    elif mode == VC_P1:
+        return po if j == 0 else -1
+    else:
+        raise ValueError(mode)
+    return -1 if iy < 0 or ix < 0 or iy >= Sin or ix >= Sin else iy * Sin + ix
+
+
+def conv_plan(mode, Sin, Sout):
+    """-> dict(f_nb, f_minseg, d_nb, d_minseg, w_nb, w_minseg): batches of the forward / data-gradient / weight-gradient launch of one 2-D
+    convolution and the fewest segments any of them has.  Forward: one batch per output pixel, a segment per live tap; data gradient: one
+    batch per input pixel, a segment per (output pixel, tap) that reads it -- none at the pixels a stride-2 1x1 skips; weight gradient: one
+    batch per tap that is live somewhere, a segment per output pixel it is live at."""
+    ntaps = 1 if mode in (VC_P1, VC_P2) else 9
+    Tin, Tout = Sin * Sin, Sout * Sout
+    live = [[tap_in(mode, Sin, Sout, to, j) for j in range(ntaps)] for to in range(Tout)]
+    hits = [0] * Tin
+    for row in live:
+        for ti in row:
+            if ti >= 0:
+                hits[ti] += 1
+    per_tap = [sum(1 for to in range(Tout) if live[to][j] >= 0) for j in range(ntaps)]
+    per_tap = [n for n in per_tap if n > 0]
+    return dict(f_nb=Tout, f_minseg=min(sum(1 for ti in row if ti >= 0) for row in live), d_nb=Tin, d_minseg=min(hits),
+                w_nb=len(per_tap), w_minseg=min(per_tap))
+
+
+def encoder_convs():
+    """The 20 convolutions of csrc/resnet_train.hpp's tape as (mode, Sin, Sout, cin, cout, has a data gradient): the stem as a 1x1 over gathered
+    patches (K = 147 padded to 160; the image is no parameter) and, per ResNetBlock (rnt_block), Conv_0, Conv_1 and the projection."""
+    out = [(VC_P1, 32, 32, 160, 64, False)]
+    S = 16
+    for b in range(8):
+        stage = b // 2
+        cout, cin = 64 << stage, 64 if b == 0 else 64 << ((b - 1) // 2)
+        stride = 2 if stage > 0 and b % 2 == 0 else 1
+        So = S // stride
+        out.append((VC_S1 if stride == 1 else VC_S2, S, So, cin, cout, True))
+        out.append((VC_S1, So, So, cout, cout, True))
+        if stride != 1 or cin != cout:
+            out.append((VC_P2, S, So, cin, cout, True))
+        S = So
+    return out
+
+
+def encoder_launches(rows):
+    """The 59 GEMM launches of one encoder forward + backward over `rows` padded frames (conv_fwd_add / conv_dgrad / conv_wgrad): 20 forward,
+    19 data-gradient, 20 weight-gradient, as (form, M, N, batches, fewest K steps of a batch)."""
+    fwd, dgrad, wgrad = [], [], []
+    for mode, Sin, Sout, cin, cout, has_d in encoder_convs():
+        p = conv_plan(mode, Sin, Sout)
+        fwd.append(("nn", rows, cout, p["f_nb"], p["f_minseg"] * (cin // 32)))
+        if has_d:
+            dgrad.append(("nt", rows, cin, p["d_nb"], p["d_minseg"] * (cout // 32)))
+        wgrad.append(("tn", cin, cout, p["w_nb"], p["w_minseg"] * (rows // 32)))
+    return fwd + dgrad + wgrad
+
+
 def known_launches(model, rows):
     """Launches every gradient call of `model` over `rows` (padded) rows makes, as (form, M, N, batches, fewest K steps of a batch): the Dense
     layers 256 -> 1024 -> 256 both tapes have (the planner's step encoder, the IDM's residual blocks: csrc/train.hip dense_fwd / dense_dgrad /
-    dense_wgrad) and, for the planner, the 256 -> 256 k = 5 convolution at 8 positions (three live taps at the ends; taps +-2 meet 6 positions)."""
+    dense_wgrad) and, for the planner, the 256 -> 256 k = 5 convolution at 8 positions (three live taps at the ends; taps +-2 meet 6 positions).
+    "encoder": every GEMM launch of the ResNet-18 tape (encoder_launches), forward and backward call together."""
+    if model == "encoder":
+        return encoder_launches(rows)
     out = [("nn", rows, 1024, 1, 8), ("nn", rows, 256, 1, 32), ("nt", rows, 1024, 1, 8), ("tn", 1024, 256, 1, rows // 32), ("tn", 256, 1024, 1, rows // 32)]
     if model == "planner":
         out += [("nn", rows, 256, 8, 3 * 8), ("nt", rows, 256, 8, 3 * 8), ("tn", 256, 256, 5, 6 * (rows // 32))]
@@ -80,15 +166,16 @@ def known_launches(model, rows):
 
 def expected(model, rows, name):
     """-> (counters that must rise, counters that must stay) for one gradient call under configuration `name`: the table of the module's
-    docstring where the batch allows it, else what the restated rule gives for the launches known_launches lists."""
+    docstring where the batch allows it, else what the restated rule gives for the launches known_launches lists.  A launch that splits K
+    finishes inside the launch where train_fuse_reduce is set and fused_part_bytes allows it, else through the reduce launch."""
     opt = options(name)
-    must, fused = set(), False
+    must, finishes = set(), set()
     for form, M, N, nb, steps in known_launches(model, rows):
         tile, ks, ki = gemm_shape(M, N, nb, steps, opt)
         must.add(kernel_of(form, tile, ki))
-        fused |= ks > 1
-    if fused:
-        must.add("fused" if opt["train_fuse_reduce"] else "reduce")
+        if ks > 1:
+            finishes.add("fused" if opt["train_fuse_reduce"] and fused_part_bytes(M, N, nb, tile, ks) > 0 else "reduce")
+    must |= finishes
     never = set()
     if not opt["train_big"]:
         never |= {k for k in KERNELS if k.endswith("_128")}
@@ -100,7 +187,12 @@ def expected(model, rows, name):
         never |= {k for k in KERNELS if "_64" in k}
     if not opt["train_split"]:
         never |= {"fused", "reduce"}
-    never.add("reduce" if opt["train_fuse_reduce"] else "fused")
+    if model == "encoder":                                  # known_launches lists every launch of this tape
+        never |= (set(KERNELS) | {"fused", "reduce"}) - must
+    elif not opt["train_fuse_reduce"]:
+        never.add("fused")
+    elif "reduce" not in finishes:
+        never.add("reduce")
     assert not (must & never), (model, rows, name, must & never)
     return must, never
 
