@@ -3,7 +3,7 @@
 //
 // Included by train.hip inside its anonymous namespace, after vae_train.hpp: an encoder slot is module bit 8 << slot of the same Trainer (flat
 // arenas, Adam + EMA in one launch, read / write / publish by Flax path), its convolutions run through the VAE tape's 2-D launch tables
-// (plan_conv2d: rows = samples, z = pixel) on the exact-fp32 segmented GEMM.  The sixteen 3x3 convolutions are VC_S1 / VC_S2, the three conv_proj
+// (plan_2d of train_tables.hpp: rows = samples, z = pixel) on the exact-fp32 segmented GEMM.  The sixteen 3x3 convolutions are VC_S1 / VC_S2, the three conv_proj
 // the stride-2 1x1 table VC_P2.  Nothing in this network has a bias, so the tape has no column sums besides the norms' scale / bias partials.
 //
 // Stem (7x7 stride 2 pad 3, 3 -> 64 channels).  Each output pixel's 147-value patch is gathered once, in the Flax leaf's own flattening
@@ -311,9 +311,9 @@ struct RntSave {                    // what a ResNetBlock keeps for its backward
 
 // One slot's tape.  backward = false: the forward is enqueued (the dry walk goes on through the backward, to size the workspace for both);
 // backward = true: the forward is walked without launching (the same bump allocation: the same pointers), the backward is enqueued.
-int encoder_tape(Ctx& c, int slot, const float* img, float* feat_out, const float* dfeat, int N, bool backward) {
+int encoder_tape(Ctx& c, const float* img, float* feat_out, const float* dfeat, int N, bool backward) {
   Trainer& t = *c.t;
-  Module& m = t.enc[slot];
+  Module& m = *c.M;
   const bool real = !c.dry;
   const int Bp = rup(N, RP), CL = RNT_F << 3;                 // CL: channels of the last feature map (512)
   c.L->ws_used = 0;
@@ -333,7 +333,7 @@ int encoder_tape(Ctx& c, int slot, const float* img, float* feat_out, const floa
   float* c0 = take(n0);
   float* a0 = take(n0);
   float* st0 = take((size_t)Bp * RNT_G * 2);
-  RNT_TRY(conv_fwd_add(c, stem, patches, P("conv_init/kernel"), nullptr, nullptr, c0, Bp));
+  RNT_TRY(conv_fwd(c, stem, patches, P("conv_init/kernel"), nullptr, nullptr, c0, Bp));
   RNT_TRY(rnt_gn_fwd(c, c0, P("norm_init/scale"), P("norm_init/bias"), nullptr, nullptr, nullptr, a0, st0, nullptr, Bp, 32 * 32, RNT_F, 0));
   const long long npool = (long long)Bp * 16 * 16 * RNT_F;
   float* p0 = take((size_t)npool);
@@ -352,13 +352,13 @@ int encoder_tape(Ctx& c, int slot, const float* img, float* feat_out, const floa
     B.cv2 = &vae_plan(t, VC_S1, B.S, B.S, C, C);
     B.c1 = take(ny); B.a1 = take(ny); B.c2 = take(ny); B.y = take(ny);
     B.st1 = take((size_t)Bp * RNT_G * 2); B.st2 = take((size_t)Bp * RNT_G * 2);
-    RNT_TRY(conv_fwd_add(c, *B.cv1, x, P(p + "/Conv_0/kernel"), nullptr, nullptr, B.c1, Bp));
+    RNT_TRY(conv_fwd(c, *B.cv1, x, P(p + "/Conv_0/kernel"), nullptr, nullptr, B.c1, Bp));
     RNT_TRY(rnt_gn_fwd(c, B.c1, P(p + "/MyGroupNorm_0/scale"), P(p + "/MyGroupNorm_0/bias"), nullptr, nullptr, nullptr, B.a1, B.st1, nullptr, Bp, T, C, 0));
-    RNT_TRY(conv_fwd_add(c, *B.cv2, B.a1, P(p + "/Conv_1/kernel"), nullptr, nullptr, B.c2, Bp));
+    RNT_TRY(conv_fwd(c, *B.cv2, B.a1, P(p + "/Conv_1/kernel"), nullptr, nullptr, B.c2, Bp));
     if (B.d.proj) {
       B.cvp = &vae_plan(t, VC_P2, B.Sin, B.S, B.d.cin, C);
       B.pr = take(ny); B.stp = take((size_t)Bp * RNT_G * 2);
-      RNT_TRY(conv_fwd_add(c, *B.cvp, x, P(p + "/conv_proj/kernel"), nullptr, nullptr, B.pr, Bp));
+      RNT_TRY(conv_fwd(c, *B.cvp, x, P(p + "/conv_proj/kernel"), nullptr, nullptr, B.pr, Bp));
       RNT_TRY(rnt_gn_fwd(c, B.c2, P(p + "/MyGroupNorm_1/scale"), P(p + "/MyGroupNorm_1/bias"), B.pr, P(p + "/norm_proj/scale"), P(p + "/norm_proj/bias"),
                          B.y, B.st2, B.stp, Bp, T, C, 2));
     } else {

@@ -23,6 +23,7 @@
 // counts that are not multiples of 32 (D, A, the FiLM / IDM input widths) are zero-padded in the arena: padded entries receive exactly
 // zero gradient and stay zero under Adam.  Nothing here uses atomics: every number is bit-reproducible run to run.
 #include "engine.hpp"
+#include "train_tables.hpp"      // GemmSeg, GemmBatch, ConvPlan and the builder of the convolutions' launch tables (host only)
 
 #include <cmath>
 #include <cstring>
@@ -33,6 +34,9 @@
 namespace ldp {
 namespace {
 
+using namespace train_tables;
+using train_tables::ConvPlan;         // (the training tables' plan, not the sampling path's ldp::ConvPlan of tconv.hpp)
+
 constexpr int RP = 32;                 // row / channel padding granule
 
 inline int rup(int x, int m) { return (x + m - 1) / m * m; }
@@ -40,9 +44,6 @@ inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 // =====================================================================================================================
 // segmented-K batched GEMM on the exact-fp32 MFMA
 // =====================================================================================================================
-struct GemmSeg { long long a_off, b_off; };
-struct GemmBatch { long long c_off; int seg_begin, seg_end; long long bias_off = 0; };      // bias_off: this batch's bias row = GemmArgs::bias + bias_off
-
 struct GemmArgs {
   const float* A; const float* B; float* C;
   const float* bias;            // (N) or nullptr
@@ -1113,12 +1114,6 @@ struct Module {
   float* g(const std::string& path) const { return G.f() + leaf(path).off; }
 };
 
-struct ConvPlan {                  // launch tables of one convolution (device indices into Trainer::d_segs / d_batches)
-  int mode = MODE_K5, Tin = 0, Tout = 0, cin = 0, cout = 0, ntaps = 0;
-  int f_b0 = 0, f_nb = 0, d_b0 = 0, d_nb = 0, w_b0 = 0, w_nb = 0;      // first batch / batch count of the forward, dgrad, wgrad launches
-  int f_minseg = 0, d_minseg = 0, w_minseg = 0;                       // fewest segments any batch of the forward / dgrad / wgrad launch has (split-K sizing)
-};
-
 // What one module's tape writes while it runs: the bump-allocated activations, the split-K / column-sum workspaces of its main and of its side stream
 // (fork / join below), the side stream itself.  One per module, so that the planner's and the IDM's tapes can be in flight together.
 struct Lane {
@@ -1147,26 +1142,32 @@ struct ProjPlan { int f_b0 = 0, f_nb = 0, f_minseg = 0, d_b0 = 0, d_nb = 0, d_mi
 constexpr int RNT_SLOTS = 4;       // ResNet image encoders per handle (weight modules encoder0 .. encoder3, module bits 8 << slot)
 constexpr int32_t MOD_ALL = 7 | (15 << 3);
 #define LDP_MODS_MSG "modules must be a mask of 1 (planner), 2 (idm), 4 (vae) and 8 << slot (encoder0 .. encoder3)"
-inline int enc_slot_of(int32_t bit) { return bit == 8 ? 0 : bit == 16 ? 1 : bit == 32 ? 2 : bit == 64 ? 3 : -1; }
+
+// Everything the trainer keeps per module, in one place.  The lane is the module's own, so that nothing mutable is shared between tapes: the
+// planner's, the IDM's and the VAE's may be enqueued on different streams, and an encoder slot's forward activations live until its backward
+// while other slots' tapes run.
+struct ModSlot {
+  int32_t bit;                     // its bit in a `modules` mask
+  const char* prefix;              // of its leaves in the handle's weight store
+  Module m;
+  Lane lane;
+  bool described = false;          // planner and IDM by ensure_trainer; the VAE and an encoder by the first ldp_train_init that asks for their bit
+};
+enum { MOD_PLANNER = 0, MOD_IDM = 1, MOD_VAE = 2, MOD_ENC0 = 3, N_MODS = MOD_ENC0 + RNT_SLOTS };
 
 struct Trainer {
   int D = 0, DP = 0, A = 0, AP = 0, G = 0, T = 0, L = 0, E = 0, CP = 0;       // CP = padded width of [temb | cond]
   int IH = 0, INP = 0, NB = 0, TD = 0;                                           // IDM hidden, padded input width, blocks, time dim
   std::vector<int> dims, Tl;
-  Module pl, idm;
-  Module vae;                      // StableVAE (vae_train.hpp): described by the first ldp_train_init that asks for bit 4
-  bool vae_described = false;
-  Module enc[RNT_SLOTS];           // the ResNet-18 image encoders (resnet_train.hpp): described by the first ldp_train_init that asks for their bit
-  bool enc_described[RNT_SLOTS] = {false, false, false, false};
+  ModSlot mods[N_MODS] = {{1, "planner/"}, {2, "idm/"}, {4, "vae/"},           // vae: StableVAE (vae_train.hpp)
+                          {8, "encoder0/"}, {16, "encoder1/"}, {32, "encoder2/"}, {64, "encoder3/"}};      // the ResNet-18 image encoders (resnet_train.hpp)
   int enc_fwd_n[RNT_SLOTS] = {0, 0, 0, 0};      // frames of the slot's last ldp_train_encoder_forward (0: none its backward could use)
-  std::map<std::string, ConvPlan> vconvs;      // its 2-D convolutions' tables, built on the first call for a frame size
-  bool tables_dirty = false;       // h_segs / h_batches grew since the last upload
   // launch tables
-  std::vector<GemmSeg> h_segs;
-  std::vector<GemmBatch> h_batches;
+  LaunchTables tab;
+  bool tables_dirty = false;       // tab grew since the last upload
   DevBuf d_segs, d_batches;
-  int plan_B = 0;                  // the batch the conv tables were built for (offsets do not depend on B: built once)
-  std::map<std::string, ConvPlan> convs;
+  std::map<std::string, ConvPlan> convs;       // the U-Net's convolutions, built with the trainer (a planner-only handle never re-uploads its tables)
+  std::map<std::string, ConvPlan> vconvs;      // the 2-D convolutions of the VAE and the encoders, built on the first call for a frame size
   std::map<int, ProjPlan> projs;          // block -> the grouped launches of its two input convolutions (plan_proj)
   int dense_batch = 0;             // a one-segment batch with zero offsets (plain GEMMs)
   // The FiLM Dense layers of all residual blocks of one width read the same conditioning vector: one batched launch per width for the forward
@@ -1175,118 +1176,57 @@ struct Trainer {
   struct FilmGroup { int C2 = 0; std::vector<int> blocks; int f_b0 = 0, w_b0 = 0, d_b0 = 0; };
   std::vector<FilmGroup> film;
   std::vector<std::pair<int, int>> film_of;      // block -> (group, slot)
-  // tables and workspaces
   DevBuf sintab_p, sintab_i;       // (n_train, E) sin|cos and (n_train, TD) cos|sin
-  Lane lane[3];                    // [0] the planner's tape, [1] the IDM's, [2] the VAE's: nothing mutable is shared, they may be enqueued on different streams
-  Lane enc_lane[RNT_SLOTS];        // one per encoder slot: a slot's forward activations live until its backward, several slots' tapes at once
+  // the slot of a module bit, or nullptr where `bit` is not exactly one module's
+  ModSlot* slot_of(int32_t bit) {
+    for (ModSlot& s : mods)
+      if (s.bit == bit) return &s;
+    return nullptr;
+  }
 };
 
 Trainer* trainer(ldp_handle* h) { return static_cast<Trainer*>(h->train); }
 
-// ---- tap sets (csrc/tconv.hpp's, restated for the launch tables) -------------------------------------------------------------------
-int ntaps_of(int mode) { return mode == MODE_K5 ? 5 : mode == MODE_DOWN ? 3 : mode == MODE_UP ? 4 : 1; }
-// input position of tap j at output position to, or -1 when the tap does not contribute there
-int tap_in(int mode, int to, int j) {
-  switch (mode) {
-    case MODE_K5: return to + j - 2;
-    case MODE_DOWN: return 2 * to + j;                                       // XLA SAME on an even length: pads (0, 1)
-    case MODE_UP: {                                                          // out[2q] = x[q-1] K0 + x[q] K2; out[2q+1] = x[q] K1 + x[q+1] K3
-      const int q = to >> 1;
-      if ((to & 1) == 0) return j == 0 ? q - 1 : j == 2 ? q : -1;
-      return j == 1 ? q : j == 3 ? q + 1 : -1;
-    }
-    default: return to;
-  }
-}
-
-ConvPlan plan_conv(Trainer& t, int mode, int Tin, int Tout, int cin, int cout) {
-  ConvPlan c;
-  c.mode = mode; c.Tin = Tin; c.Tout = Tout; c.cin = cin; c.cout = cout; c.ntaps = ntaps_of(mode);
-  const long long wtap = (long long)cin * cout;
-  // forward: one batch per output position
-  c.f_b0 = (int)t.h_batches.size();
-  for (int to = 0; to < Tout; ++to) {
-    GemmBatch b{(long long)to * cout, (int)t.h_segs.size(), 0};
-    for (int j = 0; j < c.ntaps; ++j) {
-      const int ti = tap_in(mode, to, j);
-      if (ti >= 0 && ti < Tin) t.h_segs.push_back(GemmSeg{(long long)ti * cin, j * wtap});
-    }
-    b.seg_end = (int)t.h_segs.size();
-    c.f_minseg = to == 0 ? b.seg_end - b.seg_begin : std::min(c.f_minseg, b.seg_end - b.seg_begin);
-    t.h_batches.push_back(b);
-  }
-  c.f_nb = Tout;
-  // dgrad: one batch per input position; A = dY at the output positions that read it, B = W[j] read transposed
-  c.d_b0 = (int)t.h_batches.size();
-  for (int ti = 0; ti < Tin; ++ti) {
-    GemmBatch b{(long long)ti * cin, (int)t.h_segs.size(), 0};
-    for (int to = 0; to < Tout; ++to)
-      for (int j = 0; j < c.ntaps; ++j)
-        if (tap_in(mode, to, j) == ti) t.h_segs.push_back(GemmSeg{(long long)to * cout, j * wtap});
-    b.seg_end = (int)t.h_segs.size();
-    c.d_minseg = ti == 0 ? b.seg_end - b.seg_begin : std::min(c.d_minseg, b.seg_end - b.seg_begin);
-    t.h_batches.push_back(b);
-  }
-  c.d_nb = Tin;
-  // wgrad: one batch per tap that is live somewhere; A = X at t_in (transposed read), B = dY at t_out
-  c.w_b0 = (int)t.h_batches.size();
-  for (int j = 0; j < c.ntaps; ++j) {
-    GemmBatch b{j * wtap, (int)t.h_segs.size(), 0};
-    for (int to = 0; to < Tout; ++to) {
-      const int ti = tap_in(mode, to, j);
-      if (ti >= 0 && ti < Tin) t.h_segs.push_back(GemmSeg{(long long)ti * cin, (long long)to * cout});
-    }
-    b.seg_end = (int)t.h_segs.size();
-    if (b.seg_end > b.seg_begin) {
-      c.w_minseg = c.w_nb == 0 ? b.seg_end - b.seg_begin : std::min(c.w_minseg, b.seg_end - b.seg_begin);
-      t.h_batches.push_back(b);
-      ++c.w_nb;
-    }
-    else t.h_segs.resize(b.seg_begin);
-  }
-  return c;
-}
+static_assert(CONV1_K5 == MODE_K5 && CONV1_DOWN == MODE_DOWN && CONV1_UP == MODE_UP && CONV1_P1 == MODE_P1, "train_tables.hpp numbers the 1-D tap sets as tconv.hpp does");
 
 // A residual block with a 1 x 1 projection runs TWO convolutions over its input (k = 5 -> GroupNorm, 1 x 1 -> the residual) and sums two data
 // gradients into it.  One launch each: forward = the k = 5 batches plus one batch per position for the projection (second output base); data gradient
 // = the k = 5 segments of an input position plus one segment that reads the projection's dY (second A base).  Offsets into the weights are arena offsets.
-ProjPlan plan_proj(Trainer& t, int T, int cin, int cout, long long w5, long long b5, long long w1, long long b1) {
+ProjPlan plan_proj(LaunchTables& tb, int T, int cin, int cout, long long w5, long long b5, long long w1, long long b1) {
   ProjPlan p;
-  const long long wtap = (long long)cin * cout;
-  p.f_b0 = (int)t.h_batches.size();
+  const TapWalk k5 = walk_taps(T, T, cin, cout, 5, [T](int to, int j) { return tap_1d(MODE_K5, T, to, j); });
+  auto k5_segs = [&](const std::vector<GemmSeg>& list) {      // the walk's segments, their weights at the arena offset of the k = 5 kernel
+    for (const GemmSeg& s : list) tb.segs.push_back(GemmSeg{s.a_off, w5 + s.b_off});
+  };
+  p.f_b0 = (int)tb.batches.size();
   p.f_minseg = 1;
   for (int to = 0; to < T; ++to) {
-    GemmBatch b{(long long)to * cout, (int)t.h_segs.size(), 0, b5};
-    for (int j = 0; j < 5; ++j) {
-      const int ti = tap_in(MODE_K5, to, j);
-      if (ti >= 0 && ti < T) t.h_segs.push_back(GemmSeg{(long long)ti * cin, w5 + j * wtap});
-    }
-    b.seg_end = (int)t.h_segs.size();
-    t.h_batches.push_back(b);
+    GemmBatch b{(long long)to * cout, (int)tb.segs.size(), 0, b5};
+    k5_segs(k5.fwd[to]);
+    b.seg_end = (int)tb.segs.size();
+    tb.batches.push_back(b);
   }
   for (int to = 0; to < T; ++to) {
-    GemmBatch b{GEMM_ALT | ((long long)to * cout), (int)t.h_segs.size(), (int)t.h_segs.size() + 1, b1};
-    t.h_segs.push_back(GemmSeg{(long long)to * cin, w1});
-    t.h_batches.push_back(b);
+    GemmBatch b{GEMM_ALT | ((long long)to * cout), (int)tb.segs.size(), (int)tb.segs.size() + 1, b1};
+    tb.segs.push_back(GemmSeg{(long long)to * cin, w1});
+    tb.batches.push_back(b);
   }
   p.f_nb = 2 * T;
-  p.d_b0 = (int)t.h_batches.size();
+  p.d_b0 = (int)tb.batches.size();
   for (int ti = 0; ti < T; ++ti) {
-    GemmBatch b{(long long)ti * cin, (int)t.h_segs.size(), 0, 0};
-    for (int to = 0; to < T; ++to)
-      for (int j = 0; j < 5; ++j)
-        if (tap_in(MODE_K5, to, j) == ti) t.h_segs.push_back(GemmSeg{(long long)to * cout, w5 + j * wtap});
-    t.h_segs.push_back(GemmSeg{GEMM_ALT | ((long long)ti * cout), w1});
-    b.seg_end = (int)t.h_segs.size();
+    GemmBatch b{(long long)ti * cin, (int)tb.segs.size(), 0, 0};
+    k5_segs(k5.dgrad[ti]);
+    tb.segs.push_back(GemmSeg{GEMM_ALT | ((long long)ti * cout), w1});
+    b.seg_end = (int)tb.segs.size();
     p.d_minseg = ti == 0 ? b.seg_end - b.seg_begin : std::min(p.d_minseg, b.seg_end - b.seg_begin);
-    t.h_batches.push_back(b);
+    tb.batches.push_back(b);
   }
   p.d_nb = T;
   return p;
 }
 
 struct Ctx {                        // one enqueue; dry = walk the tape only to size the workspace (nothing is launched); side = on the trainer's side stream
-  ldp_handle* h; Trainer* t; Lane* L; hipStream_t s; bool dry; int side = 0;      // side: 0 the caller's stream, k > 0 the lane's side stream k - 1
+  ldp_handle* h; Trainer* t; Module* M; Lane* L; hipStream_t s; bool dry; int side = 0;      // M, L: the slot's; side: 0 the caller's stream, k > 0 the lane's side stream k - 1
   const GemmSeg* segs() const { return t->d_segs.as<GemmSeg>(); }
   const GemmBatch* batches() const { return t->d_batches.as<GemmBatch>(); }
 };
@@ -1353,16 +1293,16 @@ int run_gemm(const Ctx& c, GemmForm f, const GemmArgs& g, int nbatch, int min_st
     const GemmShape sh = gemm_shape(g, nbatch, min_steps, tn, true);
     const long long b0 = g.batches - c.batches();
     long long steps = 0;
-    for (int b = 0; b < nbatch; ++b) steps += (long long)(c.t->h_batches[b0 + b].seg_end - c.t->h_batches[b0 + b].seg_begin) * (g.K / BK);
+    for (int b = 0; b < nbatch; ++b) steps += (long long)(c.t->tab.batches[b0 + b].seg_end - c.t->tab.batches[b0 + b].seg_begin) * (g.K / BK);
     fprintf(stderr, "LDP_GEMM form=%s M=%d N=%d K=%d nb=%d steps=%lld ks=%d tile=%s gflop=%.4f\n", f == G_NN ? "NN" : f == G_NT ? "NT" : "TN", g.M, g.N, g.K, nbatch,
             steps, sh.ks * sh.ki, sh.big ? "128x128" : sh.small32 ? "32x64" : "64x64", 2.0 * g.M * g.N * BK * steps / 1e9);
   }
   return gemm_launch(f, g, nbatch, c.s, tn, min_steps, (c.side ? c.L->gemm_part2[c.side - 1] : c.L->gemm_part).f(), c_extent,
                      (c.side ? c.L->gemm_cnt2[c.side - 1] : c.L->gemm_cnt).as<unsigned int>(), c.h->stat_train_gemm);
 }
-// y (Bp, Tout, cout) = conv(x (Bp, Tin, cin)) + bias
-int conv_fwd(const Ctx& c, const ConvPlan& p, const float* x, const float* w, const float* bias, float* y, int Bp) {
-  GemmArgs g{x, w, y, bias, nullptr, c.segs(), c.batches() + p.f_b0, Bp, p.cout, p.cin, p.Tin * p.cin, p.cout, p.Tout * p.cout};
+// y (Bp, Tout, cout) = conv(x (Bp, Tin, cin)) + bias (+ add)
+int conv_fwd(const Ctx& c, const ConvPlan& p, const float* x, const float* w, const float* bias, const float* add, float* y, int Bp) {
+  GemmArgs g{x, w, y, bias, add, c.segs(), c.batches() + p.f_b0, Bp, p.cout, p.cin, p.Tin * p.cin, p.cout, p.Tout * p.cout};
   return run_gemm(c, G_NN, g, p.f_nb, p.f_minseg * (p.cin / BK), (long long)Bp * p.Tout * p.cout);
 }
 // dx (Bp, Tin, cin) = conv^T(dy) (+ add)
@@ -1460,8 +1400,7 @@ void planner_blocks(const Trainer& t, std::vector<BlockDesc>& out) {
   }
 }
 
-void describe_planner(Trainer& t) {
-  Module& m = t.pl;
+void describe_planner(const Trainer& t, Module& m) {
   const int E = t.E, cd = E + t.G;
   m.add("Dense_0/kernel", {E, 4 * E});
   m.add("Dense_0/bias", {4 * E});
@@ -1507,8 +1446,7 @@ void describe_planner(Trainer& t) {
   m.add("Conv_0/bias", {t.D}, 1, t.DP);
 }
 
-void describe_idm(Trainer& t) {
-  Module& m = t.idm;
+void describe_idm(const Trainer& t, Module& m) {
   const int H = t.IH;
   m.add("MLP_0/Dense_0/kernel", {t.TD, H});
   m.add("MLP_0/Dense_0/bias", {H});
@@ -1540,33 +1478,36 @@ int ensure_trainer(ldp_handle* h) {
   for (int l = 0; l < t->L; ++l) { t->dims.push_back(c.down_dims[l]); t->Tl.push_back(c.pred_horizon >> l); }
   t->IH = c.idm_hidden; t->NB = c.idm_blocks; t->TD = c.idm_time_dim;
   t->INP = rup(t->A + 2 * t->D + t->IH, RP);
-  describe_planner(*t);
-  describe_idm(*t);
+  Module& pl = t->mods[MOD_PLANNER].m;
+  describe_planner(*t, pl);
+  describe_idm(*t, t->mods[MOD_IDM].m);
+  t->mods[MOD_PLANNER].described = t->mods[MOD_IDM].described = true;
   // launch tables: the plain-GEMM batch first, then every convolution of the U-Net
-  t->h_segs.push_back(GemmSeg{0, 0});
-  t->h_batches.push_back(GemmBatch{0, 0, 1});
+  LaunchTables& tb = t->tab;
+  tb.segs.push_back(GemmSeg{0, 0});
+  tb.batches.push_back(GemmBatch{0, 0, 1});
   t->dense_batch = 0;
   std::vector<BlockDesc> bs;
   planner_blocks(*t, bs);
   for (size_t i = 0; i < bs.size(); ++i) {
     const std::string p = "b" + std::to_string(i);
-    t->convs[p + "c0"] = plan_conv(*t, MODE_K5, bs[i].T, bs[i].T, rup(bs[i].cin, RP), bs[i].cout);
-    t->convs[p + "c1"] = plan_conv(*t, MODE_K5, bs[i].T, bs[i].T, bs[i].cout, bs[i].cout);
-    if (bs[i].proj) t->convs[p + "r"] = plan_conv(*t, MODE_P1, bs[i].T, bs[i].T, rup(bs[i].cin, RP), bs[i].cout);
+    t->convs[p + "c0"] = plan_1d(tb, MODE_K5, bs[i].T, bs[i].T, rup(bs[i].cin, RP), bs[i].cout);
+    t->convs[p + "c1"] = plan_1d(tb, MODE_K5, bs[i].T, bs[i].T, bs[i].cout, bs[i].cout);
+    if (bs[i].proj) t->convs[p + "r"] = plan_1d(tb, MODE_P1, bs[i].T, bs[i].T, rup(bs[i].cin, RP), bs[i].cout);
   }
-  for (int l = 0; l + 1 < t->L; ++l) t->convs["down" + std::to_string(l)] = plan_conv(*t, MODE_DOWN, t->Tl[l], t->Tl[l + 1], t->dims[l], t->dims[l]);
+  for (int l = 0; l + 1 < t->L; ++l) t->convs["down" + std::to_string(l)] = plan_1d(tb, MODE_DOWN, t->Tl[l], t->Tl[l + 1], t->dims[l], t->dims[l]);
   for (int i = 0; i + 1 < t->L; ++i) {
     const int lv = t->L - 1 - i;
-    t->convs["up" + std::to_string(i)] = plan_conv(*t, MODE_UP, t->Tl[lv], t->Tl[lv - 1], t->dims[lv - 1], t->dims[lv - 1]);
+    t->convs["up" + std::to_string(i)] = plan_1d(tb, MODE_UP, t->Tl[lv], t->Tl[lv - 1], t->dims[lv - 1], t->dims[lv - 1]);
   }
-  t->convs["fin"] = plan_conv(*t, MODE_K5, t->T, t->T, t->dims[0], t->dims[0]);
-  t->convs["out"] = plan_conv(*t, MODE_P1, t->T, t->T, t->dims[0], t->DP);
+  t->convs["fin"] = plan_1d(tb, MODE_K5, t->T, t->T, t->dims[0], t->dims[0]);
+  t->convs["out"] = plan_1d(tb, MODE_P1, t->T, t->T, t->dims[0], t->DP);
   for (size_t i = 0; i < bs.size(); ++i) {
     if (!bs[i].proj) continue;
     const std::string p = "ConditionalResidualBlock1D_" + std::to_string(i);
-    t->projs[(int)i] = plan_proj(*t, bs[i].T, rup(bs[i].cin, RP), bs[i].cout, (long long)t->pl.leaf(p + "/Conv1dBlock_0/Conv_0/kernel").off,
-                                 (long long)t->pl.leaf(p + "/Conv1dBlock_0/Conv_0/bias").off, (long long)t->pl.leaf(p + "/Conv_0/kernel").off,
-                                 (long long)t->pl.leaf(p + "/Conv_0/bias").off);
+    t->projs[(int)i] = plan_proj(tb, bs[i].T, rup(bs[i].cin, RP), bs[i].cout, (long long)pl.leaf(p + "/Conv1dBlock_0/Conv_0/kernel").off,
+                                 (long long)pl.leaf(p + "/Conv1dBlock_0/Conv_0/bias").off, (long long)pl.leaf(p + "/Conv_0/kernel").off,
+                                 (long long)pl.leaf(p + "/Conv_0/bias").off);
   }
   t->film_of.assign(bs.size(), {0, 0});
   for (size_t i = 0; i < bs.size(); ++i) {
@@ -1578,44 +1519,33 @@ int ensure_trainer(ldp_handle* h) {
   }
   for (Trainer::FilmGroup& fg : t->film) {
     const int nb = (int)fg.blocks.size();
-    auto woff = [&](int slot) { return (long long)t->pl.leaf("ConditionalResidualBlock1D_" + std::to_string(fg.blocks[slot]) + "/Dense_0/kernel").off; };
-    auto boff = [&](int slot) { return (long long)t->pl.leaf("ConditionalResidualBlock1D_" + std::to_string(fg.blocks[slot]) + "/Dense_0/bias").off; };
-    fg.f_b0 = (int)t->h_batches.size();
+    auto woff = [&](int slot) { return (long long)pl.leaf("ConditionalResidualBlock1D_" + std::to_string(fg.blocks[slot]) + "/Dense_0/kernel").off; };
+    auto boff = [&](int slot) { return (long long)pl.leaf("ConditionalResidualBlock1D_" + std::to_string(fg.blocks[slot]) + "/Dense_0/bias").off; };
+    fg.f_b0 = (int)tb.batches.size();
     for (int k = 0; k < nb; ++k) {
-      GemmBatch b{(long long)k * fg.C2, (int)t->h_segs.size(), (int)t->h_segs.size() + 1, boff(k)};
-      t->h_segs.push_back(GemmSeg{0, woff(k)});
-      t->h_batches.push_back(b);
+      GemmBatch b{(long long)k * fg.C2, (int)tb.segs.size(), (int)tb.segs.size() + 1, boff(k)};
+      tb.segs.push_back(GemmSeg{0, woff(k)});
+      tb.batches.push_back(b);
     }
-    fg.w_b0 = (int)t->h_batches.size();
+    fg.w_b0 = (int)tb.batches.size();
     for (int k = 0; k < nb; ++k) {
-      GemmBatch b{woff(k), (int)t->h_segs.size(), (int)t->h_segs.size() + 1, 0};
-      t->h_segs.push_back(GemmSeg{0, (long long)k * fg.C2});
-      t->h_batches.push_back(b);
+      GemmBatch b{woff(k), (int)tb.segs.size(), (int)tb.segs.size() + 1, 0};
+      tb.segs.push_back(GemmSeg{0, (long long)k * fg.C2});
+      tb.batches.push_back(b);
     }
-    fg.d_b0 = (int)t->h_batches.size();
-    GemmBatch b{0, (int)t->h_segs.size(), (int)t->h_segs.size() + nb, 0};
-    for (int k = 0; k < nb; ++k) t->h_segs.push_back(GemmSeg{(long long)k * fg.C2, woff(k)});
-    t->h_batches.push_back(b);
+    fg.d_b0 = (int)tb.batches.size();
+    GemmBatch b{0, (int)tb.segs.size(), (int)tb.segs.size() + nb, 0};
+    for (int k = 0; k < nb; ++k) tb.segs.push_back(GemmSeg{(long long)k * fg.C2, woff(k)});
+    tb.batches.push_back(b);
   }
-  int r = upload(t->d_segs, t->h_segs.data(), t->h_segs.size() * sizeof(GemmSeg), nullptr);
-  if (r == LDP_OK) r = upload(t->d_batches, t->h_batches.data(), t->h_batches.size() * sizeof(GemmBatch), nullptr);
+  int r = upload(t->d_segs, tb.segs.data(), tb.segs.size() * sizeof(GemmSeg), nullptr);
+  if (r == LDP_OK) r = upload(t->d_batches, tb.batches.data(), tb.batches.size() * sizeof(GemmBatch), nullptr);
   std::vector<float> tab;
   if (r == LDP_OK) { sinusoid_table(c.planner_train_steps, t->E, false, tab); r = upload(t->sintab_p, tab.data(), tab.size() * 4, nullptr); }
   if (r == LDP_OK) { sinusoid_table(c.idm_train_steps, t->TD, true, tab); r = upload(t->sintab_i, tab.data(), tab.size() * 4, nullptr); }
   if (r != LDP_OK) { delete t; return r; }
   h->train = t;
   return LDP_OK;
-}
-
-Module* module_of(ldp_handle* h, int32_t module, const char** prefix) {
-  Trainer* t = trainer(h);
-  if (module == 1) { if (prefix) *prefix = "planner/"; return &t->pl; }
-  if (module == 2) { if (prefix) *prefix = "idm/"; return &t->idm; }
-  if (module == 4 && t->vae_described) { if (prefix) *prefix = "vae/"; return &t->vae; }
-  static const char* const enc_prefix[RNT_SLOTS] = {"encoder0/", "encoder1/", "encoder2/", "encoder3/"};
-  const int slot = enc_slot_of(module);
-  if (slot >= 0 && t->enc_described[slot]) { if (prefix) *prefix = enc_prefix[slot]; return &t->enc[slot]; }
-  return nullptr;
 }
 
 // Flax leaf (host) <-> padded arena image (host)
@@ -1692,7 +1622,7 @@ struct BlockSave {                 // what a ConditionalResidualBlock1D keeps fo
 // ---- planner: loss + gradients (agent/ldp_agent.py:113-127; networks/diffusion_nets_v2.py:66-169) ----------------------------------
 int planner_tape(Ctx& c, const float* x0, const float* noise, const int* tdev, const float* cond, float alpha, float* loss_out, int B, float* dcond_out = nullptr) {
   Trainer& t = *c.t;
-  Module& m = t.pl;
+  Module& m = *c.M;
   const int Bp = rup(B, RP), T = t.T, DP = t.DP, E = t.E, CP = t.CP, NG = c.h->cfg.n_groups;
   std::vector<BlockDesc> bs;
   planner_blocks(t, bs);
@@ -1765,16 +1695,16 @@ int planner_tape(Ctx& c, const float* x0, const float* noise, const int* tdev, c
     } else {
       if (b.proj) {
         S.res = take(ny);
-        LDP_TRY(conv_fwd(c, t.convs[k + "r"], x, P(p + "/Conv_0/kernel"), P(p + "/Conv_0/bias"), S.res, Bp));
+        LDP_TRY(conv_fwd(c, t.convs[k + "r"], x, P(p + "/Conv_0/kernel"), P(p + "/Conv_0/bias"), nullptr, S.res, Bp));
         res = S.res;
       }
-      LDP_TRY(conv_fwd(c, t.convs[k + "c0"], x, P(p + "/Conv1dBlock_0/Conv_0/kernel"), P(p + "/Conv1dBlock_0/Conv_0/bias"), S.c0, Bp));
+      LDP_TRY(conv_fwd(c, t.convs[k + "c0"], x, P(p + "/Conv1dBlock_0/Conv_0/kernel"), P(p + "/Conv1dBlock_0/Conv_0/bias"), nullptr, S.c0, Bp));
     }
     const int fgi = t.film_of[i].first;
     if (!film_waited[fgi]) { LDP_TRY(wait_for(c, film_ready[fgi])); film_waited[fgi] = 1; }
     LDP_TRY(gn_fwd(c, S.c0, P(p + "/Conv1dBlock_0/GroupNorm_0/scale"), P(p + "/Conv1dBlock_0/GroupNorm_0/bias"),
        S.emb, (const float*)nullptr, S.f, S.st0, Bp, b.T, b.cout, NG, ldE[fgi]));
-    LDP_TRY(conv_fwd(c, t.convs[k + "c1"], S.f, P(p + "/Conv1dBlock_1/Conv_0/kernel"), P(p + "/Conv1dBlock_1/Conv_0/bias"), S.c1, Bp));
+    LDP_TRY(conv_fwd(c, t.convs[k + "c1"], S.f, P(p + "/Conv1dBlock_1/Conv_0/kernel"), P(p + "/Conv1dBlock_1/Conv_0/bias"), nullptr, S.c1, Bp));
     LDP_TRY(gn_fwd(c, S.c1, P(p + "/Conv1dBlock_1/GroupNorm_0/scale"), P(p + "/Conv1dBlock_1/GroupNorm_0/bias"),
        (const float*)nullptr, res, S.out, S.st1, Bp, b.T, b.cout, NG, 0));
     return LDP_OK;
@@ -1791,7 +1721,7 @@ int planner_tape(Ctx& c, const float* x0, const float* noise, const int* tdev, c
       const std::string p = "Downsample1d_" + std::to_string(l) + "/Conv_0";
       float* xd = take((size_t)Bp * t.Tl[l + 1] * t.dims[l]);
       down_in[l] = x;
-      LDP_TRY(conv_fwd(c, t.convs["down" + std::to_string(l)], x, P(p + "/kernel"), P(p + "/bias"), xd, Bp));
+      LDP_TRY(conv_fwd(c, t.convs["down" + std::to_string(l)], x, P(p + "/kernel"), P(p + "/bias"), nullptr, xd, Bp));
       x = xd;
     }
   }
@@ -1810,7 +1740,7 @@ int planner_tape(Ctx& c, const float* x0, const float* noise, const int* tdev, c
     const int cu = t.dims[lv - 1];
     float* xu = take((size_t)Bp * t.Tl[lv - 1] * cu);
     up_in[i] = x;
-    LDP_TRY(conv_fwd(c, t.convs["up" + std::to_string(i)], x, P(p + "/kernel"), P(p + "/bias"), xu, Bp));
+    LDP_TRY(conv_fwd(c, t.convs["up" + std::to_string(i)], x, P(p + "/kernel"), P(p + "/bias"), nullptr, xu, Bp));
     x = xu;
   }
   const int c0 = t.dims[0];
@@ -1818,11 +1748,11 @@ int planner_tape(Ctx& c, const float* x0, const float* noise, const int* tdev, c
   float* cF = take((size_t)Bp * T * c0);
   float* yF = take((size_t)Bp * T * c0);
   float* stF = take((size_t)Bp * 8 * 2);
-  LDP_TRY(conv_fwd(c, t.convs["fin"], x, P("Conv1dBlock_0/Conv_0/kernel"), P("Conv1dBlock_0/Conv_0/bias"), cF, Bp));
+  LDP_TRY(conv_fwd(c, t.convs["fin"], x, P("Conv1dBlock_0/Conv_0/kernel"), P("Conv1dBlock_0/Conv_0/bias"), nullptr, cF, Bp));
   LDP_TRY(gn_fwd(c, cF, P("Conv1dBlock_0/GroupNorm_0/scale"), P("Conv1dBlock_0/GroupNorm_0/bias"), (const float*)nullptr,
      (const float*)nullptr, yF, stF, Bp, T, c0, 8, 0));                 // the final Conv1dBlock keeps flax's default of 8 groups (networks/diffusion_nets_v2.py:162-165)
   float* pred = take((size_t)Bp * T * DP);
-  LDP_TRY(conv_fwd(c, t.convs["out"], yF, P("Conv_0/kernel"), P("Conv_0/bias"), pred, Bp));
+  LDP_TRY(conv_fwd(c, t.convs["out"], yF, P("Conv_0/kernel"), P("Conv_0/bias"), nullptr, pred, Bp));
 
   // ---- loss (agent/ldp_agent.py:124) and its gradient ---------------------------------------------------------------------------------
   float* dpred = take((size_t)Bp * T * DP);
@@ -1992,7 +1922,7 @@ int planner_tape(Ctx& c, const float* x0, const float* noise, const int* tdev, c
 // ---- IDM: loss + gradients (agent/ldp_agent.py:129-140; networks/mlp_diffusion_nets.py:8-68, networks/mlp_nets.py:49-97) -----------------
 int idm_tape(Ctx& c, const float* s_in, const float* a0, const float* noise, const int* tdev, float alpha, float* loss_out, int R) {
   Trainer& t = *c.t;
-  Module& m = t.idm;
+  Module& m = *c.M;
   const int Rp = rup(R, RP), H = t.IH, A = t.A, AP = t.AP, INP = t.INP, TD = t.TD, S2 = 2 * t.D, CO = A + S2;
   c.L->ws_used = 0;
   auto P = [&](const std::string& path) { return m.P.f() + m.leaf(path).off; };
@@ -2095,17 +2025,26 @@ int idm_tape(Ctx& c, const float* s_in, const float* a0, const float* noise, con
 #include "vae_train.hpp"
 #include "resnet_train.hpp"
 
-// size the workspace with a dry walk of the tape, then enqueue it
+// One tape on its module's lane: a dry walk (sizes the workspace and builds the conv tables the walk misses), the upload of tables that grew,
+// then the real enqueue.
 template <class F>
-int run_tape(ldp_handle* h, int lane, hipStream_t s, F&& tape) {
-  Lane& t = trainer(h)->lane[lane];
-  Ctx c{h, trainer(h), &t, s, true};
+int run_lane_tape(ldp_handle* h, ModSlot& ms, hipStream_t s, F&& tape) {
+  Trainer& tr = *trainer(h);
+  Lane& t = ms.lane;
+  Ctx c{h, &tr, &ms.m, &t, s, true};
   t.colsum_need = 0;
   t.part_need = 0;
   t.coljobs.clear();
   LDP_TRY(tape(c));
+  t.coljobs.clear();
+  if (tr.tables_dirty) {
+    LDP_HIP(hipDeviceSynchronize());                          // (the other lanes' tapes read the tables being replaced)
+    LDP_TRY(upload(tr.d_segs, tr.tab.segs.data(), tr.tab.segs.size() * sizeof(GemmSeg), nullptr));
+    LDP_TRY(upload(tr.d_batches, tr.tab.batches.data(), tr.tab.batches.size() * sizeof(GemmBatch), nullptr));
+    tr.tables_dirty = false;
+  }
   if (t.ws_used > t.ws_floats || t.colsum_need > t.colsum_tmp.bytes || t.part_need > t.gemm_part.bytes) {
-    LDP_HIP(hipStreamSynchronize(s));                          // (an earlier step may still be reading the old workspace; its side stream was joined into s)
+    LDP_HIP(hipStreamSynchronize(s));                         // (a previous call may still read the old workspace; its side streams were joined into s)
     if (t.ws_used > t.ws_floats) {
       LDP_TRY(t.ws.alloc(t.ws_used * 4));
       t.ws_floats = t.ws_used;
@@ -2122,14 +2061,25 @@ int run_tape(ldp_handle* h, int lane, hipStream_t s, F&& tape) {
   return join(c);
 }
 
-int need_module(ldp_handle* h, int32_t module, Module** out) {
+int need_trainer(ldp_handle* h) {
   if (!h) return fail(LDP_EINVAL, "null handle");
   if (!h->train) return fail(LDP_ESTATE, "ldp_train_init was not called");
-  Module* m = module_of(h, module, nullptr);
-  const bool known = module == 4 || enc_slot_of(module) >= 0;
-  if (!m) return fail(known ? LDP_ESTATE : LDP_EINVAL, known ? "ldp_train_init was not called for module %d" : "module must be 1 (planner), 2 (idm), 4 (vae) or 8 << slot (encoder0 .. encoder3), got %d", module);
-  if (!m->ready) return fail(LDP_ESTATE, "ldp_train_init was not called for module %d", module);
-  *out = m;
+  return LDP_OK;
+}
+int need_ready(ModSlot& ms) { return ms.m.ready ? LDP_OK : fail(LDP_ESTATE, "ldp_train_init was not called for module %d", ms.bit); }
+// the slot of module bit `module`, initialised
+int need_slot(ldp_handle* h, int32_t module, ModSlot** out) {
+  LDP_TRY(need_trainer(h));
+  ModSlot* ms = trainer(h)->slot_of(module);
+  if (!ms) return fail(LDP_EINVAL, "module must be 1 (planner), 2 (idm), 4 (vae) or 8 << slot (encoder0 .. encoder3), got %d", module);
+  LDP_TRY(need_ready(*ms));
+  *out = ms;
+  return LDP_OK;
+}
+int need_module(ldp_handle* h, int32_t module, Module** out) {
+  ModSlot* ms = nullptr;
+  LDP_TRY(need_slot(h, module, &ms));
+  *out = &ms->m;
   return LDP_OK;
 }
 
@@ -2153,28 +2103,28 @@ int ldp_train_init(ldp_handle* h, int32_t modules, void* stream) {
   LDP_HIP(hipSetDevice(h->cfg.device));
   LDP_TRY(ensure_trainer(h));
   LDP_HIP(hipDeviceSynchronize());                                      // (the module's lane may have work on other streams than `stream`)
-  if ((modules & 4) && !trainer(h)->vae_described) {
-    describe_vae(*trainer(h), h->cfg.vae_latent_channels);
-    trainer(h)->vae_described = true;
-  }
-  for (int s = 0; s < RNT_SLOTS; ++s) {
-    if (!(modules & (8 << s))) continue;
-    Trainer& tr = *trainer(h);
-    if (!tr.enc_described[s]) {
-      Module probe;                                                      // (a slot that lacks a leaf is refused before it is described: LDP_ESTATE, nothing changes)
-      describe_encoder(probe);
-      for (const Leaf& l : probe.leaves)
-        if (h->weights.find("encoder" + std::to_string(s) + "/" + l.path) == h->weights.end())
-          return fail(LDP_ESTATE, "weight 'encoder%d/%s' was never set", s, l.path.c_str());
-      describe_encoder(tr.enc[s]);
-      tr.enc_described[s] = true;
+  Trainer& tr = *trainer(h);
+  for (ModSlot& ms : tr.mods) {
+    if (!(modules & ms.bit)) continue;
+    const int enc = (int)(&ms - tr.mods) - MOD_ENC0;                     // its encoder slot, negative for the other modules
+    if (!ms.described) {
+      if (enc >= 0) {
+        Module probe;                                                    // (a slot that lacks a leaf is refused before it is described: LDP_ESTATE, nothing changes)
+        describe_encoder(probe);
+        for (const Leaf& l : probe.leaves)
+          if (h->weights.find(ms.prefix + l.path) == h->weights.end()) return fail(LDP_ESTATE, "weight '%s%s' was never set", ms.prefix, l.path.c_str());
+        describe_encoder(ms.m);
+      } else {
+        describe_vae(ms.m, h->cfg.vae_latent_channels);                  // (the planner and the IDM were described with the trainer)
+      }
+      ms.described = true;
     }
-    tr.enc_fwd_n[s] = 0;                                                 // (a kept forward belongs to the parameters it ran on)
+    if (enc >= 0) tr.enc_fwd_n[enc] = 0;                                 // (a kept forward belongs to the parameters it ran on)
   }
-  for (int bit = 1; bit <= (8 << (RNT_SLOTS - 1)); bit <<= 1) {
-    if (!(modules & bit)) continue;
+  for (ModSlot& ms : tr.mods) {
+    if (!(modules & ms.bit)) continue;
     {
-      Lane& t = bit >= 8 ? trainer(h)->enc_lane[enc_slot_of(bit)] : trainer(h)->lane[bit == 4 ? 2 : bit - 1];
+      Lane& t = ms.lane;
       LDP_TRY(t.gemm_cnt.alloc(CNT_TILES * 4));
       LDP_HIP(hipMemset(t.gemm_cnt.p, 0, CNT_TILES * 4));
       for (int k = 0; k < Lane::NS; ++k) {
@@ -2188,17 +2138,16 @@ int ldp_train_init(ldp_handle* h, int32_t modules, void* stream) {
         t.events.push_back(e);
       }
     }
-    const char* prefix = nullptr;
-    Module* m = module_of(h, bit, &prefix);
+    Module* m = &ms.m;
     std::vector<float> img(m->total, 0.0f);
     for (const Leaf& l : m->leaves) {
-      auto it = h->weights.find(std::string(prefix) + l.path);
-      if (it == h->weights.end()) return fail(LDP_ESTATE, "weight '%s%s' was never set", prefix, l.path.c_str());
+      auto it = h->weights.find(ms.prefix + l.path);
+      if (it == h->weights.end()) return fail(LDP_ESTATE, "weight '%s%s' was never set", ms.prefix, l.path.c_str());
       if (it->second.numel() != (int64_t)l.taps * l.rows * l.cols) {      // (numel, not the shape vector: idm_finalize re-labels Dense kernels as one-tap convolutions)
         std::string got, want;
         for (auto v : it->second.shape) got += std::to_string(v) + ",";
         for (auto v : l.shape) want += std::to_string(v) + ",";
-        return fail(LDP_EINVAL, "weight '%s%s' has shape (%s), the module expects (%s)", prefix, l.path.c_str(), got.c_str(), want.c_str());
+        return fail(LDP_EINVAL, "weight '%s%s' has shape (%s), the module expects (%s)", ms.prefix, l.path.c_str(), got.c_str(), want.c_str());
       }
       pack_leaf(l, it->second.data.data(), img.data() + l.off);
     }
@@ -2224,37 +2173,37 @@ int ldp_train_init(ldp_handle* h, int32_t modules, void* stream) {
 
 int ldp_train_planner_grad(ldp_handle* h, const float* x0, const float* noise, const int32_t* t_dev, const float* cond, float alpha,
                            float* loss_out, int32_t B, void* stream) {
-  Module* m = nullptr;
-  LDP_TRY(need_module(h, 1, &m));
+  ModSlot* ms = nullptr;
+  LDP_TRY(need_slot(h, 1, &ms));
   if (!x0 || !noise || !t_dev || !loss_out || B <= 0 || (h->cfg.global_cond_dim > 0 && !cond)) return fail(LDP_EINVAL, "bad argument");
   LDP_HIP(hipSetDevice(h->cfg.device));
-  m->gpart_fresh = false;
-  return run_tape(h, 0, (hipStream_t)stream, [&](Ctx& c) { return planner_tape(c, x0, noise, t_dev, cond, alpha, loss_out, B); });
+  ms->m.gpart_fresh = false;
+  return run_lane_tape(h, *ms, (hipStream_t)stream, [&](Ctx& c) { return planner_tape(c, x0, noise, t_dev, cond, alpha, loss_out, B); });
 }
 
 int ldp_train_planner_grad_cond(ldp_handle* h, const float* x0, const float* noise, const int32_t* t_dev, const float* cond, float alpha,
                                 float* loss_out, float* dcond_out, int32_t B, void* stream) {
-  Module* m = nullptr;
-  LDP_TRY(need_module(h, 1, &m));
+  ModSlot* ms = nullptr;
+  LDP_TRY(need_slot(h, 1, &ms));
   if (!x0 || !noise || !t_dev || !loss_out || !dcond_out || !cond || B <= 0) return fail(LDP_EINVAL, "bad argument");
   if (h->cfg.global_cond_dim <= 0) return fail(LDP_EINVAL, "ldp_train_planner_grad_cond: this handle has global_cond_dim = 0, there is no condition to differentiate");
   LDP_HIP(hipSetDevice(h->cfg.device));
-  m->gpart_fresh = false;
-  return run_tape(h, 0, (hipStream_t)stream, [&](Ctx& c) { return planner_tape(c, x0, noise, t_dev, cond, alpha, loss_out, B, dcond_out); });
+  ms->m.gpart_fresh = false;
+  return run_lane_tape(h, *ms, (hipStream_t)stream, [&](Ctx& c) { return planner_tape(c, x0, noise, t_dev, cond, alpha, loss_out, B, dcond_out); });
 }
 
 int ldp_train_encoder_forward(ldp_handle* h, int32_t slot, const float* img_nhwc, float* feat_out, int32_t N, void* stream) {
   if (!h) return fail(LDP_EINVAL, "null handle");
   if (slot < 0 || slot >= RNT_SLOTS) return fail(LDP_EINVAL, "encoder slot %d: a handle has slots 0..%d", slot, RNT_SLOTS - 1);
-  Module* m = nullptr;
-  LDP_TRY(need_module(h, 8 << slot, &m));
+  ModSlot* ms = nullptr;
+  LDP_TRY(need_slot(h, 8 << slot, &ms));
   if (!img_nhwc || !feat_out) return fail(LDP_EINVAL, "bad argument");
   if (N < 1 || N > RNT_MAX_FRAMES)
     return fail(LDP_EINVAL, "ldp_train_encoder_forward: %d frames, 1 to %d per call (the tape keeps every activation of the batch)", N, RNT_MAX_FRAMES);
   LDP_HIP(hipSetDevice(h->cfg.device));
   Trainer& tr = *trainer(h);
   tr.enc_fwd_n[slot] = 0;
-  LDP_TRY(run_lane_tape(h, tr.enc_lane[slot], (hipStream_t)stream, [&](Ctx& c) { return encoder_tape(c, slot, img_nhwc, feat_out, nullptr, N, false); }));
+  LDP_TRY(run_lane_tape(h, *ms, (hipStream_t)stream, [&](Ctx& c) { return encoder_tape(c, img_nhwc, feat_out, nullptr, N, false); }));
   tr.enc_fwd_n[slot] = N;
   return LDP_OK;
 }
@@ -2262,34 +2211,34 @@ int ldp_train_encoder_forward(ldp_handle* h, int32_t slot, const float* img_nhwc
 int ldp_train_encoder_backward(ldp_handle* h, int32_t slot, const float* dfeat, int32_t N, void* stream) {
   if (!h) return fail(LDP_EINVAL, "null handle");
   if (slot < 0 || slot >= RNT_SLOTS) return fail(LDP_EINVAL, "encoder slot %d: a handle has slots 0..%d", slot, RNT_SLOTS - 1);
-  Module* m = nullptr;
-  LDP_TRY(need_module(h, 8 << slot, &m));
+  ModSlot* ms = nullptr;
+  LDP_TRY(need_slot(h, 8 << slot, &ms));
   if (!dfeat) return fail(LDP_EINVAL, "bad argument");
   if (N < 1 || N > RNT_MAX_FRAMES) return fail(LDP_EINVAL, "ldp_train_encoder_backward: %d frames, 1 to %d per call", N, RNT_MAX_FRAMES);
   Trainer& tr = *trainer(h);
   if (tr.enc_fwd_n[slot] != N)
     return fail(LDP_ESTATE, "ldp_train_encoder_backward: encoder%d has no forward of %d frames to differentiate (its last forward kept %d)", slot, N, tr.enc_fwd_n[slot]);
   LDP_HIP(hipSetDevice(h->cfg.device));
-  m->gpart_fresh = false;
-  return run_lane_tape(h, tr.enc_lane[slot], (hipStream_t)stream, [&](Ctx& c) { return encoder_tape(c, slot, nullptr, nullptr, dfeat, N, true); });
+  ms->m.gpart_fresh = false;
+  return run_lane_tape(h, *ms, (hipStream_t)stream, [&](Ctx& c) { return encoder_tape(c, nullptr, nullptr, dfeat, N, true); });
 }
 
 int ldp_train_idm_grad(ldp_handle* h, const float* s, const float* a0, const float* noise, const int32_t* t_dev, float alpha, float* loss_out,
                        int32_t R, void* stream) {
-  Module* m = nullptr;
-  LDP_TRY(need_module(h, 2, &m));
+  ModSlot* ms = nullptr;
+  LDP_TRY(need_slot(h, 2, &ms));
   if (!s || !a0 || !noise || !t_dev || !loss_out || R <= 0) return fail(LDP_EINVAL, "bad argument");
   LDP_HIP(hipSetDevice(h->cfg.device));
-  m->gpart_fresh = false;
-  return run_tape(h, 1, (hipStream_t)stream, [&](Ctx& c) { return idm_tape(c, s, a0, noise, t_dev, alpha, loss_out, R); });
+  ms->m.gpart_fresh = false;
+  return run_lane_tape(h, *ms, (hipStream_t)stream, [&](Ctx& c) { return idm_tape(c, s, a0, noise, t_dev, alpha, loss_out, R); });
 }
 
 int ldp_train_vae_grad(ldp_handle* h, const float* img_nhwc, int32_t N, int32_t use_kl, float beta, const float* eps, uint64_t seed, int64_t row_offset,
                        float* metrics_out, void* stream) {
   if (!h) return fail(LDP_EINVAL, "null handle");
   if (h->cfg.image_size <= 0) return fail(LDP_EINVAL, "module 4 (vae): this handle was created with image_size = 0, it has no StableVAE");
-  Module* m = nullptr;
-  LDP_TRY(need_module(h, 4, &m));
+  ModSlot* ms = nullptr;
+  LDP_TRY(need_slot(h, 4, &ms));
   if (!img_nhwc || !metrics_out || N <= 0 || row_offset < 0) return fail(LDP_EINVAL, "bad argument");
   if (h->cfg.image_size != 64)
     return fail(LDP_EINVAL, "ldp_train_vae_grad: built and tested for 64-pixel frames, this handle has %d", h->cfg.image_size);
@@ -2297,8 +2246,8 @@ int ldp_train_vae_grad(ldp_handle* h, const float* img_nhwc, int32_t N, int32_t 
     return fail(LDP_EINVAL, "ldp_train_vae_grad: %d frames, at most %d per call (the tape keeps every activation of the batch)", N, VAE_TRAIN_MAX_FRAMES);
   if (!std::isfinite(beta)) return fail(LDP_EINVAL, "beta must be finite");
   LDP_HIP(hipSetDevice(h->cfg.device));
-  m->gpart_fresh = false;
-  return run_vae_tape(h, (hipStream_t)stream, [&](Ctx& c) { return vae_tape(c, img_nhwc, N, use_kl != 0, beta, eps, seed, (uint64_t)row_offset, metrics_out); });
+  ms->m.gpart_fresh = false;
+  return run_lane_tape(h, *ms, (hipStream_t)stream, [&](Ctx& c) { return vae_tape(c, img_nhwc, N, use_kl != 0, beta, eps, seed, (uint64_t)row_offset, metrics_out); });
 }
 
 int ldp_train_grad_norm(ldp_handle* h, int32_t modules, float* out, void* stream) {
@@ -2309,10 +2258,11 @@ int ldp_train_grad_norm(ldp_handle* h, int32_t modules, float* out, void* stream
   const float* pa[2] = {nullptr, nullptr};
   long long na[2] = {0, 0};
   int k = 0;
-  for (int bit = 1; bit <= (8 << (RNT_SLOTS - 1)); bit <<= 1) {
-    if (!(modules & bit)) continue;
-    Module* m = nullptr;
-    LDP_TRY(need_module(h, bit, &m));
+  LDP_TRY(need_trainer(h));
+  for (ModSlot& ms : trainer(h)->mods) {
+    if (!(modules & ms.bit)) continue;
+    LDP_TRY(need_ready(ms));
+    Module* m = &ms.m;
     const long long nb = (long long)((m->total + 1023) / 1024);
     if (!m->gpart_fresh) hipLaunchKernelGGL(sumsq1_kernel, dim3((unsigned)nb), dim3(256), 0, s, m->G.f(), (long long)m->total, m->gpart.f());
     pa[k] = m->gpart.f();
@@ -2411,14 +2361,15 @@ static int publish(ldp_handle* h, int32_t modules, bool ema, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   LDP_HIP(hipSetDevice(h->cfg.device));
   LDP_HIP(hipStreamSynchronize(s));
-  for (int bit = 1; bit <= (8 << (RNT_SLOTS - 1)); bit <<= 1) {
-    if (!(modules & bit)) continue;
-    Module* m = nullptr;
-    LDP_TRY(need_module(h, bit, &m));
-    if (ema && !m->ema_on) return fail(LDP_ESTATE, "module %d keeps no EMA (ldp_train_ema was not called)", bit);
-    const char* prefix = nullptr;
-    (void)module_of(h, bit, &prefix);
-    if (bit >= 8) resnet_invalidate(h, enc_slot_of(bit));               // (the slot's packed sampling weights are rebuilt below)
+  LDP_TRY(need_trainer(h));
+  Trainer& tr = *trainer(h);
+  for (ModSlot& ms : tr.mods) {
+    if (!(modules & ms.bit)) continue;
+    LDP_TRY(need_ready(ms));
+    Module* m = &ms.m;
+    if (ema && !m->ema_on) return fail(LDP_ESTATE, "module %d keeps no EMA (ldp_train_ema was not called)", ms.bit);
+    const int enc = (int)(&ms - tr.mods) - MOD_ENC0;
+    if (enc >= 0) resnet_invalidate(h, enc);                            // (the slot's packed sampling weights are rebuilt below)
     std::vector<float> img(m->total);
     LDP_HIP(hipMemcpy(img.data(), ema ? m->E.p : m->P.p, m->total * 4, hipMemcpyDeviceToHost));
     for (const Leaf& l : m->leaves) {
@@ -2426,7 +2377,7 @@ static int publish(ldp_handle* h, int32_t modules, bool ema, void* stream) {
       t.shape = l.shape;
       t.data.resize((size_t)l.taps * l.rows * l.cols);
       unpack_leaf(l, img.data() + l.off, t.data.data());
-      h->weights[std::string(prefix) + l.path] = std::move(t);
+      h->weights[ms.prefix + l.path] = std::move(t);
     }
   }
   drop_graphs(h);

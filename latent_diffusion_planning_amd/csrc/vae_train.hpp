@@ -12,7 +12,8 @@
 //     wgrad     z = tap,           segments = the output pixels where it is live,    K = the batch
 // Taps that fall on padding are not in any list.  Stride 2 reads input (2y + dy, 2x + dx) (XLA SAME on an even side pads (0, 1)); the decoder's
 // nearest x2 upsample is folded into its 3x3: tap (dy, dx) of output (y, x) reads input ((y + dy - 1) >> 1, (x + dx - 1) >> 1), so neither the
-// upsampled tensor nor its gradient exists.  The tables are built on the first call for a frame size and appended to the Trainer's.
+// upsampled tensor nor its gradient exists.  The tap sets and the table builder are train_tables.hpp's (VC_*, tap_2d, plan_2d); the tables are
+// built on the first call for a frame size and appended to the Trainer's.
 //
 // GroupNorm(32) (+ SiLU) runs on (sample, group) work-groups: at 64 px a block holds 16 384 values, so the statistics take two passes (mean, then
 // the centred sum of squares).  The mid-block attention's Dense layers are plain GEMMs over rows = N * tokens, its softmax one work-group per
@@ -23,7 +24,6 @@
 constexpr int VAE_NG = 32;                  // norm_num_groups
 constexpr int VAE_ATT_T = 16;               // most mid-block attention tokens a work-group holds (4 / 9 / 16 at 64 / 96 / 128 px)
 constexpr int VAE_TRAIN_MAX_FRAMES = 256;   // frames per ldp_train_vae_grad call (the tape keeps every activation: ~175 MB per 64-px frame)
-enum { VC_S1 = 0, VC_S2 = 1, VC_UP = 2, VC_P1 = 3, VC_P2 = 4 };      // 3x3 pad 1, 3x3 stride 2 pad (0, 1), nearest x2 then 3x3, 1x1, 1x1 stride 2
 
 __device__ __forceinline__ float vae_silu(float x) { return x / (1.0f + expf(-x)); }
 __device__ __forceinline__ float vae_silu_dx(float x) {
@@ -261,8 +261,7 @@ const int VAE_CH[6] = {128, 256, 256, 256, 256, 256};      // model/stable_vae_m
 constexpr int VAE_NB = 6, VAE_LAYERS = 2;
 
 // the Flax tree of weights.py vae_shapes, in its order; conv kernels (kh, kw, Cin, Cout) are [kh kw][Cin_p][Cout_p] with Cin / Cout padded to 32
-void describe_vae(Trainer& t, int LC) {
-  Module& m = t.vae;
+void describe_vae(Module& m, int LC) {
   auto conv = [&](const std::string& p, int k, int cin, int cout) {
     m.add(p + "/kernel", {k, k, cin, cout}, rup(cin, RP), rup(cout, RP));
     m.add(p + "/bias", {cout}, 1, rup(cout, RP));
@@ -317,91 +316,13 @@ void describe_vae(Trainer& t, int LC) {
   conv("decoder/conv_out", 3, VAE_CH[0], 3);
 }
 
-// input pixel that tap j of output pixel po reads, or -1 (padding)
-int vae_tap_in(int mode, int Sin, int Sout, int po, int j) {
-  const int y = po / Sout, x = po % Sout, dy = j / 3, dx = j % 3;
-  int iy, ix;
-  switch (mode) {
-    case VC_S1: iy = y + dy - 1; ix = x + dx - 1; break;
-    case VC_S2: iy = 2 * y + dy; ix = 2 * x + dx; break;
-    case VC_UP: {
-      const int uy = y + dy - 1, ux = x + dx - 1;
-      if (uy < 0 || ux < 0 || uy >= Sout || ux >= Sout) return -1;
-      iy = uy >> 1; ix = ux >> 1;
-      break;
-    }
-    case VC_P2: return j == 0 ? 2 * y * Sin + 2 * x : -1;
-    default: return j == 0 ? po : -1;
-  }
-  return (iy < 0 || ix < 0 || iy >= Sin || ix >= Sin) ? -1 : iy * Sin + ix;
-}
-
-// the three launch tables of one 2-D convolution (cin / cout padded), appended to the Trainer's (plan_conv's layout, z = pixel)
-ConvPlan plan_conv2d(Trainer& t, int mode, int Sin, int Sout, int cin, int cout) {
-  ConvPlan c;
-  c.mode = mode; c.Tin = Sin * Sin; c.Tout = Sout * Sout; c.cin = cin; c.cout = cout; c.ntaps = (mode == VC_P1 || mode == VC_P2) ? 1 : 9;
-  const long long wtap = (long long)cin * cout;
-  c.f_b0 = (int)t.h_batches.size();
-  for (int to = 0; to < c.Tout; ++to) {
-    GemmBatch b{(long long)to * cout, (int)t.h_segs.size(), 0};
-    for (int j = 0; j < c.ntaps; ++j) {
-      const int ti = vae_tap_in(mode, Sin, Sout, to, j);
-      if (ti >= 0) t.h_segs.push_back(GemmSeg{(long long)ti * cin, j * wtap});
-    }
-    b.seg_end = (int)t.h_segs.size();
-    c.f_minseg = to == 0 ? b.seg_end - b.seg_begin : std::min(c.f_minseg, b.seg_end - b.seg_begin);
-    t.h_batches.push_back(b);
-  }
-  c.f_nb = c.Tout;
-  // dgrad: the (output pixel, tap) pairs of every input pixel, gathered in one sweep (output pixel-major, tap-minor: a fixed order)
-  std::vector<std::vector<GemmSeg>> hits(c.Tin);
-  for (int to = 0; to < c.Tout; ++to)
-    for (int j = 0; j < c.ntaps; ++j) {
-      const int ti = vae_tap_in(mode, Sin, Sout, to, j);
-      if (ti >= 0) hits[ti].push_back(GemmSeg{(long long)to * cout, j * wtap});
-    }
-  c.d_b0 = (int)t.h_batches.size();
-  c.d_minseg = 1 << 30;
-  for (int ti = 0; ti < c.Tin; ++ti) {
-    GemmBatch b{(long long)ti * cin, (int)t.h_segs.size(), 0};
-    t.h_segs.insert(t.h_segs.end(), hits[ti].begin(), hits[ti].end());
-    b.seg_end = (int)t.h_segs.size();
-    c.d_minseg = std::min(c.d_minseg, b.seg_end - b.seg_begin);
-    t.h_batches.push_back(b);
-  }
-  c.d_nb = c.Tin;
-  c.w_b0 = (int)t.h_batches.size();
-  for (int j = 0; j < c.ntaps; ++j) {
-    GemmBatch b{j * wtap, (int)t.h_segs.size(), 0};
-    for (int to = 0; to < c.Tout; ++to) {
-      const int ti = vae_tap_in(mode, Sin, Sout, to, j);
-      if (ti >= 0) t.h_segs.push_back(GemmSeg{(long long)ti * cin, (long long)to * cout});
-    }
-    b.seg_end = (int)t.h_segs.size();
-    if (b.seg_end > b.seg_begin) {
-      c.w_minseg = c.w_nb == 0 ? b.seg_end - b.seg_begin : std::min(c.w_minseg, b.seg_end - b.seg_begin);
-      t.h_batches.push_back(b);
-      ++c.w_nb;
-    } else {
-      t.h_segs.resize(b.seg_begin);
-    }
-  }
-  return c;
-}
-
 // the plan of a convolution: built (and the tables marked for upload) the first time the dry walk of a tape asks for it
 const ConvPlan& vae_plan(Trainer& t, int mode, int Sin, int Sout, int cin, int cout) {
   const std::string key = std::to_string(mode) + ":" + std::to_string(Sin) + ":" + std::to_string(Sout) + ":" + std::to_string(cin) + ":" + std::to_string(cout);
   auto it = t.vconvs.find(key);
   if (it != t.vconvs.end()) return it->second;
   t.tables_dirty = true;
-  return t.vconvs.emplace(key, plan_conv2d(t, mode, Sin, Sout, cin, cout)).first->second;
-}
-
-// y = conv(x) + bias (+ add)
-int conv_fwd_add(const Ctx& c, const ConvPlan& p, const float* x, const float* w, const float* bias, const float* add, float* y, int Bp) {
-  GemmArgs g{x, w, y, bias, add, c.segs(), c.batches() + p.f_b0, Bp, p.cout, p.cin, p.Tin * p.cin, p.cout, p.Tout * p.cout};
-  return run_gemm(c, G_NN, g, p.f_nb, p.f_minseg * (p.cin / BK), (long long)Bp * p.Tout * p.cout);
+  return t.vconvs.emplace(key, plan_2d(t.tab, mode, Sin, Sout, cin, cout)).first->second;
 }
 
 int vae_gn_fwd(const Ctx& c, const float* x, const float* gamma, const float* beta, float* y, float* stats, int Bp, int T, int C, int silu) {
@@ -428,7 +349,7 @@ struct VaeOp {
 // ---- the StableVAE: loss + gradients (model/stable_vae_model.py:25-73; diffusers FlaxAutoencoderKL) -------------------------------------
 int vae_tape(Ctx& c, const float* img, int B, int use_kl, float beta, const float* eps, uint64_t seed, uint64_t row0, float* metrics) {
   Trainer& t = *c.t;
-  Module& m = t.vae;
+  Module& m = *c.M;
   const int S = c.h->cfg.image_size, LC = c.h->cfg.vae_latent_channels, Bp = rup(B, RP), HW = S * S;
   const int hl = S >> (VAE_NB - 1), E = hl * hl, CL = RP;      // CL: padded width of the image / latent-side tensors
   c.L->ws_used = 0;
@@ -444,7 +365,7 @@ int vae_tape(Ctx& c, const float* img, int B, int use_kl, float beta, const floa
     op.kind = 0; op.p = p; op.x = x;
     op.cv[0] = &vae_plan(t, mode, Sin, Sout, rup(cin, RP), rup(cout, RP));
     op.y = take((size_t)Bp * Sout * Sout * rup(cout, RP));
-    VAE_TRY(conv_fwd_add(c, *op.cv[0], x, P(p + "/kernel"), P(p + "/bias"), add, op.y, Bp));
+    VAE_TRY(conv_fwd(c, *op.cv[0], x, P(p + "/kernel"), P(p + "/bias"), add, op.y, Bp));
     ops.push_back(op);
     return op.y;
   };
@@ -469,13 +390,13 @@ int vae_tape(Ctx& c, const float* img, int B, int use_kl, float beta, const floa
     if (cin != cout) {
       op.cv[2] = &vae_plan(t, VC_P1, Sd, Sd, cin, cout);
       op.r = take(no);
-      VAE_TRY(conv_fwd_add(c, *op.cv[2], x, P(p + "/conv_shortcut/kernel"), P(p + "/conv_shortcut/bias"), nullptr, op.r, Bp));
+      VAE_TRY(conv_fwd(c, *op.cv[2], x, P(p + "/conv_shortcut/kernel"), P(p + "/conv_shortcut/bias"), nullptr, op.r, Bp));
       res = op.r;
     }
     VAE_TRY(vae_gn_fwd(c, x, P(p + "/norm1/scale"), P(p + "/norm1/bias"), op.a1, op.st1, Bp, Sd * Sd, cin, 1));
-    VAE_TRY(conv_fwd_add(c, *op.cv[0], op.a1, P(p + "/conv1/kernel"), P(p + "/conv1/bias"), nullptr, op.h1, Bp));
+    VAE_TRY(conv_fwd(c, *op.cv[0], op.a1, P(p + "/conv1/kernel"), P(p + "/conv1/bias"), nullptr, op.h1, Bp));
     VAE_TRY(vae_gn_fwd(c, op.h1, P(p + "/norm2/scale"), P(p + "/norm2/bias"), op.a2, op.st2, Bp, Sd * Sd, cout, 1));
-    VAE_TRY(conv_fwd_add(c, *op.cv[1], op.a2, P(p + "/conv2/kernel"), P(p + "/conv2/bias"), res, op.y, Bp));
+    VAE_TRY(conv_fwd(c, *op.cv[1], op.a2, P(p + "/conv2/kernel"), P(p + "/conv2/bias"), res, op.y, Bp));
     ops.push_back(op);
     return op.y;
   };
@@ -677,37 +598,3 @@ int vae_tape(Ctx& c, const float* img, int B, int use_kl, float beta, const floa
   if (!c.dry) LDP_HIP(hipGetLastError());
   return LDP_OK;
 }
-
-// dry walk (sizes the workspace and builds the missing conv tables), table upload, then the real enqueue on the given lane
-int run_lane_tape(ldp_handle* h, Lane& t, hipStream_t s, const std::function<int(Ctx&)>& tape) {
-  Trainer& tr = *trainer(h);
-  Ctx c{h, &tr, &t, s, true};
-  t.colsum_need = 0;
-  t.part_need = 0;
-  t.coljobs.clear();
-  LDP_TRY(tape(c));
-  t.coljobs.clear();
-  if (tr.tables_dirty) {
-    LDP_HIP(hipDeviceSynchronize());                          // (the other lanes' tapes read the tables being replaced)
-    LDP_TRY(upload(tr.d_segs, tr.h_segs.data(), tr.h_segs.size() * sizeof(GemmSeg), nullptr));
-    LDP_TRY(upload(tr.d_batches, tr.h_batches.data(), tr.h_batches.size() * sizeof(GemmBatch), nullptr));
-    tr.tables_dirty = false;
-  }
-  if (t.ws_used > t.ws_floats || t.colsum_need > t.colsum_tmp.bytes || t.part_need > t.gemm_part.bytes) {
-    LDP_HIP(hipStreamSynchronize(s));                         // (a previous call may still read the old workspace; its side streams were joined into s)
-    if (t.ws_used > t.ws_floats) {
-      LDP_TRY(t.ws.alloc(t.ws_used * 4));
-      t.ws_floats = t.ws_used;
-    }
-    LDP_TRY(t.colsum_tmp.alloc(t.colsum_need));
-    LDP_TRY(t.gemm_part.alloc(t.part_need));
-    for (int k = 0; k < Lane::NS; ++k) {
-      LDP_TRY(t.colsum_tmp2[k].alloc(t.colsum_need));
-      LDP_TRY(t.gemm_part2[k].alloc(t.part_need));
-    }
-  }
-  c.dry = false;
-  LDP_TRY(tape(c));
-  return join(c);
-}
-int run_vae_tape(ldp_handle* h, hipStream_t s, const std::function<int(Ctx&)>& tape) { return run_lane_tape(h, trainer(h)->lane[2], s, tape); }

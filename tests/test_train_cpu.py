@@ -220,8 +220,8 @@ def test_the_shape_cases_reach_every_training_gemm_instantiation():
 
 def test_the_encoder_cases_reach_every_training_gemm_instantiation():
     """tests/test_hip_resnet_train_shapes.py, part A: the ResNet-18 tape's 59 GEMM launches as tests/train_cases.py restates them from the
-    convolution tables (vae_tap_in / plan_conv2d), the launch-table facts the restatement rests on worked out by hand, and the counters the
-    (case, configuration) pairs require covering all 15 instantiations, the in-launch finish and the reduce launch."""
+    convolution tables (tap_2d / plan_taps of csrc/train_tables.hpp), the launch-table facts the restatement rests on worked out by hand, and
+    the counters the (case, configuration) pairs require covering all 15 instantiations, the in-launch finish and the reduce launch."""
     from tests import train_cases as TC
     from tests.test_hip_resnet_train_shapes import CASES, WORKLOAD
     # a 3x3 at 2x2 pixels: every output pixel sees 4 live taps, every input pixel is read 4 times, the centre tap is live at all 4 pixels and a corner tap at 1

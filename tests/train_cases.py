@@ -81,8 +81,25 @@ def fused_part_bytes(M, N, nbatch, tile, ks):
     return size if tiles <= CNT_TILES and size < 1 << 31 else 0
 
 
-# ---- csrc/vae_train.hpp vae_tap_in / plan_conv2d, restated for the modes the encoder's tape uses ------------------------------------------------
-VC_S1, VC_S2, VC_P1, VC_P2 = 0, 1, 3, 4   # 3x3 pad 1, 3x3 stride 2 pad (0, 1), 1x1, 1x1 stride 2
+# ---- csrc/train_tables.hpp tap_1d / tap_2d / plan_taps, restated ----------------------------------------------------------------------------------
+MODE_K5, MODE_DOWN, MODE_UP, MODE_P1 = 0, 1, 2, 3   # 1-D: k = 5 pad 2, k = 3 stride 2 pad (0, 1), transposed k = 4 stride 2, 1x1
+VC_S1, VC_S2, VC_UP, VC_P1, VC_P2 = 0, 1, 2, 3, 4   # 2-D: 3x3 pad 1, 3x3 stride 2 pad (0, 1), nearest x2 then 3x3, 1x1, 1x1 stride 2
+
+
+def tap_in_1d(mode, Tin, to, j):
+    """Input position that tap j of output position `to` reads, or -1 (padding, or a tap of the transposed convolution's other phase)."""
+    if mode == MODE_K5:
+        ti = to + j - 2
+    elif mode == MODE_DOWN:
+        ti = 2 * to + j
+    elif mode == MODE_UP:                  # out[2q] = x[q-1] K0 + x[q] K2; out[2q+1] = x[q] K1 + x[q+1] K3
+        q = to >> 1
+        ti = {0: q - 1, 2: q}.get(j, -1) if to % 2 == 0 else {1: q, 3: q + 1}.get(j, -1)
+    elif mode == MODE_P1:
+        ti = to
+    else:
+        raise ValueError(mode)
+    return ti if 0 <= ti < Tin else -1
 
 
 def tap_in(mode, Sin, Sout, po, j):
@@ -92,6 +109,11 @@ def tap_in(mode, Sin, Sout, po, j):
         iy, ix = y + dy - 1, x + dx - 1
     elif mode == VC_S2:
         iy, ix = 2 * y + dy, 2 * x + dx
+    elif mode == VC_UP:                    # the 3x3 reads the upsampled image (side Sout) at (uy, ux): input pixel (uy >> 1, ux >> 1)
+        uy, ux = y + dy - 1, x + dx - 1
+        if uy < 0 or ux < 0 or uy >= Sout or ux >= Sout:
+            return -1
+        iy, ix = uy >> 1, ux >> 1
     elif mode == VC_P2:
         return 2 * y * Sin + 2 * x if j == 0 else -1
     elif mode == VC_P1:
@@ -99,6 +121,60 @@ def tap_in(mode, Sin, Sout, po, j):
     else:
         raise ValueError(mode)
     return -1 if iy < 0 or ix < 0 or iy >= Sin or ix >= Sin else iy * Sin + ix
+
+
+def ntaps_of(family, mode):
+    return {MODE_K5: 5, MODE_DOWN: 3, MODE_UP: 4, MODE_P1: 1}[mode] if family == "1d" else (1 if mode in (VC_P1, VC_P2) else 9)
+
+
+def conv_tables(family, mode, Sin, Sout, cin, cout):
+    """The three launch tables of one convolution, appended to empty tables -> dict(segs=[(a_off, b_off)], batches=[(c_off, seg_begin, seg_end)],
+    plan=dict(Tin, Tout, ntaps, f_b0, f_nb, f_minseg, d_b0, ...)).  family "1d": Sin / Sout positions; "2d": square images of side Sin / Sout.
+    Written loop for loop as the two builders this header replaced walked them, so it states their order: forward = a batch per output with a
+    segment per live tap; data gradient = a batch per input whose segments run output-major and tap-minor (the summation order of its split
+    K); weight gradient = a batch per tap with a segment per output it is live at, and no batch for a tap that is live nowhere."""
+    if family == "1d":
+        Tin, Tout = Sin, Sout
+        tap = lambda to, j: tap_in_1d(mode, Tin, to, j)                  # noqa: E731
+    else:
+        Tin, Tout = Sin * Sin, Sout * Sout
+        tap = lambda to, j: tap_in(mode, Sin, Sout, to, j)               # noqa: E731
+    ntaps, wtap = ntaps_of(family, mode), cin * cout
+    segs, batches, plan = [], [], dict(Tin=Tin, Tout=Tout, ntaps=ntaps)
+
+    def close(kind, c_off, s0, keep_empty=True):
+        n = len(segs) - s0
+        if n == 0 and not keep_empty:
+            return
+        batches.append((c_off, s0, len(segs)))
+        plan[kind + "_minseg"] = n if plan[kind + "_nb"] == 0 else min(plan[kind + "_minseg"], n)
+        plan[kind + "_nb"] += 1
+
+    plan.update(f_b0=len(batches), f_nb=0, f_minseg=0)
+    for to in range(Tout):
+        s0 = len(segs)
+        for j in range(ntaps):
+            ti = tap(to, j)
+            if ti >= 0:
+                segs.append((ti * cin, j * wtap))
+        close("f", to * cout, s0)
+    plan.update(d_b0=len(batches), d_nb=0, d_minseg=0)
+    for ti in range(Tin):
+        s0 = len(segs)
+        for to in range(Tout):
+            for j in range(ntaps):
+                if tap(to, j) == ti:
+                    segs.append((to * cout, j * wtap))
+        close("d", ti * cin, s0)
+    plan.update(w_b0=len(batches), w_nb=0, w_minseg=0)
+    for j in range(ntaps):
+        s0 = len(segs)
+        for to in range(Tout):
+            ti = tap(to, j)
+            if ti >= 0:
+                segs.append((ti * cin, to * cout))
+        close("w", j * wtap, s0, keep_empty=False)
+    return dict(segs=segs, batches=batches, plan=plan)
 
 
 def conv_plan(mode, Sin, Sout):
@@ -139,7 +215,7 @@ def encoder_convs():
 
 
 def encoder_launches(rows):
-    """The 59 GEMM launches of one encoder forward + backward over `rows` padded frames (conv_fwd_add / conv_dgrad / conv_wgrad): 20 forward,
+    """The 59 GEMM launches of one encoder forward + backward over `rows` padded frames (conv_fwd / conv_dgrad / conv_wgrad): 20 forward,
     19 data-gradient, 20 weight-gradient, as (form, M, N, batches, fewest K steps of a batch)."""
     fwd, dgrad, wgrad = [], [], []
     for mode, Sin, Sout, cin, cout, has_d in encoder_convs():
