@@ -33,6 +33,7 @@ struct ConvW {
   int nj = 0, cin = 0, cout = 0, cin_p = 0, cout_p = 0;
   bool has_gn = false, has_res = false;
   bool t2s = false;                             // w is packed for the shared-product form of two positions (t2pack.hpp): W2, W3 - W2, W1 - W2 (+ projection)
+  bool t4s = false;                             // w is packed for the nine-product form of four positions (t4pack.hpp): nine combinations (+ projection)
 };
 
 struct ResBlock {
@@ -208,6 +209,7 @@ struct ldp_handle {
   int64_t last_conv_launches = 0, last_total_launches = 0;
   int64_t stat_f16_launches = 0;         // likewise: conv launches on fp16 planes
   int64_t stat_t2_shared_launches = 0;   // likewise: exact-fp32 k = 5 launches over two positions in the three-product form (tconv.hpp t2_shared)
+  int64_t stat_t4_shared_launches = 0;   // likewise: exact-fp32 k = 5 launches over four positions in the nine-product form (tconv.hpp t4_shared)
   std::map<uint64_t, int64_t> plan_log;       // every distinct tconv instantiation this handle launched, keyed by plan_key (option "dump_plans" prints it: tools/r5/plans_used.py)
   int64_t stat_mb2_launches = 0;         // conv launches enqueued (eagerly or into a capture) on two-row-block split tiles since ldp_create: read-only option
   // training GEMM launches enqueued since ldp_create, per instantiation of train.hip's kernel family: [form (NN, NT, TN) * 5 + {32-row, 32-row KI = 2,
@@ -234,7 +236,7 @@ bool fits_f16_planes(const float* w, size_t n);
 std::vector<uint16_t> pack_conv_split16h(const float* w, int nj, int cin, int cout);
 int get_weight(ldp_handle* h, const std::string& path, const HostTensor** out,
                std::initializer_list<int64_t> shape);
-// t_pos: positions a k = 5 conv runs at (0: not a k = 5 conv / unknown); two positions get the shared-product packing
+// t_pos: positions a k = 5 conv runs at (0: not a k = 5 conv / unknown); two positions get the shared-product packing, four the nine-product one
 int make_conv(ldp_handle* h, const std::string& prefix, int nj, int cin, int cout, int cin_p,
               int cout_p, const char* gn_prefix, hipStream_t s, ConvW& out, int t_pos = 0);
 

@@ -235,9 +235,29 @@ __host__ __device__ constexpr bool t2_shared(int mode, int to_n, int split) {
   return !LDP_T2_DIRECT && mode == MODE_K5 && to_n == 2 && split == 0;
 }
 constexpr int T2_SLOTS = 3;      // weight fragments per chunk of the shared form: W2, W3 - W2, W1 - W2
+
+// Exact-fp32 k = 5 convs over FOUR positions (the conv's whole length: zero padding on both sides): the 4 x 4 Toeplitz product
+//   y0 = W2 x0 + W3 x1 + W4 x2            y2 = W0 x0 + W1 x1 + W2 x2 + W3 x3
+//   y1 = W1 x0 + W2 x1 + W3 x2 + W4 x3    y3 =         W0 x1 + W1 x2 + W2 x3        (14 products per k-step: valid_pairs(MODE_K5, 4))
+// is [[T0, T1], [T2, T0]] in 2 x 2 blocks with T0 = [[W2, W3], [W1, W2]]; the two-position identity once over the blocks and once inside
+// each block leaves NINE products (u0 = x0 + x2, u1 = x1 + x3, a = W4 - W2, a' = W0 - W2):
+//   s = W2 (u0 + u1)     e0  = (W3 - W2) u1          e1  = (W1 - W2) u0
+//   p = a  (x2 + x3)     dt0 = (-W3 - a) x3          dt1 = (W3 - W1 - a) x2
+//   q = a' (x0 + x1)     db0 = (W1 - W3 - a') x1     db1 = (-W1 - a') x0
+//   y0 = s + e0 + p + dt0,   y1 = s + e1 + p + dt1,   y2 = s + e0 + q + db0,   y3 = s + e1 + q + db1.
+// pack_conv_t4 (t4pack.hpp) stores the nine weight combinations in this order (+ the projection) per chunk where the five taps stood; the
+// five activation sums are VALU adds behind the LDS reads.  As with t2_shared the form belongs to (mode, TO, SPLIT).
+// LDP_T4_DIRECT (A/B build only, `make t4direct`): the fourteen-product loop on the five-tap packing.
+#ifndef LDP_T4_DIRECT
+#define LDP_T4_DIRECT 0
+#endif
+__host__ __device__ constexpr bool t4_shared(int mode, int to_n, int split) {
+  return !LDP_T4_DIRECT && mode == MODE_K5 && to_n == 4 && split == 0;
+}
+constexpr int T4_SLOTS = 9;      // weight fragments per chunk of the nine-product form
 // matrix instructions per k-step per wave and row block (without the projection)
 __host__ __device__ constexpr int conv_products(int mode, int to_n, int split) {
-  return t2_shared(mode, to_n, split) ? T2_SLOTS : valid_pairs(mode, to_n);
+  return t2_shared(mode, to_n, split) ? T2_SLOTS : t4_shared(mode, to_n, split) ? T4_SLOTS : valid_pairs(mode, to_n);
 }
 
 // 16-byte-slot swizzle of a 16x16 f32 sub-tile: slot' = slot ^ H(row >> 2), H = {0,3,2,1}
@@ -535,6 +555,29 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
   for (int m = 0; m < (T2S ? MB : 1); ++m) sacc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int m = 0; m < (T2S2 ? MB : 1); ++m) sacc_b[m] = acc_b[m][0] = acc_b[m][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // nine-product form of four positions: s, e0, e1, p, dt0, dt1, q, db0, db1 (t4pack.hpp's slot order), summed into acc[.][0..3] behind the loop.
+  // T4F, one K slice per work-group (the whole-group tiles): each of the nine would be one chain over the layer's whole K range, and where the
+  // sums cancel (x_t = 10^t x0 and a single tap: y0 is a thousandth of its four terms) the chains' round-off stands against the small
+  // result.  A second accumulator set for the odd sub-chunks (T2S2 above) still read 1.13e-5 against the 1e-5 bound on 1024 -> 1024; these
+  // tiles instead start the nine from zero in every iteration and add the four sums into acc[.][0..3] at its end: chains of CPI * 4
+  // instructions, the cancellation happens on partial sums of one iteration's channels, and the long chain carries the small result.
+  // T4P, two row blocks per work-group: 18 accumulators, two nine-fragment weight buffers and the fragments of two row blocks do not fit
+  // 256 registers (212 .. 320 bytes of scratch).  These tiles walk their K range once per row block -- prologue and main loop twice, the
+  // nine accumulators and the weight buffers reused, each pass staging its own row block -- and share the epilogue: the launch shape, the
+  // statistics exchange and every accumulator's order are those of a one-pass tile; the weight stream is not halved as two row blocks
+  // otherwise halve it (these tiles serve >= ~1000 plans with planner_split off: tests, no benchmark configuration).
+  constexpr bool T4S = t4_shared(MODE, TO, SPLIT);
+  constexpr bool T4F = T4S && KS == 1 && !RES_OUT;      // (with the projection's four accumulators the flush spills 96 bytes: that tile keeps one chain)
+  constexpr bool T4P = T4S && MB == 2;
+  constexpr int MBE = T4P ? 1 : MB;                      // row blocks of one pass
+  constexpr int NLDE = T4P ? C::NLD / 2 : C::NLD;        // staging loads of one pass
+  static_assert(!T4P || C::NLD % 2 == 0, "two-pass tiles: whole staging loads per row block");
+  static_assert(!(T4P && (T4F || RES_OUT)), "two-pass tiles: K slices, no projection");
+  f32x4 tacc[T4S && !T4F ? MBE : 1][T4S && !T4F ? T4_SLOTS : 1];
+#pragma unroll
+  for (int m = 0; m < (T4S && !T4F ? MBE : 1); ++m)
+#pragma unroll
+    for (int t = 0; t < (T4S && !T4F ? T4_SLOTS : 1); ++t) tacc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
   f32x4 acc_lo[C::F16 ? MB : 1][C::F16 ? TO : 1], racc_lo[C::F16 ? MB : 1][C::F16 && RES_OUT ? TO : 1];    // fp16 planes: the h l' + l' h products (x 2^11)
 #pragma unroll
   for (int m = 0; m < (C::F16 ? MB : 1); ++m) {
@@ -593,7 +636,9 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
   }
 
   f32x4 xst[C::NLD];
-  auto stage_load = [&](int it) {
+  // (two-pass tiles: a pass stages its own row block only -- loads [PASS * NLD / 2, (PASS + 1) * NLD / 2), idx / (64 * NC * TI) = the row block)
+  auto stage_load = [&](auto pass_tag, int it) {
+    constexpr int SI0 = T4P ? decltype(pass_tag)::value * (C::NLD / 2) : 0, SI1 = T4P ? SI0 + C::NLD / 2 : C::NLD;
     const int c0 = it * C::CH_IT;
     if (mode_2d(MODE)) {
       const int dh = c0 / a.ca, cbase = c0 - dh * a.ca;
@@ -618,12 +663,13 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
     const int creal = a.ca_real > 0 ? a.ca_real : 0x7fffffff;
     const int stride = a.ca_real > 0 ? a.ca_real : cw;
 #pragma unroll
-    for (int i = 0; i < C::NLD; ++i) {
+    for (int i = SI0; i < SI1; ++i) {
       const bool ok = (cbase + st_cc[i]) < creal;
       xst[i] = *reinterpret_cast<const f32x4*>(base + (size_t)st_goff[i] * stride + (ok ? cbase + st_cc[i] : 0));
     }
   };
-  auto stage_store = [&](float* buf) {
+  auto stage_store = [&](auto pass_tag, float* buf) {
+    constexpr int SI0 = T4P ? decltype(pass_tag)::value * (C::NLD / 2) : 0, SI1 = T4P ? SI0 + C::NLD / 2 : C::NLD;
     if constexpr (C::F16) {
 #pragma unroll
       for (int i = 0; i < C::NLD; ++i) {
@@ -646,7 +692,7 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
       return;
     }
 #pragma unroll
-    for (int i = 0; i < C::NLD; ++i) *reinterpret_cast<f32x4*>(buf + st_loff[i]) = xst[i];
+    for (int i = SI0; i < SI1; ++i) *reinterpret_cast<f32x4*>(buf + st_loff[i]) = xst[i];
   };
 
   // ---- weight fragment streaming ---------------------------------------------------------
@@ -657,23 +703,24 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
   // The projection's fragments live in the conv's own buffer, right behind the taps of their chunk: a
   // second weight stream from a separate allocation cost 20-25 % of the loop time of these layers.
   constexpr bool SKIPZ = MODE == MODE_K5 && RES_OUT && SPLIT == 0 && TO >= 8 && KS > 1;
-  constexpr int NJW = (T2S ? T2_SLOTS : NJ) + (RES_OUT ? 1 : 0);      // fragments per chunk in the packed buffer
-  constexpr int NJR = T2S ? T2_SLOTS : NJ;                            // slot of the projection
+  constexpr int NJR = T2S ? T2_SLOTS : T4S ? T4_SLOTS : NJ;           // slot of the projection
+  constexpr int NJW = NJR + (RES_OUT ? 1 : 0);                        // fragments per chunk in the packed buffer
+  constexpr int NJB = T4S ? T4_SLOTS : NJ;                            // register rows of one weight buffer (the two-position form uses rows 1..3 of NJ)
   // 16-row split tiles: an iteration is NSTEP 32-channel steps; a register buffer holds ONE step and the two buffers roll step by
   // step (the LDS stage + barrier of an iteration then amortises over NSTEP steps without more weight registers)
   constexpr int NSTEP = S16 ? CPI / 2 : 1;
   constexpr int WCH = S16 ? 1 : CPI;                     // weight fragments along K held by one register buffer
   constexpr int RN = RES_OUT ? WCH : 1;
   constexpr int WPL = SPLIT ? C::NPL : 1;                // weight planes
-  f32x4 wb0[NJ][WCH * WPL], wb1[NJ][WCH * WPL];
+  f32x4 wb0[NJB][WCH * WPL], wb1[NJB][WCH * WPL];
   f32x4 rb0[RN * WPL], rb1[RN * WPL];
   // S16: `it` counts 32-channel steps of this wave's K slice (iteration * NSTEP + step)
-  auto wload = [&](int it, f32x4 (&b)[NJ][WCH * WPL], f32x4 (&rb)[RN * WPL]) {
+  auto wload = [&](int it, f32x4 (&b)[NJB][WCH * WPL], f32x4 (&rb)[RN * WPL]) {
 #pragma unroll
     for (int ci = 0; ci < WCH; ++ci) {
       const int gc = S16 ? (it / NSTEP) * (NC / 2) + ks * NSTEP + (it % NSTEP) : it * NC + ks * CPI + ci;
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) {
+      for (int j = 0; j < NJB; ++j) {
         if constexpr (SPLIT) {
           if (tap_used(MODE, TO, j)) {
 #pragma unroll
@@ -683,8 +730,8 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
             }
           }
         } else
-        if (tap_used(MODE, TO, j)) {
-          // shared form: slots 0, 1, 2 = W2, W3 - W2, W1 - W2 travel in the register rows of taps 1, 2, 3
+        if (T4S || tap_used(MODE, TO, j)) {
+          // shared form: slots 0, 1, 2 = W2, W3 - W2, W1 - W2 travel in the register rows of taps 1, 2, 3 (nine-product form: slot j in row j)
           const size_t off = (((size_t)gc * NJW + (T2S ? j - 1 : j)) * nblk_total + nblk) * 256 + lane * 4;
           // LDP_W_NT (A/B build only, round 4): non-temporal weight loads in the small-batch (KWS) instantiations, where one
           // CU reads its weight slice once per launch (MI355X_MICROARCH.md row nt-weights); measured, see DESIGN 4.1
@@ -733,9 +780,10 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
 #pragma unroll
       for (int i = 0; i < 16; ++i) racc32[t][i] = 0.f;
   }
-  auto iteration = [&](auto last_tag, int it, f32x4 (&bc)[NJ][WCH * WPL], f32x4 (&rc)[RN * WPL], f32x4 (&bl)[NJ][WCH * WPL],
+  auto iteration = [&](auto pass_tag, auto last_tag, int it, f32x4 (&bc)[NJB][WCH * WPL], f32x4 (&rc)[RN * WPL], f32x4 (&bl)[NJB][WCH * WPL],
                        f32x4 (&rl)[RN * WPL]) {
     constexpr bool LAST = decltype(last_tag)::value;
+    constexpr int PASS = decltype(pass_tag)::value;      // T4P: the row block this pass multiplies
     float* xcur = smem + (it & 1) * C::XT;
     float* xnext = smem + ((it + 1) & 1) * C::XT;
     // branch-free body so that loads, LDS traffic and MFMAs share one scheduling region and can be
@@ -744,7 +792,7 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
     if (!LAST) {
       // ablations of the split tiles only (the fp32 instantiations of the ablation build keep one straight-line body): 2048 no staging
       // loads, 1024 no weight loads, 512 no LDS writes and no barrier
-      if (!(SPLIT && LDP_ABL(2048))) stage_load(itn);
+      if (!(SPLIT && LDP_ABL(2048))) stage_load(pass_tag, itn);
       if (!S16 && !(SPLIT && LDP_ABL(1024))) wload(itn, bl, rl);
     }
     if constexpr (S16) {
@@ -758,7 +806,7 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
       constexpr int NMFMA = (C::F16 ? 3 : LDP_SPLIT_NPROD) * NPAIR * MB;
       constexpr int NREAD = MB * TI * NPL;
       constexpr int AHEAD = MB * (TI > 2 ? 2 : TI) * NPL;    // fragment reads issued before the first matrix instruction (two positions)
-      auto step = [&](auto pc_tag, f32x4 (&wc)[NJ][WCH * WPL], f32x4 (&rcur)[RN * WPL], f32x4 (&wn)[NJ][WCH * WPL], f32x4 (&rnext)[RN * WPL]) {
+      auto step = [&](auto pc_tag, f32x4 (&wc)[NJB][WCH * WPL], f32x4 (&rcur)[RN * WPL], f32x4 (&wn)[NJB][WCH * WPL], f32x4 (&rnext)[RN * WPL]) {
         constexpr int pc = decltype(pc_tag)::value;
         constexpr bool PREF = pc + 1 < NSTEP || !LAST;      // a step follows this one (in this iteration or the next)
         if (PREF && !LDP_ABL(1024)) wload(pc + 1 < NSTEP ? it * NSTEP + pc + 1 : itn * NSTEP, wn, rnext);
@@ -854,7 +902,7 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
       if constexpr (NSTEP > 3) step(std::integral_constant<int, 3>{}, bl, rl, bc, rc);
       static_assert(NSTEP <= 4, "at most four 32-channel steps per iteration");
       if (LDP_ABL(512)) return;
-      if (!LAST) stage_store(xnext);
+      if (!LAST) stage_store(pass_tag, xnext);
       __syncthreads();
       return;
     }
@@ -921,7 +969,7 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
         }
         if (NMFMA - NLOADS * MPL > 0) __builtin_amdgcn_sched_group_barrier(0x008, NMFMA - NLOADS * MPL, 0);
       }
-      if (!LAST) stage_store(xnext);
+      if (!LAST) stage_store(pass_tag, xnext);
       __syncthreads();
       return;
     }
@@ -977,6 +1025,56 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
         }
       }
     } else
+    if constexpr (T4S) {
+      // nine products per k-step on the five sum fragments and the four positions themselves; slot k multiplies into accumulator k, so
+      // consecutive matrix instructions write different accumulators and every accumulator takes its products in K order whatever the tile
+      f32x4 tit[T4F ? MB : 1][T4F ? T4_SLOTS : 1];      // T4F: this iteration's nine (below: mm = row block of the pass, m = of the tile)
+#pragma unroll
+      for (int m = 0; m < (T4F ? MB : 1); ++m)
+#pragma unroll
+        for (int k = 0; k < (T4F ? T4_SLOTS : 1); ++k) tit[m][k] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ci = 0; ci < CPI; ++ci) {
+        f32x4 af[MBE][T4_SLOTS];
+#pragma unroll
+        for (int mm = 0; mm < MBE; ++mm) {
+          const int m = T4P ? PASS : mm;
+          const f32x4 x0 = areg[m][0][ci], x1 = areg[m][1][ci], x2 = areg[m][2][ci], x3 = areg[m][3][ci];
+          const f32x4 u0 = x0 + x2, u1 = x1 + x3;
+          af[mm][0] = u0 + u1; af[mm][1] = u1; af[mm][2] = u0;
+          af[mm][3] = x2 + x3; af[mm][4] = x3; af[mm][5] = x2;
+          af[mm][6] = x0 + x1; af[mm][7] = x1; af[mm][8] = x0;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+#pragma unroll
+          for (int k = 0; k < T4_SLOTS; ++k) {
+#pragma unroll
+            for (int m = 0; m < MBE; ++m) {
+              f32x4& d = T4F ? tit[T4F ? m : 0][T4F ? k : 0] : tacc[T4F ? 0 : m][T4F ? 0 : k];
+              d = __builtin_amdgcn_mfma_f32_16x16x4f32(af[m][k][s], bc[k][ci][s], d, 0, 0, 0);
+            }
+          }
+          if (RES_OUT) {
+#pragma unroll
+            for (int to = 0; to < TO; ++to)
+#pragma unroll
+              for (int m = 0; m < MB; ++m)
+                racc[m][to] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[m][to][ci][s], rc[ci][s], racc[m][to], 0, 0, 0);
+          }
+        }
+      }
+      if constexpr (T4F) {
+#pragma unroll
+        for (int m = 0; m < MB; ++m) {
+          const f32x4 se0 = tit[m][0] + tit[m][1], se1 = tit[m][0] + tit[m][2];
+          acc[m][0] = acc[m][0] + ((se0 + tit[m][3]) + tit[m][4]);
+          acc[m][1] = acc[m][1] + ((se1 + tit[m][3]) + tit[m][5]);
+          acc[m][2] = acc[m][2] + ((se0 + tit[m][6]) + tit[m][7]);
+          acc[m][3] = acc[m][3] + ((se1 + tit[m][6]) + tit[m][8]);
+        }
+      }
+    } else
     if (!dead_slice) {
 #pragma unroll
     for (int ci = 0; ci < CPI; ++ci) {
@@ -1011,39 +1109,32 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
     // pipe's queue while the MFMA pipe idles), then the LDS writes of the next activation tile.
     if (LAST) {
 #pragma unroll
-      for (int i = 0; i < MB * TI * CPI; ++i) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      for (int i = 0; i < MBE * TI * CPI; ++i) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
     } else {
       constexpr int NUSED = (tap_used(MODE, TO, 0) ? 1 : 0) + (NJ > 1 && tap_used(MODE, TO, 1) ? 1 : 0) +
                             (NJ > 2 && tap_used(MODE, TO, 2) ? 1 : 0) + (NJ > 3 && tap_used(MODE, TO, 3) ? 1 : 0) +
                             (NJ > 4 && tap_used(MODE, TO, 4) ? 1 : 0);
-      constexpr int NLOADS = C::NLD + (NUSED + (RES_OUT ? 1 : 0)) * CPI;
-      constexpr int NMFMA = MB * CPI * 4 * (conv_products(MODE, TO, SPLIT) + (RES_OUT ? TO : 0));
+      constexpr int NLOADS = NLDE + ((T4S ? T4_SLOTS : NUSED) + (RES_OUT ? 1 : 0)) * CPI;
+      constexpr int NMFMA = MBE * CPI * 4 * (conv_products(MODE, TO, SPLIT) + (RES_OUT ? TO : 0));
       // loads are spread evenly over the whole MFMA stream: each is consumed at the same position of the
       // next iteration, i.e. every load gets exactly one iteration of prefetch distance (bunching them
       // into the first half or third of the stream measured 1.5 % / 4 % slower)
       constexpr int MPL = NMFMA / NLOADS > 0 ? NMFMA / NLOADS : 1;
 #pragma unroll
-      for (int i = 0; i < MB * TI * CPI; ++i) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      for (int i = 0; i < MBE * TI * CPI; ++i) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
 #pragma unroll
       for (int i = 0; i < NLOADS; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, MPL, 0);
       }
       if (NMFMA - NLOADS * MPL > 0) __builtin_amdgcn_sched_group_barrier(0x008, NMFMA - NLOADS * MPL, 0);
-      __builtin_amdgcn_sched_group_barrier(0x200, C::NLD, 0);      // LDS writes last
+      __builtin_amdgcn_sched_group_barrier(0x200, NLDE, 0);      // LDS writes last
     }
-    if (!LAST) stage_store(xnext);
+    if (!LAST) stage_store(pass_tag, xnext);
     __syncthreads();
   };
 
-  // ---- prologue ---------------------------------------------------------------------------
-  stage_load(it0);
-  wload(S16 ? it0 * NSTEP : it0, wb0, rb0);
-  stage_store(smem + (it0 & 1) * C::XT);
-  __syncthreads();
-  LDP_TL(1);
-
-  // ---- main loop over input-channel chunks ---------------------------------------------------
+  // ---- prologue and main loop over input-channel chunks: one pass over the K range (LDP_TCONV_PASS) --------------------------------------
   // Unrolled by two with the buffer roles swapped.  The counted loop holds whole pairs only and the one or two
   // closing iterations live behind it (round-3 findings, both read off the ISA):
   //  * the last iteration of the K range gets its own copy of the body without prefetch (LAST): the branch-free
@@ -1054,35 +1145,70 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
   //    opens with s_waitcnt vmcnt(0).  A straight-line pair body has no such path (the waits are the designed
   //    vmcnt(12..) again); the same loop with `break` exits, or all four copies inside one for(;;), cost 40-60
   //    more VGPRs and spilled in the two-row-block tiles.
-  if (mode_2d(MODE) && !S16) {
-    // The StableVAE's 3x3 convs keep the round-2 loop (branch-free, the last iteration re-requests its own chunk):
-    // measured on one box at N = 256, encode 26.96 ms with it, 27.9 ms with the peeled last iteration, 29.3 ms
-    // with zero padding as an address select (no wait behind the staging loads any more -- and slower), 30.2 ms
-    // with the last k-step's MFMAs deferred behind the next iteration's LDS reads.  Long steady-state loops over
-    // thousands of work-groups do not behave like the planner's launch-bound ones.
-    for (int it = it0; it < nit; it += 2) {
-      iteration(std::false_type{}, it, wb0, rb0, wb1, rb1);
-      if (it + 1 < nit) iteration(std::false_type{}, it + 1, wb1, rb1, wb0, rb0);
-    }
-  } else {
-    int it = it0;
-    if constexpr (S16 && NSTEP % 2 == 0) {
-      // an even number of steps leaves the next iteration's first step in the buffer this one started from: no role swap
-      for (; it + 1 < nit; ++it) iteration(std::false_type{}, it, wb0, rb0, wb1, rb1);
-      iteration(std::true_type{}, it, wb0, rb0, wb1, rb1);
-    } else {
-    for (; it + 2 < nit; it += 2) {
-      iteration(std::false_type{}, it, wb0, rb0, wb1, rb1);
-      iteration(std::false_type{}, it + 1, wb1, rb1, wb0, rb0);
-    }
-    if (it + 2 == nit) {
-      iteration(std::false_type{}, it, wb0, rb0, wb1, rb1);
-      iteration(std::true_type{}, it + 1, wb1, rb1, wb0, rb0);
-    } else if (it + 1 == nit) {
-      iteration(std::true_type{}, it, wb0, rb0, wb1, rb1);
-    }
+  // First branch: the StableVAE's 3x3 convs keep the round-2 loop (branch-free, the last iteration re-requests its own chunk):
+  // measured on one box at N = 256, encode 26.96 ms with it, 27.9 ms with the peeled last iteration, 29.3 ms
+  // with zero padding as an address select (no wait behind the staging loads any more -- and slower), 30.2 ms
+  // with the last k-step's MFMAs deferred behind the next iteration's LDS reads.  Long steady-state loops over
+  // thousands of work-groups do not behave like the planner's launch-bound ones.
+  // S16 with an even number of steps: the next iteration's first step is in the buffer this one started from, no role swap.
+  // The pass is a macro, not a lambda around `iteration`: the two-pass tiles (T4P) expand it twice, and a closure around the
+  // `iteration` closure kept the accumulator arrays in memory (1.1 .. 1.8 KB of scratch in every tile that has the projection).
+#define LDP_TCONV_PASS(pass_tag) \
+  stage_load(pass_tag, it0); \
+  wload(S16 ? it0 * NSTEP : it0, wb0, rb0); \
+  stage_store(pass_tag, smem + (it0 & 1) * C::XT); \
+  __syncthreads(); \
+  LDP_TL(1); \
+  if (mode_2d(MODE) && !S16) { \
+    for (int it = it0; it < nit; it += 2) { \
+      iteration(pass_tag, std::false_type{}, it, wb0, rb0, wb1, rb1); \
+      if (it + 1 < nit) iteration(pass_tag, std::false_type{}, it + 1, wb1, rb1, wb0, rb0); \
+    } \
+  } else { \
+    int it = it0; \
+    if constexpr (S16 && NSTEP % 2 == 0) { \
+      for (; it + 1 < nit; ++it) iteration(pass_tag, std::false_type{}, it, wb0, rb0, wb1, rb1); \
+      iteration(pass_tag, std::true_type{}, it, wb0, rb0, wb1, rb1); \
+    } else { \
+    for (; it + 2 < nit; it += 2) { \
+      iteration(pass_tag, std::false_type{}, it, wb0, rb0, wb1, rb1); \
+      iteration(pass_tag, std::false_type{}, it + 1, wb1, rb1, wb0, rb0); \
+    } \
+    if (it + 2 == nit) { \
+      iteration(pass_tag, std::false_type{}, it, wb0, rb0, wb1, rb1); \
+      iteration(pass_tag, std::true_type{}, it + 1, wb1, rb1, wb0, rb0); \
+    } else if (it + 1 == nit) { \
+      iteration(pass_tag, std::true_type{}, it, wb0, rb0, wb1, rb1); \
+    } \
+    } \
+  }
+  auto t4_combine_pass = [&](auto pass_tag) {
+  if constexpr (T4S && !T4F) {      // y0 = s + e0 + p + dt0, y1 = s + e1 + p + dt1, y2 = s + e0 + q + db0, y3 = s + e1 + q + db1: from here on any other TO = 4 tile
+    constexpr int PASS = decltype(pass_tag)::value;
+#pragma unroll
+    for (int mm = 0; mm < MBE; ++mm) {
+      const int m = T4P ? PASS : mm;
+      const f32x4 se0 = tacc[mm][0] + tacc[mm][1], se1 = tacc[mm][0] + tacc[mm][2];
+      acc[m][0] = (se0 + tacc[mm][3]) + tacc[mm][4];
+      acc[m][1] = (se1 + tacc[mm][3]) + tacc[mm][5];
+      acc[m][2] = (se0 + tacc[mm][6]) + tacc[mm][7];
+      acc[m][3] = (se1 + tacc[mm][6]) + tacc[mm][8];
+#pragma unroll
+      for (int k = 0; k < T4_SLOTS; ++k) tacc[mm][k] = f32x4{0.f, 0.f, 0.f, 0.f};      // (two-pass tiles: the second row block starts from zero)
     }
   }
+  };
+  {
+    using pass0 = std::integral_constant<int, 0>;
+    LDP_TCONV_PASS(pass0{})
+    t4_combine_pass(pass0{});
+  }
+  if constexpr (T4P) {      // the second row block of the two-pass tiles
+    using pass1 = std::integral_constant<int, 1>;
+    LDP_TCONV_PASS(pass1{})
+    t4_combine_pass(pass1{});
+  }
+#undef LDP_TCONV_PASS
 
   if constexpr (T2S) {      // out0 = S + (W3 - W2) x1, out1 = S + (W1 - W2) x0: from here on the tile is any other TO = 2 tile
 #pragma unroll
