@@ -376,6 +376,24 @@ LDP_API int ldp_train_idm_grad(ldp_handle* h, const float* s, const float* a0, c
 LDP_API int ldp_train_vae_grad(ldp_handle* h, const float* img_nhwc, int32_t N, int32_t use_kl, float beta, const float* eps, uint64_t seed,
                                int64_t row_offset, float* metrics_out, void* stream);
 
+/* The gradient of PART of a batch: what chunked and data-parallel VAE training are built from.  The call differentiates the mean loss over
+ * n_total frames restricted to these N of them, i.e. (N / n_total) * grad loss(these N frames), so that the parts of a batch sum to the
+ * gradient of the whole batch: G(batch) = sum_c G(part c).  n_total enters at the two places where the batch size enters the backward pass
+ * (d rec = 2 (rec - img) / (n_total 3 S^2), and the beta ... / n_total terms of the posterior's backward), exactly where ldp_train_vae_grad
+ * uses N: there is no scaling pass over the arena, and n_total = N gives ldp_train_vae_grad's bits.
+ *   accumulate = 0: the gradients REPLACE module 4's gradient arena (ldp_train_vae_grad is this call with n_total = N, accumulate = 0).
+ *   accumulate = 1: they are ADDED to it element by element, old value first: the tape writes a second arena, and after its side streams
+ *     have joined one launch adds that to the gradient arena.  Every leaf takes part (the deferred column sums, the GroupNorm parameters,
+ *     the exact-zero key/bias); the arena's padding stays zero, and the zero frames that pad a part to 32 rows add exactly zero.  One
+ *     owner and one add per element, no atomics: the same calls in the same order give the same arena bit for bit.  The second arena
+ *     (the size of the gradient arena) is allocated by the first accumulate = 1 call; a process that never accumulates never has it.
+ * metrics_out receives the LDP_VAE_N_METRICS scalars of THESE N frames alone; the caller merges the parts' (StableVAEModel's
+ * merge_vae_metrics).  row_offset: the global index of the part's first frame, as in ldp_train_vae_grad (a frame's Philox eps does not
+ * depend on how the batch is cut).  LDP_EINVAL, with the limit in the message, for N < 1, N > 256, n_total < N, accumulate not 0 or 1,
+ * and everything ldp_train_vae_grad refuses (frames that are not 64 pixels among it).  Does not synchronise. */
+LDP_API int ldp_train_vae_grad_part(ldp_handle* h, const float* img_nhwc, int32_t N, int32_t n_total, int32_t accumulate, int32_t use_kl,
+                                    float beta, const float* eps, uint64_t seed, int64_t row_offset, float* metrics_out, void* stream);
+
 /* optax.global_norm over the gradient arenas of the listed modules (agent/ldp_agent.py:253) -> out[0] (device scalar).  Two-stage
  * reduction in a fixed order (bit-reproducible).  Called AFTER ldp_train_apply of the same gradients it costs one small launch: the optimiser
  * kernel leaves the per-stripe sums of squares behind (same stripes, same order: the same bits as the stand-alone first stage). */
@@ -409,7 +427,8 @@ LDP_API int ldp_train_write(ldp_handle* h, int32_t module, int32_t which, const 
  * ldp_train_*_grad).  The pointer stays valid until the next ldp_train_init / ldp_destroy.  This is the data-parallel seam: with the batch
  * rows split over processes (the reference shards its batch with PositionalSharding, utils/py_utils.py:27-39, and XLA inserts the gradient
  * all-reduce), the caller sums the gradient arenas over the ranks with ONE collective per module between ldp_train_*_grad and
- * ldp_train_grad_norm / ldp_train_apply, in order on `stream`. */
+ * ldp_train_grad_norm / ldp_train_apply, in order on `stream`.  Every trainable module uses it: the planner and the IDM, the VAE (module 4:
+ * after the last ldp_train_vae_grad_part of the rank's frames) and the image encoders (module 8 << slot: after ldp_train_encoder_backward). */
 LDP_API int ldp_train_arena(ldp_handle* h, int32_t module, int32_t which, float** dev_out, int64_t* numel_out);
 
 /* Make the sampling path use the trained parameters: master parameters -> the handle's weight store -> ldp_finalize of the listed

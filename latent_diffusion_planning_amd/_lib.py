@@ -21,6 +21,7 @@ SAMPLER_DDPM, SAMPLER_DDIM = 0, 1
 MOD_PLANNER, MOD_IDM, MOD_VAE, MOD_ENCODER = 1, 2, 4, 8
 RESNET_SLOTS, RESNET_FEATURES = 4, 1024       # encoder0 .. encoder3 of a handle; [expected_x (512) | expected_y (512)] per frame
 RESNET_TRAIN_MAX_FRAMES = 1024                # frames per ldp_train_encoder_forward (csrc/resnet_train.hpp RNT_MAX_FRAMES)
+VAE_TRAIN_MAX_FRAMES = 256                    # frames per ldp_train_vae_grad(_part) call (csrc/vae_train.hpp VAE_TRAIN_MAX_FRAMES)
 RESNET_CHUNK = 64                             # frames per pass of ldp_resnet_encode (csrc/resnet.hip RN_CHUNK)
 PHILOX_STREAM_VAE_EPS = 9          # LDP_PHILOX_STREAM_VAE_EPS: eps of the StableVAE posterior draw
 # LDP_VAE_METRIC_*: the keys of StableVAEModel.loss (model/stable_vae_model.py:42-53) in the order ldp_vae_metrics writes them
@@ -120,6 +121,7 @@ SIGNATURES: Dict[str, tuple] = {
     "ldp_train_encoder_backward": (C.c_int, [_H, C.c_int32, _FP, C.c_int32, C.c_void_p]),
     "ldp_train_idm_grad": (C.c_int, [_H, _FP, _FP, _FP, _FP, C.c_float, _FP, C.c_int32, C.c_void_p]),
     "ldp_train_vae_grad": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_float, _FP, C.c_uint64, C.c_int64, _FP, C.c_void_p]),
+    "ldp_train_vae_grad_part": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _FP, C.c_uint64, C.c_int64, _FP, C.c_void_p]),
     "ldp_train_grad_norm": (C.c_int, [_H, C.c_int32, _FP, C.c_void_p]),
     "ldp_train_apply": (C.c_int, [_H, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "ldp_train_step_count": (C.c_int, [_H, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),

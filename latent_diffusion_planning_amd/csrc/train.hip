@@ -1039,6 +1039,14 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   __syncthreads();
   if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
+// g += part, element by element with the old value first (ldp_train_vae_grad_part, accumulate = 1).  One element has one owner and one add: no
+// atomics, no order to vary.  n4 = floats / 4 (an arena is a whole number of 64-float leaf slots, and both bases come from hipMalloc).
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float4* __restrict__ g, const float4* __restrict__ part, long long n4) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const float4 a = g[i], b = part[i];
+  g[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
 // sum of squares: stage 1 one partial per block (fixed 1024-element stripes), stage 2 one wave
 __global__ __launch_bounds__(256) void sumsq1_kernel(const float* __restrict__ x, long long n, float* __restrict__ part) {
   __shared__ float red[4];
@@ -1088,6 +1096,7 @@ struct Module {
   size_t total = 0;               // floats (each leaf padded to a multiple of 64)
   DevBuf P, G, M, V, gpart;       // params, grads, Adam moments, sum-of-squares partials
   DevBuf E;                       // EMA of the parameters (ldp_train_ema), same layout as P
+  DevBuf Gpart;                   // the gradients of one part of a batch before they are added to G (allocated by the first accumulating call)
   bool ema_on = false;
   float ema_decay = 0.0f;
   bool gpart_fresh = false;       // gpart holds the stripes' sums of squares of the CURRENT gradients (left by ldp_train_apply)
@@ -2233,21 +2242,54 @@ int ldp_train_idm_grad(ldp_handle* h, const float* s, const float* a0, const flo
   return run_lane_tape(h, *ms, (hipStream_t)stream, [&](Ctx& c) { return idm_tape(c, s, a0, noise, t_dev, alpha, loss_out, R); });
 }
 
-int ldp_train_vae_grad(ldp_handle* h, const float* img_nhwc, int32_t N, int32_t use_kl, float beta, const float* eps, uint64_t seed, int64_t row_offset,
-                       float* metrics_out, void* stream) {
+// `who`: the exported call the messages name (ldp_train_vae_grad is the part with n_total = N, accumulate = 0)
+static int vae_grad_part(const char* who, ldp_handle* h, const float* img_nhwc, int32_t N, int32_t n_total, int32_t accumulate, int32_t use_kl, float beta,
+                         const float* eps, uint64_t seed, int64_t row_offset, float* metrics_out, void* stream) {
   if (!h) return fail(LDP_EINVAL, "null handle");
   if (h->cfg.image_size <= 0) return fail(LDP_EINVAL, "module 4 (vae): this handle was created with image_size = 0, it has no StableVAE");
   ModSlot* ms = nullptr;
   LDP_TRY(need_slot(h, 4, &ms));
-  if (!img_nhwc || !metrics_out || N <= 0 || row_offset < 0) return fail(LDP_EINVAL, "bad argument");
+  if (!img_nhwc || !metrics_out || row_offset < 0) return fail(LDP_EINVAL, "bad argument");
+  if (N <= 0) return fail(LDP_EINVAL, "bad argument: %s takes 1 to %d frames per call, got %d", who, VAE_TRAIN_MAX_FRAMES, N);
   if (h->cfg.image_size != 64)
-    return fail(LDP_EINVAL, "ldp_train_vae_grad: built and tested for 64-pixel frames, this handle has %d", h->cfg.image_size);
+    return fail(LDP_EINVAL, "%s: built and tested for 64-pixel frames, this handle has %d", who, h->cfg.image_size);
   if (N > VAE_TRAIN_MAX_FRAMES)
-    return fail(LDP_EINVAL, "ldp_train_vae_grad: %d frames, at most %d per call (the tape keeps every activation of the batch)", N, VAE_TRAIN_MAX_FRAMES);
+    return fail(LDP_EINVAL, "%s: %d frames, at most %d per call (the tape keeps every activation of the batch)", who, N, VAE_TRAIN_MAX_FRAMES);
+  if (n_total < N) return fail(LDP_EINVAL, "%s: n_total = %d, at least the %d frames of this part", who, n_total, N);
+  if (accumulate != 0 && accumulate != 1) return fail(LDP_EINVAL, "%s: accumulate = %d, it is 0 (replace the gradient arena) or 1 (add to it)", who, accumulate);
   if (!std::isfinite(beta)) return fail(LDP_EINVAL, "beta must be finite");
   LDP_HIP(hipSetDevice(h->cfg.device));
-  ms->m.gpart_fresh = false;
-  return run_lane_tape(h, *ms, (hipStream_t)stream, [&](Ctx& c) { return vae_tape(c, img_nhwc, N, use_kl != 0, beta, eps, seed, (uint64_t)row_offset, metrics_out); });
+  hipStream_t s = (hipStream_t)stream;
+  Module& m = ms->m;
+  m.gpart_fresh = false;
+  float* gdst = m.G.f();
+  if (accumulate) {
+    if (!m.Gpart.p) {                                                    // (a process that never accumulates never pays for it)
+      LDP_TRY(m.Gpart.alloc(m.total * 4));
+      LDP_HIP(hipMemsetAsync(m.Gpart.p, 0, m.total * 4, s));             // what no tape writes stays zero, as in G
+    }
+    gdst = m.Gpart.f();
+  }
+  LDP_TRY(run_lane_tape(h, *ms, s, [&](Ctx& c) {
+    return vae_tape(c, img_nhwc, N, n_total, gdst, use_kl != 0, beta, eps, seed, (uint64_t)row_offset, metrics_out);
+  }));
+  if (accumulate) {                                                      // behind the join: every side stream's gradients are in Gpart
+    const long long n4 = (long long)(m.total / 4);
+    hipLaunchKernelGGL(grad_accumulate_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<float4*>(m.G.f()),
+                       reinterpret_cast<const float4*>(m.Gpart.f()), n4);
+    LDP_HIP(hipGetLastError());
+  }
+  return LDP_OK;
+}
+
+int ldp_train_vae_grad(ldp_handle* h, const float* img_nhwc, int32_t N, int32_t use_kl, float beta, const float* eps, uint64_t seed, int64_t row_offset,
+                       float* metrics_out, void* stream) {
+  return vae_grad_part("ldp_train_vae_grad", h, img_nhwc, N, N, 0, use_kl, beta, eps, seed, row_offset, metrics_out, stream);
+}
+
+int ldp_train_vae_grad_part(ldp_handle* h, const float* img_nhwc, int32_t N, int32_t n_total, int32_t accumulate, int32_t use_kl, float beta,
+                            const float* eps, uint64_t seed, int64_t row_offset, float* metrics_out, void* stream) {
+  return vae_grad_part("ldp_train_vae_grad_part", h, img_nhwc, N, n_total, accumulate, use_kl, beta, eps, seed, row_offset, metrics_out, stream);
 }
 
 int ldp_train_grad_norm(ldp_handle* h, int32_t modules, float* out, void* stream) {

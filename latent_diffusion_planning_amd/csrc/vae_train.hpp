@@ -230,8 +230,9 @@ __global__ void vae_rec_grad_kernel(const float* __restrict__ rec, const float* 
 // backward of the posterior draw and the KL term: z = mean + exp(lv_c / 2) eps, lv_c = clip(lv, -30, 20), loss += beta mean_n KL_n with
 // KL_n = 0.5 sum (mean^2 + exp(lv_c) - 1 - lv_c):   d mean = dz + beta mean / N;   d lv = dz eps std / 2 + beta (exp(lv) - 1) / (2 N) inside the
 // clip, 0 outside.  mom / dz / dmom (Bp, E, CP) with channels [0, LC) mean and [LC, 2 LC) log-variance; eps as vae_posterior_kernel draws it.
+// NT: the frames the loss is the mean over (B, or the whole batch that these B frames are a part of: ldp_train_vae_grad_part).
 __global__ void vae_post_bwd_kernel(const float* __restrict__ mom, const float* __restrict__ dz, const float* __restrict__ eps, uint64_t seed,
-                                    uint64_t row0, float* __restrict__ dmom, int B, int Bp, int E, int LC, int CP, int use_kl, float beta) {
+                                    uint64_t row0, float* __restrict__ dmom, int B, int NT, int Bp, int E, int LC, int CP, int use_kl, float beta) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)Bp * E * CP) return;
   const int c = (int)(i % CP);
@@ -242,14 +243,14 @@ __global__ void vae_post_bwd_kernel(const float* __restrict__ mom, const float* 
     const int cc = c < LC ? c : c - LC;
     const float g = dz[np * CP + cc];
     if (c < LC) {
-      out = use_kl ? g + beta * mom[np * CP + cc] / (float)B : g;
+      out = use_kl ? g + beta * mom[np * CP + cc] / (float)NT : g;
     } else {
       const float lv = mom[np * CP + c];
       if (lv > -30.0f && lv < 20.0f) {
         const uint64_t per = (uint64_t)E * (uint64_t)LC, e = (uint64_t)pix * LC + cc;
         const float ep = eps ? eps[(size_t)n * per + e] : philox_normal(seed, (row0 + (uint64_t)n) * per + e, 0u, LDP_PHILOX_STREAM_VAE_EPS);
         out = g * ep * expf(0.5f * lv) * 0.5f;
-        if (use_kl) out += beta * (expf(lv) - 1.0f) / (2.0f * (float)B);
+        if (use_kl) out += beta * (expf(lv) - 1.0f) / (2.0f * (float)NT);
       }
     }
   }
@@ -347,14 +348,16 @@ struct VaeOp {
 };
 
 // ---- the StableVAE: loss + gradients (model/stable_vae_model.py:25-73; diffusers FlaxAutoencoderKL) -------------------------------------
-int vae_tape(Ctx& c, const float* img, int B, int use_kl, float beta, const float* eps, uint64_t seed, uint64_t row0, float* metrics) {
+// n_total >= B: the frames of the batch whose mean loss is differentiated (these B are a part of it; the metrics are these B frames' alone);
+// gdst: the arena the gradients are written to (the module's own, or the part buffer that ldp_train_vae_grad_part adds to it afterwards)
+int vae_tape(Ctx& c, const float* img, int B, int n_total, float* gdst, int use_kl, float beta, const float* eps, uint64_t seed, uint64_t row0, float* metrics) {
   Trainer& t = *c.t;
   Module& m = *c.M;
   const int S = c.h->cfg.image_size, LC = c.h->cfg.vae_latent_channels, Bp = rup(B, RP), HW = S * S;
   const int hl = S >> (VAE_NB - 1), E = hl * hl, CL = RP;      // CL: padded width of the image / latent-side tensors
   c.L->ws_used = 0;
   auto P = [&](const std::string& path) { return m.P.f() + m.leaf(path).off; };
-  auto Gd = [&](const std::string& path) { return m.G.f() + m.leaf(path).off; };
+  auto Gd = [&](const std::string& path) { return gdst + m.leaf(path).off; };
   auto take = [&](size_t n) { return ws_take(*c.L, n); };
   std::vector<VaeOp> ops;
   int err = LDP_OK;                                           // the first failed launch of the forward lambdas below
@@ -492,7 +495,7 @@ int vae_tape(Ctx& c, const float* img, int B, int use_kl, float beta, const floa
     LDP_TRY(vae_metrics_final_launch(ipart, nib, zpart, nzb, kl, B, use_kl, beta, metrics, c.s));
   }
   float* d = take((size_t)Bp * HW * CL);
-  TK(vae_rec_grad_kernel, g1((long long)Bp * HW * CL), dim3(256), rec, img, d, B, Bp, HW, CL, (float)(2.0 / (3.0 * (double)B * HW)));
+  TK(vae_rec_grad_kernel, g1((long long)Bp * HW * CL), dim3(256), rec, img, d, B, Bp, HW, CL, (float)(2.0 / (3.0 * (double)n_total * HW)));
 
   // ---- backward: one op at a time, last first; weight-gradient work on the side streams -------------------------------------------------
   auto bwd = [&](const VaeOp& op, const float* dy, bool need_dx, float** dx_out) -> int {
@@ -585,7 +588,7 @@ int vae_tape(Ctx& c, const float* img, int B, int use_kl, float beta, const floa
     d = dx;
   }
   float* dmom = take((size_t)Bp * E * CL);                   // d is now d z (Bp, E, CL)
-  TK(vae_post_bwd_kernel, g1((long long)Bp * E * CL), dim3(256), mom, d, eps, seed, row0, dmom, B, Bp, E, LC, CL, use_kl, beta);
+  TK(vae_post_bwd_kernel, g1((long long)Bp * E * CL), dim3(256), mom, d, eps, seed, row0, dmom, B, n_total, Bp, E, LC, CL, use_kl, beta);
   d = dmom;
   for (size_t i = n_enc; i-- > 0;) {
     float* dx = nullptr;

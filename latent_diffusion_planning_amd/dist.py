@@ -84,14 +84,17 @@ def sample_sharded(agent, batch: dict, eval_rng, group=None, **kw):
 
 
 def update_sharded(agent, batch: dict, rng, step: int, group=None, mixed_batch=None, noise=None):
-    """`agent.update(batch, rng, step)` / `agent.update_mixed(batch, mixed_batch, rng, step)` (agent/ldp_agent.py:223-323; LDPHierAgent alike) with the batch rows
-    split over the ranks of `group`: the MI355X counterpart of the reference's training-time PositionalSharding (utils/py_utils.py:27-39 +
-    jit: XLA inserts the gradient all-reduce).  Every rank passes the FULL batch(es) and keeps a full replica of parameters and Adam state;
+    """`agent.update(batch, rng, step)` / `agent.update_mixed(batch, mixed_batch, rng, step)` (agent/ldp_agent.py:223-323) with the batch rows
+    split over the ranks of `group`, for every trainable class: LDPAgent, LDPHierAgent, DPVAEAgent, DPTrainAgent (the U-Net's and every image
+    encoder's arena) and StableVAEModel (each camera's rows are one run of global frames; `noise` is its eps array).  It is
+    the MI355X counterpart of the reference's training-time PositionalSharding (utils/py_utils.py:27-39 + jit: XLA inserts the gradient
+    all-reduce, used by train_bc.py:70-78 and train_vae.py:80-88).  Every rank passes the FULL batch(es) and keeps a full replica of parameters and Adam state;
     a rank computes forward / backward of its rows only, the flat gradient arena of each trained module crosses the wire ONCE (one RCCL
     all-reduce per module, in place on the engine's memory, on the launch stream) and global norm + Adam run replicated, so the replicas
     never diverge.  Timesteps and noise are keyed by the global row index: the step equals the one-GPU step of the whole batch to fp32
     round-off, for any world size.  Shards may be ragged (losses are weighted rows / total rows) but not empty.
-    The statistics scalars of the metrics dict (emb_*, action_*, <obs key>_*) describe this rank's rows."""
+    The statistics scalars of the metrics dict (emb_*, action_*, <obs key>_*, DPTrainAgent's obs_*) describe this rank's rows; the
+    StableVAE's eleven metrics are merged over the ranks (one all_gather of 12 floats) and describe the GLOBAL batch on every rank."""
     on = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if on else 1
     rank = dist.get_rank(group) if on else 0

@@ -82,10 +82,23 @@ class DPTrainAgent(DPAgent):
         return [self._frames(obs[k]).reshape(-1, 64, 64, 3) for k in cfg["rgb_obs"]]
 
     # ---- agent/dp_agent.py:112-136 ------------------------------------------------------------------
+    def _gates(self, step):
+        """update() trains the U-Net and the encoders on every step: (use_planner, use_idm) for dist.update_sharded."""
+        return True, False
+
     def update(self, batch, rng, step, noise=None):
         """-> (new agent, metrics).  rng: seed of the timesteps (host PCG64) and of the noise (device Philox stream 7), as
         DPVAEAgent.update; noise: optional explicit dict(t (B,), noise (B, T, A)) for parity runs.  metrics: loss, obs_min / obs_max /
         obs_mean / obs_std of obs_cond, planner_lr / planner_step and enc_<key>_lr / enc_<key>_step (the OLD states' counts, :128-135)."""
+        return self._update_step(batch, None, rng, True, False, noise)
+
+    def _update_step(self, batch, mixed_batch, rng, use_planner, use_idm, noise, shard=None):
+        """shard (dist.update_sharded): dict(group, rows=(lo, n)) -- `batch` holds rows [lo, lo + B) of a global batch of n: timesteps and
+        noise of the global rows, the U-Net's loss weighted B / n (its condition gradient, and so the encoders' backward, carry the
+        weight), ONE all-reduce of the gradient arena per trained module (the U-Net and every encoder slot) and of the loss, Adam and
+        the EMAs replicated.  The obs_* statistics describe this rank's rows; the frame limit applies to this rank's frames."""
+        if mixed_batch is not None or use_idm:
+            raise NotImplementedError("DPTrainAgent trains one policy on one batch")
         if self._lr_schedules is None:
             raise ValueError("update() needs the optimiser settings of DPTrainAgent.create (lr, end_lr, warmup_steps, decay_steps)")
         cfg, eng = self.config, self._engine
@@ -117,12 +130,28 @@ class DPTrainAgent(DPAgent):
         stats = eng.reduce_stats(cond)
         hg = np.random.Generator(np.random.PCG64(seed & (2**63 - 1)))
         t = nz.get("t")
-        t = np.asarray(hg.integers(0, int(cfg["n_diffusion_steps"]), size=B) if t is None else t).reshape(-1)
+        lo, n = (0, B) if shard is None else shard["rows"]
+        t = np.asarray(hg.integers(0, int(cfg["n_diffusion_steps"]), size=n) if t is None else t).reshape(-1)
+        if len(t) == n and n != B:
+            t = t[lo:lo + B]
         eps = nz.get("noise")
-        eps = self._t(eps) if eps is not None else _philox_normal(seed, 0, 0, 7, action.numel(), self._device).reshape(action.shape)
-        loss, dcond = eng.train_planner_grad_cond(action, eps, t, cond)
+        if eps is not None:
+            eps = self._t(eps[lo:lo + B] if len(eps) == n and n != B else eps)
+        else:
+            eps = _philox_normal(seed, lo * (action.numel() // B), 0, 7, action.numel(), self._device).reshape(action.shape)
+        if shard is None:
+            loss, dcond = eng.train_planner_grad_cond(action, eps, t, cond)
+        else:
+            loss, dcond = eng.train_planner_grad_cond(action, eps, t, cond, float(np.float32(B) / np.float32(n)))
         for i, d in enumerate(dp_image_cond_inverse(dcond, [x.shape[0] // B for x in frames])):
             eng.train_encoder_backward(i, d)
+        if shard is not None:                                       # data parallel: the B / n weighted shard gradients sum to the global batch's
+            import torch.distributed as tdist
+            for mod in mods:
+                tdist.all_reduce(eng.train_arena(mod, eng.TRAIN_GRADS), group=shard.get("group"))
+            loss = loss.reshape(1).clone()
+            tdist.all_reduce(loss, group=shard.get("group"))
+            loss = loss.reshape(())
         m, new, scheds = {}, [], self._lr_schedules
         for mod, st, sh, name in zip(mods, states, shapes, ["planner"] + [f"enc_{k}" for k in keys]):
             lr = np.float32(scheds["planner" if mod == "planner" else keys[int(mod[-1])]](st.step))

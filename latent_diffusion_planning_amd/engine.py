@@ -636,7 +636,29 @@ class HipEngine:
         out = torch.empty((len(_lib.VAE_METRIC_KEYS),), device=self.device, dtype=torch.float32)
         check(self.lib.ldp_train_vae_grad(self._h, _ptr(img), n, int(bool(use_kl)), C.c_float(float(beta)), _ptr(eps), seed_c, row_c, _ptr(out),
                                           self._stream()))
-        self._keep_v = (img, eps)                      # the launches are asynchronous: the inputs must outlive them
+        self._keep_v = [(img, eps)]                    # the launches are asynchronous: the inputs must outlive them
+        return out
+
+    def train_vae_grad_part(self, img: torch.Tensor, n_total: int, accumulate: bool, use_kl: bool = True, beta: float = 1e-5, seed: int = 0,
+                            noise: Optional[torch.Tensor] = None, row_offset: int = 0) -> torch.Tensor:
+        """train_vae_grad for PART of a batch (ldp_train_vae_grad_part): img holds N of the `n_total` frames whose mean loss is trained on,
+        the first of them global frame `row_offset`; the gradients are (N / n_total) * those of these frames' own mean loss, and they
+        replace the gradient arena (accumulate False: the first part of a step) or are added to it (True: every later part) -> the eleven
+        metrics of THESE frames as an (11,) device tensor (vae_model.merge_vae_metrics merges the parts')."""
+        img = _f32(img, self.device)
+        if img.dim() != 4:
+            raise ValueError(f"img must have shape (N, {self.image_size}, {self.image_size}, 3), got {tuple(img.shape)}")
+        n = img.shape[0]
+        _want("img", img, (n, self.image_size, self.image_size, 3))
+        if not np.isfinite(float(beta)):
+            raise ValueError(f"beta must be finite, got {beta}")
+        eps, seed_c, row_c = self._vae_noise_args(noise, n, seed, row_offset)
+        out = torch.empty((len(_lib.VAE_METRIC_KEYS),), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_train_vae_grad_part(self._h, _ptr(img), n, int(n_total), int(accumulate), int(bool(use_kl)), C.c_float(float(beta)),
+                                               _ptr(eps), seed_c, row_c, _ptr(out), self._stream()))
+        if not accumulate or getattr(self, "_keep_v", None) is None:
+            self._keep_v = []                          # a new step begins: the previous step's inputs may go
+        self._keep_v.append((img, eps))                # every part's inputs outlive their launches
         return out
 
     def train_grad_norm(self, modules) -> torch.Tensor:

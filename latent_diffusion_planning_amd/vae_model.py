@@ -63,6 +63,30 @@ def _check_vae_cfg(vae) -> W.VAESpec:
     return W.VAESpec(latent_channels=lc)
 
 
+def merge_vae_metrics(vectors, frame_counts, use_kl, beta) -> torch.Tensor:
+    """The eleven metrics (_lib.VAE_METRIC_KEYS order) of a batch from those of its parts: `vectors` one (11,) device tensor per part,
+    `frame_counts` the parts' frames (ints, or a device tensor).  min / max: of the parts; means, loss_mse and loss_kl: weighted by frames
+    (every frame has the same number of pixels and of latent entries); std: var = sum_i w_i (std_i^2 + (mean_i - mean)^2); loss =
+    loss_mse + beta loss_kl (loss_mse without the KL term).  Float64 on the tensors' device, no host synchronisation -> (11,) float32."""
+    v = [x.reshape(-1).double() for x in vectors]
+    if torch.is_tensor(frame_counts):
+        c = frame_counts.reshape(-1).to(device=v[0].device, dtype=torch.float64)
+        w = list(c / c.sum())
+    else:
+        total = float(sum(frame_counts))
+        w = [float(c) / total for c in frame_counts]
+    K = {k: i for i, k in enumerate(_lib.VAE_METRIC_KEYS)}
+    out = sum(wi * x for wi, x in zip(w, v))                                    # the weighted means; the other entries are replaced below
+    both = torch.stack(v)
+    for k in ("img", "z"):
+        out[K[k + "_min"]] = both[:, K[k + "_min"]].min()
+        out[K[k + "_max"]] = both[:, K[k + "_max"]].max()
+        s, m = K[k + "_std"], K[k + "_mean"]
+        out[s] = sum(wi * (x[s] * x[s] + (x[m] - out[m]) ** 2) for wi, x in zip(w, v)).sqrt()
+    out[K["loss"]] = out[K["loss_mse"]] + float(beta) * out[K["loss_kl"]] if use_kl else out[K["loss_mse"]]
+    return out.float()
+
+
 class StableVAEModel(_EngineCalls):
     def __init__(self, vae_state: DPState, obs_normalization, config, engine: Optional[HipEngine], vae_spec: W.VAESpec, image_size: int,
                  device, lr_schedule=None, ema_decay: float = 0.99):
@@ -244,11 +268,44 @@ class StableVAEModel(_EngineCalls):
     # ---- model/stable_vae_model.py:57-73 ---------------------------------------------------------------------------------------------
     TRAIN_SIZES = (64,)                       # frame sizes the training tape is built and tested for
 
-    def update(self, batch, rng, step, noise=None, row_offset: int = 0):
+    def _gates(self, step):
+        """update() trains the VAE on every step: (use_planner, use_idm) in the form dist.update_sharded asks every trainable class for."""
+        return True, False
+
+    def update(self, batch, rng, step, noise=None, row_offset: int = 0, chunk=None):
         """`update_step`: jax.grad of `loss` on `params`, one optax.adam step with the warmup-cosine schedule, then the EMA -> (new model,
         metrics).  metrics: the eleven keys of `loss` on the pre-update parameters (device scalars, as get_metrics), then vae_lr =
         schedule(old step) and vae_step = old step.  rng / noise / row_offset: the eps of the posterior draw, as get_metrics (the same seed draws
-        the same eps here and there).  `step` is unused, as in the reference."""
+        the same eps here and there).  `step` is unused, as in the reference.
+        chunk: at most this many frames per gradient call (1 .. 256, default 256).  A batch of more frames is differentiated part by part
+        into the same gradient arena (ldp_train_vae_grad_part): one Adam step on the whole batch's gradient at the activation memory of
+        `chunk` frames; the metrics are those of the whole batch (merge_vae_metrics)."""
+        return self._update_step(batch, None, rng, True, False, noise, row_offset=row_offset, chunk=chunk)
+
+    def _parts(self, n_local: int, n_cams: int, rows, row_offset: int, chunk: int):
+        """The ONE rule that cuts a step's frames into gradient calls -> [(first local frame, frames, first global index)].  This process's
+        frames in `_frames` order (cameras concatenated on the batch axis); frame b of camera `cam` has the global index
+        row_offset + cam * n_rows_global + first_row + b.  A new part starts where the index is not the previous one plus 1, or when the
+        part holds `chunk` frames."""
+        lo, n = rows
+        parts, prev = [], None
+        for cam in range(n_cams):
+            for b in range(n_local):
+                g = row_offset + cam * n + lo + b
+                if prev is None or g != prev + 1 or parts[-1][1] == chunk:
+                    parts.append([cam * n_local + b, 0, g])
+                parts[-1][1] += 1
+                prev = g
+        return [tuple(p) for p in parts]
+
+    def _update_step(self, batch, mixed_batch, rng, use_planner, use_idm, noise, shard=None, row_offset: int = 0, chunk=None):
+        """shard (dist.update_sharded): dict(group, rows=(lo, n)) -- `batch` holds rows [lo, lo + B) of a global batch of n rows per camera.
+        Every camera's rows are one run of global frames (cam * n + lo ...), each differentiated with the weight frames / (cameras * n);
+        ONE all-reduce of the gradient arena after the last part, Adam and the EMA replicated; the metrics are those of the GLOBAL batch
+        on every rank (one all_gather of 12 floats per rank, merged in rank order).  noise: eps of the global frames or of exactly the
+        local ones."""
+        if mixed_batch is not None or use_idm:
+            raise NotImplementedError("StableVAEModel trains one network on one batch")
         eng = self._engine
         if not hasattr(eng, "train_vae_grad"):
             raise NotImplementedError("StableVAEModel.update: this engine has no backward pass of the 2-D convolutions (HipEngine.train_vae_grad); "
@@ -258,17 +315,48 @@ class StableVAEModel(_EngineCalls):
                                       f"this model takes {self._image_size}-pixel frames")
         if self.lr_schedule is None:
             raise ValueError("update() needs the optimiser settings of StableVAEModel.create (lr, end_lr, warmup_steps, decay_steps)")
+        chunk = _lib.VAE_TRAIN_MAX_FRAMES if chunk is None else int(chunk)
+        if not 1 <= chunk <= _lib.VAE_TRAIN_MAX_FRAMES:
+            raise ValueError(f"chunk={chunk}: a gradient call takes 1 to {_lib.VAE_TRAIN_MAX_FRAMES} frames")
         seed = _seed_of(rng)
         use_kl, beta = bool(self.config["use_kl"]), float(self.config["beta"])
         eps = None if noise is None else self._t(noise)
         st = self.vae_state
         lr = np.float32(self.lr_schedule(st.step))
         shapes = self._shapes()
+        n_cams = len(self.config["rgb_obs"])
 
         def run():
             self._train_sync(st)
             img = self._frames(batch, self.config["rgb_obs"])
-            out = eng.train_vae_grad(img, use_kl, beta, seed=seed, noise=eps, row_offset=row_offset)
+            n_local = img.shape[0] // n_cams
+            rows = (0, n_local) if shard is None else shard["rows"]
+            n_total = n_cams * int(rows[1])
+            parts = self._parts(n_local, n_cams, rows, int(row_offset), chunk)
+            if eps is not None and eps.shape[0] not in (n_total, img.shape[0]):
+                raise ValueError(f"noise holds {eps.shape[0]} frames: give the eps of the {n_total} global frames or of the {img.shape[0]} local ones")
+            is_global = eps is not None and eps.shape[0] == n_total
+
+            def eps_of(first, cnt, g0):
+                if eps is None:
+                    return None
+                a = g0 - int(row_offset) if is_global else first
+                return eps[a:a + cnt]
+            if len(parts) == 1 and parts[0][1] == n_total:                      # the whole batch in one call: the call it has always been
+                out = eng.train_vae_grad(img, use_kl, beta, seed=seed, noise=eps, row_offset=parts[0][2])
+            else:
+                vecs = [eng.train_vae_grad_part(img[first:first + cnt], n_total, k > 0, use_kl, beta, seed=seed, noise=eps_of(first, cnt, g0),
+                                                row_offset=g0) for k, (first, cnt, g0) in enumerate(parts)]
+                out = vecs[0] if len(vecs) == 1 else merge_vae_metrics(vecs, [p[1] for p in parts], use_kl, beta)
+            if shard is not None:                                               # data parallel: the weighted shard gradients sum to the global batch's
+                import torch.distributed as tdist
+                group = shard.get("group")
+                tdist.all_reduce(eng.train_arena("vae", eng.TRAIN_GRADS), group=group)
+                mine = torch.cat([out.reshape(-1).float(), torch.full((1,), float(img.shape[0]), dtype=torch.float32, device=out.device)])
+                every = [torch.empty_like(mine) for _ in range(tdist.get_world_size(group))]
+                tdist.all_gather(every, mine, group=group)
+                every = torch.stack(every)
+                out = merge_vae_metrics(list(every[:, :-1]), every[:, -1], use_kl, beta)
             eng.train_apply("vae", float(lr))                                   # Adam + EMA, one launch
             return [out]
         # the tape runs on exact-fp32 kernels only (no range guard, no in-launch exchange): a later fault poll has nothing to recompute here,
