@@ -189,6 +189,48 @@ LDP_API int ldp_policy_sample(ldp_handle* h, const float* obs_emb, int32_t obs_f
                       int32_t n_steps, float* action_out, const float* act_lo, const float* act_hi, int32_t act_dim,
                       int32_t act_mode, int32_t B, int32_t use_graph, void* stream);
 
+/* -- best-of-N planning (defined by this repo; the reference draws one plan per observation) ----------------
+ * B observations, N candidate plans each, K = T * D floats per candidate.  Rows are CANDIDATE-MAJOR everywhere below: global candidate
+ * row r = c * B + b (candidate c of observation b), so a candidate range [c0, c0 + n_loc) is the contiguous row range
+ * [c0 * B, (c0 + n_loc) * B) -- one rank's shard -- and with N = 1 row b is ldp_plan_sample's row b.  Lower cost is better.
+ *
+ * ldp_plan_candidates: the planner loop of ldp_plan_sample on the n_loc * B rows of candidates [c0, c0 + n_loc):
+ *   cond[r] = obs_emb[r mod B, :obs_horizon].reshape(-1)        (one kernel, into handle memory; no tiled copy on the caller's side)
+ *   x_out   = ldp_plan_sample(cond, x_init, step_noise, seed, row_offset = c0 * B, ...)   (that very call: its graph cache, range guard,
+ *             fault protocol and batch split; the Philox stream of a candidate is keyed by its global row c * B + b)
+ * obs_emb (B, obs_frames, D) as in ldp_agent_sample; x_init (n_loc * B, T, D) / step_noise (n_steps, n_loc * B, T, D): explicit-noise
+ * parity inputs of THESE rows, or NULL; x_out (n_loc * B, T, D).  LDP_EINVAL: B < 1, c0 < 0, n_loc < 1, an obs_horizon that does not
+ * match global_cond_dim. */
+LDP_API int ldp_plan_candidates(ldp_handle* h, const float* obs_emb, int32_t obs_frames, int32_t obs_horizon, int32_t B, int32_t c0,
+                                int32_t n_loc, const float* x_init, const float* step_noise, uint64_t seed, int32_t sampler,
+                                int32_t n_steps, float* x_out, int32_t use_graph, void* stream);
+
+/* score "density" (mode seeking): for the candidates i in [c0, c0 + n_loc) of every observation b
+ *   cost_i = - sum_{j = 0 .. N-1} exp(-d2_ij / (2 h2)),  d2_ij = sum_k (x_ik - x_jk)^2,  h2 = bandwidth^2 * m_b,
+ *   m_b = 2 * sum_k Var_k (biased variance over the N candidates) = the mean of d2 over all N^2 ordered pairs of observation b.
+ * x_all (N * B, K): ALL candidates (every rank holds them); cost_out (n_loc * B): cost_out[(i - c0) * B + b].
+ * m_b in float64 from all N candidates in a fixed order; d2 by direct differences in k order 0 .. K-1 (fp32 FMA chain; never
+ * |x|^2 + |y|^2 - 2 x.y); the sum over j strictly in the order 0 .. N-1 in fp32.  No atomics, and nothing depends on c0 or n_loc: a
+ * candidate's cost has the same bits whichever range (rank) computes it.  m_b = 0 (all candidates equal, N = 1): every cost is -N.
+ * Stand-alone (no handle); two launches on `stream` and one stream-ordered allocation of B floats, nothing synchronises.
+ * LDP_EINVAL, naming the argument: B < 1, N < 1, K < 1, c0 < 0, n_loc < 1, c0 + n_loc > N, bandwidth not finite or <= 0. */
+LDP_API int ldp_plan_cost_density(const float* x_all, int32_t B, int32_t N, int32_t K, int32_t c0, int32_t n_loc, float bandwidth,
+                                  float* cost_out, void* stream);
+
+/* score "goal": cost[c * B + b] = sum_d weight[d] * (x[c * B + b, t_goal, d] - goal[b, d])^2 for the n candidates of this call
+ * (x (n * B, T, D), any candidate range: a row's cost reads that row only), d in the order 0 .. D-1, fp32.  goal (B, D) normalised
+ * embeddings, weight (D) non-negative (not checked: device memory), cost_out (n * B).  Stand-alone, one launch.
+ * LDP_EINVAL: B, n, T, D < 1, t_goal outside 0 .. T-1. */
+LDP_API int ldp_plan_cost_goal(const float* x, int32_t B, int32_t n, int32_t T, int32_t D, int32_t t_goal, const float* goal,
+                               const float* weight, float* cost_out, void* stream);
+
+/* The winner of every observation: best_index_out[b] = argmin_c cost_all[c * B + b] over c = 0 .. N-1, ties to the lowest c, a NaN
+ * cost compared as +inf (all NaN / +inf: c = 0); best_cost_out[b] = that cost as stored; x_best_out[b] = x_all[best * B + b] (K floats,
+ * a copy: the candidate's bits).  cost_all (N * B), x_all (N * B, K), best_index_out (B) int32, best_cost_out (B), x_best_out (B, K).
+ * One work-group per observation, fixed comparison order.  Stand-alone, one launch.  LDP_EINVAL: B, N, K < 1. */
+LDP_API int ldp_plan_select(const float* cost_all, const float* x_all, int32_t B, int32_t N, int32_t K, int32_t* best_index_out,
+                            float* best_cost_out, float* x_best_out, void* stream);
+
 /* -- StableVAE ----------------------------------------------------------------------------
  * FlaxAutoencoderKL.encode(x).latent_dist.mean   (call site agent/ldp_agent.py:55-60)
  * img (N, S, S, 3) NHWC already normalised to [-1,1] -> mean (N, S/32, S/32, latent_channels)

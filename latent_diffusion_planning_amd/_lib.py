@@ -72,6 +72,11 @@ SIGNATURES: Dict[str, tuple] = {
     "ldp_unet_forward": (C.c_int, [_H, _FP, _FP, C.c_int32, _FP, _FP, C.c_int32, C.c_void_p]),
     "ldp_plan_sample": (C.c_int, [_H, _FP, _FP, _FP, C.c_uint64, C.c_int64, C.c_int32, C.c_int32,
                                   _FP, C.c_int32, C.c_int32, C.c_void_p]),
+    "ldp_plan_candidates": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_uint64, C.c_int32,
+                                      C.c_int32, _FP, C.c_int32, C.c_void_p]),
+    "ldp_plan_cost_density": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _FP, C.c_void_p]),
+    "ldp_plan_cost_goal": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, C.c_void_p]),
+    "ldp_plan_select": (C.c_int, [_FP, _FP, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, C.c_void_p]),
     "ldp_idm_forward": (C.c_int, [_H, _FP, _FP, _FP, C.c_int32, _FP, C.c_int32, C.c_void_p]),
     "ldp_idm_sample": (C.c_int, [_H, _FP, _FP, _FP, C.c_uint64, C.c_int64, C.c_int32, C.c_int32,
                                  _FP, C.c_int32, C.c_int32, C.c_void_p]),

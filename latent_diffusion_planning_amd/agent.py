@@ -816,6 +816,120 @@ class LDPAgent(_EngineCalls):
         metrics["plan_viz"] = viz
         return action, metrics
 
+    # ---- best-of-N planning (defined by this repository: DESIGN.md 4.14; csrc/select.hip) ----------------------------------
+    def _goal_embedding(self, goal, B):
+        """`goal`: normalised embeddings (B, D), or an observation dict in batch['obs'] form (embedded like the batch, frame 0)."""
+        if isinstance(goal, Mapping):
+            obs = self._vae_encode_t(self._postprocess({"obs": goal})["obs"])
+            g = self.get_obs_cond(obs)[:, 0]
+        else:
+            g = self._t(goal)
+        if tuple(g.shape) != (B, self.config["obs_dim"]):
+            raise ValueError(f"goal must embed to shape {(B, self.config['obs_dim'])}, got {tuple(g.shape)}")
+        return g.contiguous()
+
+    def _best_of(self, batch, seed, N, score, bandwidth, goal, goal_weight, t_goal, sampler, n_steps, idm_steps, noise, shard=None):
+        """The steps of sample_best_of as device tensors -> [action, plan, best_index, best_cost, costs (B, N), candidates (B, N, T, D)].
+        shard = (group, world, rank) (dist.sample_best_of_sharded): this rank draws and costs the candidates shard_bounds(N, world, rank);
+        candidates and costs cross the ranks once each.  Whatever leaves the rank, and the redundant tail, is completed first (stream
+        synchronised, fault word polled, recomputed on a fault): gathered copies could never be recalled."""
+        from .dist import all_gather_rows, shard_bounds
+        from .engine import check_candidate_range
+        check_candidate_range(1, N, 1, bandwidth=bandwidth if score == "density" else None)
+        cfg, eng = self.config, self._engine
+        oh, ah, T, D = cfg["obs_horizon"], cfg["action_horizon"], cfg["pred_horizon"], cfg["obs_dim"]
+        nz = noise or {}
+        c0, c1 = (0, N) if shard is None else shard_bounds(N, shard[1], shard[2])
+
+        def checked(fn):
+            if shard is None:
+                return fn()
+            for _ in range(3):
+                out = self._guarded(fn)
+                torch.cuda.current_stream(self._device).synchronize()
+                if not sum(e.poll_fault_kinds() for e in self._engines()):
+                    return out
+            raise RuntimeError("libldp_hip faulted again after switching to safe mode / bf16 planes")
+
+        def gather(t):                                         # (n_loc, ...) of this rank's candidates -> (N, ...), in candidate order
+            return t if shard is None or shard[1] == 1 else all_gather_rows(t.reshape(t.shape[0], -1).contiguous(), N, shard[0])
+
+        self._sync_weights()
+        obs_emb = checked(lambda: self.get_obs_cond(self._vae_encode_t(self._postprocess(batch)["obs"])).contiguous())
+        B = obs_emb.shape[0]
+        xi, xn = nz.get("x_init"), nz.get("x_noise")
+        if xi is not None:
+            xi = self._t(xi)[c0 * B:c1 * B]
+        if xn is not None:
+            xn = self._t(xn)[:, c0 * B:c1 * B]
+        if c1 > c0:
+            x_loc = checked(lambda: eng.plan_candidates(obs_emb, oh, N, c0=c0, n_loc=c1 - c0, x_init=xi, step_noise=xn, seed=seed,
+                                                        sampler=sampler, n_steps=n_steps))
+        else:                                                  # more ranks than candidates
+            x_loc = torch.zeros((0, T, D), device=self._device)
+        x_all = gather(x_loc.reshape(c1 - c0, B * T * D)).reshape(N * B, T, D)
+        if callable(score):                                    # every rank scores all candidates: nothing to gather
+            cand = x_all.reshape(N, B, T, D).transpose(0, 1).contiguous()
+            costs = as_tensor(score(cand))
+            if tuple(costs.shape) != (B, N) or not costs.is_cuda:
+                raise ValueError(f"score(candidates) must return a device tensor of shape {(B, N)}, got {tuple(costs.shape)} on {costs.device}")
+            cost_all = costs.to(dtype=torch.float32).t().contiguous()
+        else:
+            if score == "density":
+                cost_loc = eng.plan_cost_density(x_all, B, bandwidth, c0=c0, n_loc=c1 - c0) if c1 > c0 else None
+            elif score == "goal":
+                if goal is None:
+                    raise ValueError('score="goal" needs goal= (embeddings (B, D) or an observation dict)')
+                g = checked(lambda: self._goal_embedding(goal, B))
+                cost_loc = eng.plan_cost_goal(x_all[c0 * B:c1 * B], B, g, goal_weight, t_goal) if c1 > c0 else None
+            else:
+                raise ValueError(f'score must be "density", "goal" or a callable, got {score!r}')
+            cost_all = gather(torch.zeros((0, B), device=self._device) if cost_loc is None else cost_loc).reshape(N, B)
+
+        def tail():
+            idx, best, x_best = eng.plan_select(cost_all, x_all, B)
+            plan = torch.cat([obs_emb[:, oh - 1:oh], x_best[:, :ah]], dim=1)
+            action = self._idm_actions(plan[:, :-1], plan[:, 1:], seed, B, nz, sampler=sampler, n_steps=idm_steps)
+            return [action, plan, idx, best]
+        return checked(tail) + [cost_all.t().contiguous(), x_all.reshape(N, B, T, D).transpose(0, 1).contiguous()]
+
+    def sample_best_of(self, batch, eval_rng, n_candidates, score="density", bandwidth=0.5, goal=None, goal_weight=None, t_goal=None,
+                       sampler="ddpm", n_steps=None, idm_steps=None, noise=None, decode=False):
+        """Draw n_candidates plans per observation, score them on the GPU, act on the best one
+        -> (action (B, ah, A), metrics): the action of the winning plan through the IDM, and
+           metrics = {'plan' (B, ah+1, D), 'plan_viz' (lazy unless decode), 'best_index' (B,), 'best_cost' (B,), 'costs' (B, N),
+                      'candidates' (B, N, T, D)}, all DeviceArrays of one call record, like sample_viz's.
+        Candidate c of observation b is global planner row c * B + b (its Philox stream; with n_candidates = 1 row b is sample()'s row b).
+        score: "density" -- cost_i = -sum_j exp(-|x_i - x_j|^2 / (2 h^2)), h^2 = bandwidth^2 x the mean squared distance over all pairs of
+               the observation's candidates: the candidate in the densest region (mode seeking; lower cost is better everywhere);
+               "goal" -- cost_i = sum_d goal_weight[d] (x_i[t_goal, d] - goal[b, d])^2 with goal = normalised embeddings (B, D) or an
+               observation dict in batch['obs'] form, goal_weight (D,) >= 0 (default ones), t_goal default action_horizon - 1;
+               a callable -- receives the candidates (B, N, T, D) as a device tensor and returns costs (B, N) as a device tensor.
+        Ties go to the lowest candidate index, a NaN cost counts as +inf.
+        noise: explicit-noise dict with x_init (N*B, T, D) / x_noise (S, N*B, T, D) in candidate-major rows and a_init (B*ah, A) /
+        a_noise (S, B*ah, A) for the winners' IDM rows."""
+        if not (self.use_planner and self.use_idm):
+            raise NotImplementedError("sample_best_of() needs both the planner and the IDM (use_planner / use_idm)")
+        N = int(n_candidates)
+        seed = _seed_of(eval_rng)
+        if idm_steps is None and n_steps is not None and sampler != "ddpm":
+            idm_steps = n_steps
+
+        def run():
+            return self._best_of(batch, seed, N, score, bandwidth, goal, goal_weight, t_goal, sampler, n_steps, idm_steps, noise)
+        res, rec = self._call(run, lambda: run() + [None])             # plan_viz re-decodes itself from the new plan
+        return self._best_of_result(res, rec, decode)
+
+    def _best_of_result(self, res, rec, decode):
+        arrs = [DeviceArray(t, record=rec) for t in res]
+        metrics = dict(zip(("plan", "best_index", "best_cost", "costs", "candidates"), arrs[1:]))
+        plan, S = arrs[1], self._engine.image_size
+        viz = DeviceArray(thunk=lambda: self._vae_decode_t(plan.tensor), shape=tuple(plan.shape[:2]) + (3, S, S), record=rec)
+        if decode:
+            viz.tensor
+        metrics["plan_viz"] = viz
+        return arrs[0], metrics
+
     # ---- agent/ldp_agent.py:223-323: the training step ----------------------------------------------------------------
     def _gates(self, step):
         """The python-side schedule gates of `update` / `update_mixed` (agent/ldp_agent.py:224-230, 275-281)."""

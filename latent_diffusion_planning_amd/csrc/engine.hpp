@@ -196,6 +196,7 @@ struct ldp_handle {
   bool f16_vae() const { return opt.vae_split_f16 != 0 && !range_fallback; }
   ldp::Options opt;
   ldp::DevBuf plan_out, act_out, obs_last;   // joint sample(): handle-owned outputs the graph writes
+  ldp::DevBuf cand_cond;                 // ldp_plan_candidates (select.hip): the condition tiled over the candidate rows (no graph node reads it)
   hipStream_t cap_stream = nullptr;      // internal stream used only for graph capture
   int n_cu = 256;                        // compute units of cfg.device (co-residency bound of the column split)
   // Captured loops, least-recently-used eviction at `graph_cap` entries.  Batches are bucketed to whole 16-row tiles

@@ -83,6 +83,27 @@ def sample_sharded(agent, batch: dict, eval_rng, group=None, **kw):
     return DeviceArray(action), {"plan": DeviceArray(plan)}
 
 
+def sample_best_of_sharded(agent, batch: dict, eval_rng, n_candidates: int, group=None, **kw):
+    """`agent.sample_best_of(batch, rng, n_candidates, **kw)` with the CANDIDATES split over the ranks of `group` (observations are not
+    sharded).  Every rank passes the full batch; rank r draws candidates shard_bounds(n_candidates, world, r) -- candidate-major rows, so
+    its shard is the contiguous planner row range [c0 * B, c1 * B) keyed by global row -- and completes them (fault poll) before they
+    leave; the ranks all-gather the candidates, each costs its own range against all of them, all-gather the costs, and then select and
+    run the IDM redundantly: two collectives per call, none in the selection.  A candidate's cost does not depend on the rank that
+    computed it (csrc/select.hip), so every rank returns the same tensors, as record-less DeviceArrays.  The explicit-noise dict is
+    that of the whole call (rows of all candidates); `decode` is honoured for plan_viz."""
+    from .agent import _seed_of
+    on = dist.is_available() and dist.is_initialized()
+    world = dist.get_world_size(group) if on else 1
+    rank = dist.get_rank(group) if on else 0
+    decode = kw.pop("decode", False)
+    kw = dict(dict(score="density", bandwidth=0.5, goal=None, goal_weight=None, t_goal=None, sampler="ddpm", n_steps=None,
+                   idm_steps=None, noise=None), **kw)
+    if kw["idm_steps"] is None and kw["n_steps"] is not None and kw["sampler"] != "ddpm":
+        kw["idm_steps"] = kw["n_steps"]
+    res = agent._best_of(batch, _seed_of(eval_rng), int(n_candidates), shard=(group, world, rank), **kw)
+    return agent._best_of_result(res, None, decode)
+
+
 def update_sharded(agent, batch: dict, rng, step: int, group=None, mixed_batch=None, noise=None):
     """`agent.update(batch, rng, step)` / `agent.update_mixed(batch, mixed_batch, rng, step)` (agent/ldp_agent.py:223-323) with the batch rows
     split over the ranks of `group`, for every trainable class: LDPAgent, LDPHierAgent, DPVAEAgent, DPTrainAgent (the U-Net's and every image

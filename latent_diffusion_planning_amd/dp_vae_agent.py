@@ -167,6 +167,9 @@ class DPVAEAgent(LDPAgent):
     def sample_action_from_plan(self, *a, **k):
         raise NotImplementedError("DPVAEAgent has no sample_action_from_plan")
 
+    def sample_best_of(self, *a, **k):
+        raise NotImplementedError("sample_best_of is built for LDPAgent only (it scores latent plans; a DP agent samples actions)")
+
     def update_mixed(self, *a, **k):
         raise NotImplementedError("DPVAEAgent has no update_mixed")
 

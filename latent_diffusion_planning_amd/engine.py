@@ -36,6 +36,30 @@ def _want(name: str, t: Optional[torch.Tensor], shape) -> None:
         raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
 
 
+def check_candidate_range(B: int, N: int, K: int, c0: int = 0, n_loc: Optional[int] = None, bandwidth: Optional[float] = None) -> None:
+    """The argument rules of the best-of-N calls (include/ldp_hip.h), raised here with the argument's name before a pointer crosses
+    the ABI: B observations, N candidates of K floats each, of which this call handles [c0, c0 + n_loc)."""
+    n_loc = N - c0 if n_loc is None else n_loc
+    if B < 1:
+        raise ValueError(f"B must be >= 1, got {B}")
+    if N < 1:
+        raise ValueError(f"n_candidates (N) must be >= 1, got {N}")
+    if K < 1:
+        raise ValueError(f"K must be >= 1, got {K}")
+    if c0 < 0 or n_loc < 1 or c0 + n_loc > N:
+        raise ValueError(f"candidate range c0 = {c0}, n_loc = {n_loc} must be non-empty and lie in 0..N = {N}")
+    if bandwidth is not None and not (np.isfinite(bandwidth) and bandwidth > 0):
+        raise ValueError(f"bandwidth must be finite and > 0, got {bandwidth}")
+
+
+def _candidate_dims(x: torch.Tensor, B: int):
+    """(N, K) of a candidate-major tensor (N * B, ...)."""
+    B = int(B)
+    if B < 1 or x.dim() < 2 or x.shape[0] < B or x.shape[0] % B:
+        raise ValueError(f"candidates must have shape (N * B, ...) with B = {B}, got {tuple(x.shape)}")
+    return x.shape[0] // B, int(np.prod(x.shape[1:]))
+
+
 class HipEngine:
     """One `ldp_handle` on one GPU."""
 
@@ -238,6 +262,77 @@ class HipEngine:
                                        1 if use_graph else 0, self._stream()))
         self.call_seq += 1
         return out
+
+    # -- best-of-N planning (csrc/select.hip): candidate-major rows r = c * B + b ---------------------
+    def plan_candidates(self, obs_emb: torch.Tensor, obs_horizon: int, n_candidates: int, *, c0: int = 0, n_loc: Optional[int] = None,
+                        x_init=None, step_noise=None, seed: int = 0, sampler: str = "ddpm", n_steps: Optional[int] = None,
+                        use_graph: bool = True) -> torch.Tensor:
+        """Candidates [c0, c0 + n_loc) of n_candidates plans per observation: obs_emb (B, frames, D) -> x (n_loc * B, T, D), row
+        (c - c0) * B + b, each keyed by its global row c * B + b.  x_init (n_loc * B, T, D) / step_noise (n_steps, n_loc * B, T, D):
+        explicit noise of these rows."""
+        ob = _f32(obs_emb, self.device)
+        B, H = ob.shape[0], ob.shape[1]
+        _want("obs_emb", ob, (B, H, self.D))
+        n_loc = int(n_candidates) - int(c0) if n_loc is None else int(n_loc)
+        check_candidate_range(B, int(n_candidates), self.T * self.D, int(c0), n_loc)
+        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
+        rows = n_loc * B
+        xi = None if x_init is None else _f32(x_init, self.device)
+        nz = None if step_noise is None else _f32(step_noise, self.device)
+        _want("x_init", xi, (rows, self.T, self.D))
+        _want("step_noise", nz, (n_steps, rows, self.T, self.D))
+        out = torch.empty((rows, self.T, self.D), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_plan_candidates(self._h, _ptr(ob), H, int(obs_horizon), B, int(c0), n_loc, _ptr(xi), _ptr(nz),
+                                           C.c_uint64(seed & (2**64 - 1)), _SAMPLERS[sampler], n_steps, _ptr(out),
+                                           1 if use_graph else 0, self._stream()))
+        self.call_seq += 1
+        return out
+
+    def plan_cost_density(self, x_all: torch.Tensor, B: int, bandwidth: float = 0.5, *, c0: int = 0,
+                          n_loc: Optional[int] = None) -> torch.Tensor:
+        """Density cost of candidates [c0, c0 + n_loc) against ALL candidates: x_all (N * B, ...) candidate-major -> (n_loc, B)."""
+        x = _f32(x_all, self.device)
+        N, K = _candidate_dims(x, B)
+        n_loc = N - int(c0) if n_loc is None else int(n_loc)
+        check_candidate_range(int(B), N, K, int(c0), n_loc, bandwidth=bandwidth)
+        out = torch.empty((n_loc, int(B)), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_plan_cost_density(_ptr(x), int(B), N, K, int(c0), n_loc, C.c_float(float(bandwidth)), _ptr(out), self._stream()))
+        return out
+
+    def plan_cost_goal(self, x: torch.Tensor, B: int, goal: torch.Tensor, weight=None, t_goal: Optional[int] = None) -> torch.Tensor:
+        """Goal cost of the n candidates given: x (n * B, T, D) candidate-major, goal (B, D), weight (D,) >= 0 (default ones),
+        t_goal (default action_horizon - 1) -> (n, B)."""
+        x = _f32(x, self.device)
+        if x.dim() != 3:
+            raise ValueError(f"x must have shape (n * B, T, D), got {tuple(x.shape)}")
+        n, _ = _candidate_dims(x, B)
+        T, D = int(x.shape[1]), int(x.shape[2])
+        g = _f32(goal, self.device)
+        _want("goal", g, (int(B), D))
+        w = torch.ones(D, device=self.device, dtype=torch.float32) if weight is None else _f32(weight, self.device).reshape(-1)
+        _want("goal_weight", w, (D,))
+        if weight is not None and not bool((np.asarray(torch.as_tensor(weight).detach().cpu()) >= 0).all()):
+            raise ValueError("goal_weight must be non-negative")
+        t_goal = self.ah - 1 if t_goal is None else int(t_goal)
+        if not 0 <= t_goal < T:
+            raise ValueError(f"t_goal must lie in 0..{T - 1}, got {t_goal}")
+        out = torch.empty((n, int(B)), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_plan_cost_goal(_ptr(x), int(B), n, T, D, t_goal, _ptr(g), _ptr(w), _ptr(out), self._stream()))
+        return out
+
+    def plan_select(self, cost_all: torch.Tensor, x_all: torch.Tensor, B: int):
+        """argmin over the candidates of every observation (ties to the lowest index, NaN as +inf) and the winner's rows:
+        cost_all (N, B), x_all (N * B, ...) -> (best_index (B,) int32, best_cost (B,), x_best (B, ...))."""
+        x = _f32(x_all, self.device)
+        N, K = _candidate_dims(x, B)
+        cost = _f32(cost_all, self.device)
+        if cost.numel() != N * int(B):
+            raise ValueError(f"cost_all must hold N * B = {N * int(B)} costs, got shape {tuple(cost.shape)}")
+        idx = torch.empty((int(B),), device=self.device, dtype=torch.int32)
+        best = torch.empty((int(B),), device=self.device, dtype=torch.float32)
+        xb = torch.empty((int(B),) + tuple(x.shape[1:]), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_plan_select(_ptr(cost), _ptr(x), int(B), N, K, _ptr(idx), _ptr(best), _ptr(xb), self._stream()))
+        return idx, best, xb
 
     # -- IDM ------------------------------------------------------------------------------------
     def idm_forward(self, s: torch.Tensor, a: torch.Tensor, k) -> torch.Tensor:

@@ -140,6 +140,9 @@ class LDPHierAgent(LDPAgent):
         return [n if n.key != "idm" else n._replace(eng=ieng, slot="planner", grad=lambda s, a, eps, t, w: ieng.train_planner_grad(a, eps, t, s, w))
                 for n in super()._nets()]
 
+    def sample_best_of(self, *a, **k):
+        raise NotImplementedError("sample_best_of is built for LDPAgent only (the hierarchical plan has a stride and a U-Net IDM)")
+
     # ---- agent/ldp_hier_agent.py:385-461 -----------------------------------------------------------
     def sample(self, batch, eval_rng, **kw):
         kw.setdefault("decode", False)
