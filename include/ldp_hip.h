@@ -53,6 +53,7 @@ extern "C" {
 #define LDP_PHILOX_STREAM_LOSS_IDM 8u  /* add_noise of the IDM loss                                                  */
 #define LDP_PHILOX_STREAM_VAE_EPS 9u   /* eps of the StableVAE posterior draw z = mean + std * eps (ldp_vae_posterior) */
 #define LDP_PHILOX_STREAM_VAE_SAMPLE 10u /* the latents StableVAEModel.sample decodes (drawn through ldp_philox_normal)  */
+#define LDP_PHILOX_STREAM_DATA 11u     /* the window indices of a training batch (ldp_data_draw / ldp_data_sample)   */
 
 /* Index of each scalar in the 11-float result of ldp_vae_metrics: the keys of StableVAEModel.loss
  * (model/stable_vae_model.py:42-53), in the reference's order. */
@@ -588,6 +589,47 @@ LDP_API int ldp_philox_raw(uint64_t seed, uint64_t elem0, uint32_t step, uint32_
                    uint32_t* out_dev, int64_t n, void* stream);
 LDP_API int ldp_philox_normal(uint64_t seed, uint64_t elem0, uint32_t step, uint32_t stream_id,
                       float* out_dev, int64_t n, void* stream);
+
+/* -- device-resident training data (csrc/data.hip) ----------------------------------
+ * The welded episode tables of a dataset (or of a mixture: its datasets welded one behind the other)
+ * live in HBM; one launch draws the B window indices of a batch and gathers the episode-clamped
+ * windows of every key.  Stateless: no handle, no workspace, no atomics -- the outputs are a pure
+ * function of the arguments.  Arrays marked "host" are read during the call and travel as kernel
+ * arguments (no copy is enqueued); nothing synchronises.
+ * replaces: RobomimicLatentDataset._sample / get_item / _get_batch (data/robomimic_latent_data.py:112-147,
+ * the same in data/alohasim_latent_data.py), RobomimicMixedLatentData._sample
+ * (data/robomimic_mixed_latent_data.py:84-88), the DataLoader collation behind them and the
+ * `tensor.numpy()` map + device_put of train_bc.py:78. */
+#define LDP_DATA_MAX_KEYS 16
+#define LDP_DATA_MAX_SETS 8
+
+typedef struct ldp_data_key {
+  const void* table;  /* device: welded table of this key, (total_rows, row_bytes) bytes, any element type        */
+  void* out;          /* device: (B, n_rows, row_bytes) bytes                                                     */
+  int64_t row_bytes;  /* multiple of 4; table and out must be 4-byte aligned (16: rows move as 16-byte vectors)   */
+  int32_t first_row;  /* first window row this key takes: 0 (observations) or frame_stack - 1 (actions)           */
+  int32_t n_rows;     /* window rows it takes; first_row + n_rows <= W = frame_stack + seq_length - 1             */
+} ldp_data_key;
+
+/* The draw alone.  Sample b, global row r = row_offset + b, takes the Philox words w of (seed, elem = r, step,
+ * LDP_PHILOX_STREAM_DATA): dataset d = the first with w[1] < thr[d] (thr = floor(cumulative split * 2^32) as uint64;
+ * the last one is taken as 2^32 whatever is passed), index_out[b] = dataset_base[d] + ((uint64) w[0] * dataset_total[d] >> 32)
+ * -- a multiply-shift map onto [0, total) whose bias is below total / 2^32, hence dataset_total[d] < 2^31.  Deliberately
+ * not NumPy's randint stream.  dataset_base / dataset_total / thr: host, n_sets (1 .. LDP_DATA_MAX_SETS) entries.
+ * replaces: `np.random.randint(self.total_n_sequences)` (robomimic_latent_data.py:113) and `random.choices(..., train_split)`
+ * (robomimic_mixed_latent_data.py:86) of one batch. */
+LDP_API int ldp_data_draw(const int64_t* dataset_base, const int64_t* dataset_total, const uint64_t* thr, int32_t n_sets,
+                          uint64_t seed, int64_t row_offset, uint32_t step, int32_t B, int64_t* index_out, void* stream);
+
+/* One batch in ONE launch, whatever n_keys (1 .. LDP_DATA_MAX_KEYS; keys: host).  Sample b has the welded row i = index_in[b]
+ * (device int64, clamped to [0, total_rows) so that nothing outside the tables is ever read) or, with index_in NULL, the draw
+ * above; bounds (device int32, (total_rows, 2)) holds the episode [s, e) of every welded row.  Window row j of key k is welded
+ * row clamp(i - (frame_stack - 1) + first_row + j, s, e - 1), j < n_rows.  index_out (device int64, B) may be NULL.
+ * total_rows < 2^31 and n_rows * row_bytes < 2^31; all byte offsets are 64-bit. */
+LDP_API int ldp_data_sample(const ldp_data_key* keys, int32_t n_keys, const int32_t* bounds, int64_t total_rows,
+                            const int64_t* dataset_base, const int64_t* dataset_total, const uint64_t* thr, int32_t n_sets,
+                            uint64_t seed, int64_t row_offset, uint32_t step, int32_t B, int32_t frame_stack, int32_t seq_length,
+                            const int64_t* index_in, int64_t* index_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,8 @@ RESNET_TRAIN_MAX_FRAMES = 1024                # frames per ldp_train_encoder_for
 VAE_TRAIN_MAX_FRAMES = 256                    # frames per ldp_train_vae_grad(_part) call (csrc/vae_train.hpp VAE_TRAIN_MAX_FRAMES)
 RESNET_CHUNK = 64                             # frames per pass of ldp_resnet_encode (csrc/resnet.hip RN_CHUNK)
 PHILOX_STREAM_VAE_EPS = 9          # LDP_PHILOX_STREAM_VAE_EPS: eps of the StableVAE posterior draw
+PHILOX_STREAM_DATA = 11            # LDP_PHILOX_STREAM_DATA: the window indices of a training batch (data.py)
+DATA_MAX_KEYS, DATA_MAX_SETS = 16, 8          # LDP_DATA_MAX_KEYS / LDP_DATA_MAX_SETS
 # LDP_VAE_METRIC_*: the keys of StableVAEModel.loss (model/stable_vae_model.py:42-53) in the order ldp_vae_metrics writes them
 VAE_METRIC_KEYS = ("img_min", "img_max", "img_mean", "img_std", "loss", "loss_mse", "loss_kl", "z_min", "z_max", "z_mean", "z_std")
 
@@ -56,6 +58,10 @@ class LdpConfig(C.Structure):
         ("idm_hidden", C.c_int32), ("idm_blocks", C.c_int32), ("idm_time_dim", C.c_int32),
         ("image_size", C.c_int32), ("vae_latent_channels", C.c_int32), ("device", C.c_int32),
     ]
+
+
+class LdpDataKey(C.Structure):                 # ldp_data_key: one key of ldp_data_sample
+    _fields_ = [("table", C.c_void_p), ("out", C.c_void_p), ("row_bytes", C.c_int64), ("first_row", C.c_int32), ("n_rows", C.c_int32)]
 
 
 _FP = C.c_void_p       # device float*/int* passed as integers from tensor.data_ptr()
@@ -115,6 +121,11 @@ SIGNATURES: Dict[str, tuple] = {
     "ldp_get_option": (C.c_int, [_H, C.c_char_p, C.POINTER(C.c_int64)]),
     "ldp_philox_raw": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _FP, C.c_int64, C.c_void_p]),
     "ldp_philox_normal": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _FP, C.c_int64, C.c_void_p]),
+    "ldp_data_draw": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_int32, C.c_uint64, C.c_int64, C.c_uint32,
+                                C.c_int32, _FP, C.c_void_p]),
+    "ldp_data_sample": (C.c_int, [C.POINTER(LdpDataKey), C.c_int32, _FP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_uint64), C.c_int32, C.c_uint64, C.c_int64, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP,
+                                  C.c_void_p]),
     "ldp_launch_count": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int64)]),
     "ldp_range_fallbacks": (C.c_int64, []),
     "ldp_add_noise": (C.c_int, [_FP, _FP, _FP, C.c_int32, _FP, C.c_int64, C.c_int32, C.c_void_p]),

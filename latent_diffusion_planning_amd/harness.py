@@ -355,6 +355,35 @@ def eval_loss_metrics(policy, batch: dict, rng) -> dict:
     return metrics
 
 
+def fit(agent, data_iter, n_steps: int, rng, log_every: int = 100, on_log: Optional[Callable] = None, mixed_iter=None, start_step: int = 0):
+    """The training loop of train_bc.py:97-112: `next(batch)` -> `agent.update(batch, rng, step)` (`update_mixed` with the IDM's batch
+    from `mixed_iter`) -> metrics.  `data_iter` yields batch dicts -- with data.BatchIterator they are device tensors and the loop
+    enqueues launches only: the metrics of `update` are lazy, so the host waits for the GPU at log steps alone (every `log_every`-th
+    step, where `on_log(step, {key: float})` is called), never in between.  Step n uses the seed rng + n (the reference splits its key
+    once per step).  With torch.distributed initialised the step is `dist.update_sharded`: every rank passes the FULL batch, which
+    every rank draws identically from (seed, step) without communication.  -> (agent, metrics of the last step)."""
+    import torch.distributed as tdist
+
+    from .agent import _seed_of
+    seed = _seed_of(rng)
+    sharded = tdist.is_available() and tdist.is_initialized()
+    if sharded:
+        from .dist import update_sharded
+    metrics: dict = {}
+    for step in range(int(start_step), int(start_step) + int(n_steps)):
+        batch = next(data_iter)
+        mixed = next(mixed_iter) if mixed_iter is not None else None
+        if sharded:
+            agent, metrics = update_sharded(agent, batch, seed + step, step, mixed_batch=mixed)
+        elif mixed is not None:
+            agent, metrics = agent.update_mixed(batch, mixed, seed + step, step)
+        else:
+            agent, metrics = agent.update(batch, seed + step, step)
+        if on_log is not None and log_every and (step + 1) % int(log_every) == 0:
+            on_log(step + 1, {k: float(v) for k, v in metrics.items() if np.ndim(v) == 0})
+    return agent, metrics
+
+
 def eval_vae_metrics(model, batches, rng, max_batches: int = 11) -> dict:
     """The evaluation loop of train_vae.py:146-157 on a StableVAEModel: `get_metrics` on up to `max_batches` held-out batches, the mean of
     every key over the batches, prefixed `evaldata/`.  `rng` seeds batch i with rng + i (the reference splits its key once per batch)."""

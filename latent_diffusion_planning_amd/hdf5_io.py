@@ -257,6 +257,67 @@ class File:
             self.lib.H5Sclose(space)
             self.lib.H5Dclose(d)
 
+    def _types(self):
+        """The datatype calls of the two readers below, typed on first use (load() binds only what the latent container needs)."""
+        lib = self.lib
+        if not getattr(lib, "_ldp_types", False):
+            for name, (res, args) in {"H5Dget_type": (hid_t, [hid_t]), "H5Aget_type": (hid_t, [hid_t]), "H5Tget_class": (C.c_int, [hid_t]),
+                                      "H5Tget_size": (C.c_size_t, [hid_t]), "H5Tis_variable_str": (C.c_int, [hid_t]),
+                                      "H5Tclose": (herr_t, [hid_t]), "H5free_memory": (herr_t, [C.c_void_p])}.items():
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = res, args
+            lib._ldp_types = True
+        return lib
+
+    def read_dataset_raw(self, name: str) -> np.ndarray:
+        """A dataset stored as one-byte integers (camera frames) -> uint8, nothing converted; any other numeric dataset -> float32 like
+        `read_dataset`.  For consumers that keep frames as bytes (data.DeviceDataset.from_files)."""
+        lib = self._types()
+        d = _ok(lib.H5Dopen2(self.fid, name.strip("/").encode(), H5P_DEFAULT), f"open dataset {name}")
+        try:
+            t = _ok(lib.H5Dget_type(d), "datatype")
+            try:
+                is_u8 = lib.H5Tget_class(t) == 0 and lib.H5Tget_size(t) == 1           # H5T_INTEGER = 0
+            finally:
+                lib.H5Tclose(t)
+            if not is_u8:
+                return self.read_dataset(name)
+            out = np.empty(self.shape(name), dtype=np.uint8)
+            if out.size:
+                _ok(lib.H5Dread(d, lib._t_u8, H5S_ALL, H5S_ALL, H5P_DEFAULT, out.ctypes.data_as(C.c_void_p)), f"read {name}")
+            return out
+        finally:
+            lib.H5Dclose(d)
+
+    def read_attr_str(self, group: str, name: str) -> str:
+        """A string attribute (robomimic's `env_args` JSON on the `data` group), fixed or variable length, read in its stored type."""
+        lib = self._types()
+        g = _ok(lib.H5Gopen2(self.fid, group.strip("/").encode(), H5P_DEFAULT), f"open group {group}")
+        try:
+            at = _ok(lib.H5Aopen(g, name.encode(), H5P_DEFAULT), f"open attribute {name}")
+            try:
+                t = _ok(lib.H5Aget_type(at), "attribute type")
+                try:
+                    if lib.H5Tget_class(t) != 3:                                        # H5T_STRING = 3
+                        raise HDF5Error(f"HDF5: attribute {name} is not a string")
+                    if lib.H5Tis_variable_str(t) > 0:
+                        p = C.c_void_p()
+                        _ok(lib.H5Aread(at, t, C.byref(p)), f"read attribute {name}")
+                        val = C.string_at(p.value) if p.value else b""
+                        if p.value:
+                            lib.H5free_memory(p)
+                    else:
+                        buf = C.create_string_buffer(int(lib.H5Tget_size(t)) + 1)
+                        _ok(lib.H5Aread(at, t, buf), f"read attribute {name}")
+                        val = buf.value
+                    return val.decode("utf-8")
+                finally:
+                    lib.H5Tclose(t)
+            finally:
+                lib.H5Aclose(at)
+        finally:
+            lib.H5Gclose(g)
+
     def read_attr(self, group: str, name: str, as_int: bool = False):
         g = _ok(self.lib.H5Gopen2(self.fid, group.strip("/").encode(), H5P_DEFAULT), f"open group {group}")
         at = _ok(self.lib.H5Aopen(g, name.encode(), H5P_DEFAULT), f"open attribute {name}")
