@@ -134,7 +134,7 @@ LDP_API int ldp_unet_forward(ldp_handle* h, const float* x, const int32_t* k_dev
  * index of this call's first plan, so a plan's noise does not depend on how a batch is sharded.  sampler/n_steps: DDPM requires n_steps ==
  * planner_train_steps; DDIM requires n_steps | planner_train_steps.
  * use_graph != 0 replays a cached hipGraph of the whole loop (keyed by B, n_steps, sampler,
- * noise mode).  out: (B, T, D). */
+ * noise mode and the step range, here (0, n_steps): see ldp_plan_sample_range).  out: (B, T, D). */
 LDP_API int ldp_plan_sample(ldp_handle* h, const float* cond, const float* x_init,
                     const float* step_noise, uint64_t seed, int64_t row_offset,
                     int32_t sampler, int32_t n_steps, float* out, int32_t B,
@@ -231,6 +231,50 @@ LDP_API int ldp_plan_cost_goal(const float* x, int32_t B, int32_t n, int32_t T, 
  * One work-group per observation, fixed comparison order.  Stand-alone, one launch.  LDP_EINVAL: B, N, K < 1. */
 LDP_API int ldp_plan_select(const float* cost_all, const float* x_all, int32_t B, int32_t N, int32_t K, int32_t* best_index_out,
                             float* best_cost_out, float* x_best_out, void* stream);
+
+/* -- warm-started replanning (defined by this repo; the reference starts every call from pure noise) ----------
+ * Between two closed-loop calls the world moves by action_horizon states: the plan just computed, shifted by that many positions and
+ * noised to an intermediate level, starts a loop that runs only the last k of n denoising steps (Janner et al. 2022, 5.4).
+ *
+ * ldp_plan_sample_range: ldp_plan_sample restricted to the executed steps [step_begin, step_end), 0 <= step_begin <= step_end <= n_steps.
+ * Step i is the step i of the whole loop in every way (coefficients, timestep t_i = (n_steps-1-i) * stride, noise row i of step_noise
+ * (n_steps, B, T, D), Philox key (seed, element, step i)), so ranges compose: (0, m) then (m, n) on its output gives ldp_plan_sample's
+ * bits.  x_init == NULL draws x_T as ldp_plan_sample does; an empty range returns the drawn or given initial state.  A range has its own
+ * captured graph (the key carries it).  ldp_plan_sample IS this call with (0, n_steps): the same batch split, range guard and fault
+ * protocol.  LDP_EINVAL, naming the argument: step_begin outside 0 .. n_steps, step_end outside step_begin .. n_steps. */
+LDP_API int ldp_plan_sample_range(ldp_handle* h, const float* cond, const float* x_init, const float* step_noise, uint64_t seed,
+                                  int64_t row_offset, int32_t sampler, int32_t n_steps, int32_t step_begin, int32_t step_end,
+                                  float* out, int32_t B, int32_t use_graph, void* stream);
+
+/* The warm initial state, ONE launch (csrc/replan.hip plan_warm_init_kernel):
+ *   xs[b, j, c]    = x_prev[src(b), min(j + shift, T-1), c]         (the edge is held: shift >= T gives the last state everywhere)
+ *   x_out[b, j, c] = fma(a, xs, s * eps[b, j, c])                   (two fp32 roundings: the product s * eps, then the fused sum)
+ * a = sqrt(abar_t), s = sqrt(1 - abar_t) at t = t_{step_begin} = (n_steps-1-step_begin) * (planner_train_steps / n_steps), computed on
+ * the host in float64 from the float32 abar table (FlaxDDPMScheduler.add_noise's coefficients); eps = the LDP_PHILOX_STREAM_INIT draw of
+ * ldp_plan_sample's x_T for the same (seed, row_offset): step 0, element ((row_offset + b) * T + j) * 32-padded width + c.
+ * x_prev (n_slots, T, D); src(b) = slot[b], or b when slot == NULL (then B <= n_slots).  slot (B) int32 may live on the host or on the
+ * device: a host table is checked (LDP_EINVAL names the entry outside 0 .. n_slots-1) and copied by the call; DEVICE-SIDE SLOT VALUES
+ * ARE NOT CHECKED (an entry outside the table reads out of bounds).  x_out (B, T, D).  Exists for tests and tools: ldp_agent_resample
+ * runs the same kernel straight into its loop state.  LDP_EINVAL: step_begin outside 0 .. n_steps-1, shift < 0, n_slots < 1. */
+LDP_API int ldp_plan_warm_init(ldp_handle* h, const float* x_prev, const int32_t* slot, int32_t n_slots, int32_t shift, uint64_t seed,
+                               int64_t row_offset, int32_t sampler, int32_t n_steps, int32_t step_begin, float* x_out, int32_t B,
+                               void* stream);
+
+/* ldp_agent_sample with two differences: the planner state comes from the warm-init kernel above (in the eager prologue, where
+ * ldp_agent_sample draws x_T: the seed changes call to call), and the planner loop is [step_begin, planner_steps).  One captured graph
+ * per (B bucket, steps, sampler, noise modes, step_begin); the IDM loop, the plan assembly and the action un-normalisation are
+ * ldp_agent_sample's.
+ * x_store (n_slots, T, D) device table: row slot[b] (row b with slot == NULL) is read as the previous plan, and the epilogue writes the
+ * new full state x back to the same row (one launch; the padding columns of the loop state never reach the table).  Rows not named by
+ * `slot` are untouched.  Slots must be distinct within a call (two rows writing one slot race).  slot: host or device, as above.
+ * x_noise (planner_steps, B, T, D): row i is used at executed step i (rows below step_begin are not read); x_out (B, T, D) or NULL.
+ * LDP_EINVAL: step_begin outside 0 .. planner_steps-1, shift < 0, n_slots < 1, a host slot outside the table. */
+LDP_API int ldp_agent_resample(ldp_handle* h, const float* obs_emb, int32_t obs_frames, int32_t obs_horizon, float* x_store,
+                               const int32_t* slot, int32_t n_slots, int32_t shift, int32_t step_begin, const float* x_noise,
+                               const float* a_init, const float* a_noise, uint64_t seed, int64_t row_offset, int32_t sampler,
+                               int32_t planner_steps, int32_t idm_steps, float* x_out, float* plan_out, float* action_out,
+                               const float* act_lo, const float* act_hi, int32_t act_dim, int32_t act_mode, int32_t B,
+                               int32_t use_graph, void* stream);
 
 /* -- StableVAE ----------------------------------------------------------------------------
  * FlaxAutoencoderKL.encode(x).latent_dist.mean   (call site agent/ldp_agent.py:55-60)

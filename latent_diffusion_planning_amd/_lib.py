@@ -78,6 +78,13 @@ SIGNATURES: Dict[str, tuple] = {
     "ldp_unet_forward": (C.c_int, [_H, _FP, _FP, C.c_int32, _FP, _FP, C.c_int32, C.c_void_p]),
     "ldp_plan_sample": (C.c_int, [_H, _FP, _FP, _FP, C.c_uint64, C.c_int64, C.c_int32, C.c_int32,
                                   _FP, C.c_int32, C.c_int32, C.c_void_p]),
+    "ldp_plan_sample_range": (C.c_int, [_H, _FP, _FP, _FP, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        _FP, C.c_int32, C.c_int32, C.c_void_p]),
+    "ldp_plan_warm_init": (C.c_int, [_H, _FP, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                     _FP, C.c_int32, C.c_void_p]),
+    "ldp_agent_resample": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, _FP, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP,
+                                     C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, C.c_int32,
+                                     C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ldp_plan_candidates": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_uint64, C.c_int32,
                                       C.c_int32, _FP, C.c_int32, C.c_void_p]),
     "ldp_plan_cost_density": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _FP, C.c_void_p]),

@@ -816,6 +816,84 @@ class LDPAgent(_EngineCalls):
         metrics["plan_viz"] = viz
         return action, metrics
 
+    # ---- warm-started replanning (defined by this repository: DESIGN.md 4.16; csrc/replan.hip, replan.py) ---------------------
+    def sample_warm(self, batch, eval_rng, prev, warm_steps, shift=None, sampler="ddim", n_steps=None, idm_steps=None, noise=None,
+                    row_offset=0, decode=False):
+        """sample() resumed from the previous call's plan -> (action, metrics): metrics is sample()'s plus 'x', the full planner state
+        (B, T, D) as a DeviceArray -- the `prev` of the next call.
+        prev: metrics['x'] of the previous call, or a (B, T, D) device tensor (it is not modified).  warm_steps = k runs the last k of the
+        n_steps planner steps (1 <= k <= n_steps) from the warm initial state: prev shifted by `shift` positions (default action_horizon)
+        with the edge held, noised to the level of step n_steps - k with the Philox draw a cold call would use as x_T.  The IDM loop, the
+        plan assembly and the un-normalisation are sample()'s.  noise: optional dict(x_noise, a_init, a_noise) as in sample_viz (the
+        initial state is the warm one: no x_init).
+        prev=None, warm_steps=None is the cold call that also returns 'x' (the existing path)."""
+        from .replan import check_warm_steps
+        if not (self.use_planner and self.use_idm):
+            raise NotImplementedError("sample_warm() needs both the planner and the IDM (use_planner / use_idm)")
+        if (prev is None) != (warm_steps is None):
+            raise ValueError("prev and warm_steps go together: both None (a cold call that returns 'x') or both given")
+        seed = _seed_of(eval_rng)
+        cfg = self.config
+        oh = cfg["obs_horizon"]
+        ns = int(cfg["planner_n_diffusion_steps"] if n_steps is None else n_steps)
+        if idm_steps is None and n_steps is not None and sampler != "ddpm":
+            idm_steps = n_steps                                # one schedule for both loops unless told otherwise
+        nz = dict(noise or {})
+        if prev is None:
+            def core():
+                return self._sample_core(batch, seed, noise, row_offset, sampler, n_steps, idm_steps)
+        else:
+            step_begin = check_warm_steps(warm_steps, ns)
+            if "x_init" in nz:
+                raise ValueError("a warm call has no x_init: its initial state is the shifted, noised previous plan")
+            sh = int(cfg["action_horizon"] if shift is None else shift)
+            if sh < 0:
+                raise ValueError(f"shift must be >= 0, got {shift}")
+
+            def core():
+                self._sync_weights()
+                obs_emb = self.get_obs_cond(self._vae_encode_t(self._postprocess(batch)["obs"])).contiguous()
+                lo, hi, mode = self._action_bounds()
+                store = self._t(prev).clone()                  # the engine writes the new state back in place: not into the caller's prev
+                if tuple(store.shape) != (obs_emb.shape[0], cfg["pred_horizon"], cfg["obs_dim"]):
+                    raise ValueError(f"prev must have shape {(obs_emb.shape[0], cfg['pred_horizon'], cfg['obs_dim'])}, got {tuple(store.shape)}")
+                x, plan, action = self._engine.agent_resample(
+                    obs_emb, oh, store, step_begin, shift=sh, x_noise=nz.get("x_noise"), a_init=nz.get("a_init"),
+                    a_noise=nz.get("a_noise"), seed=seed, row_offset=row_offset, sampler=sampler, planner_steps=ns,
+                    idm_steps=idm_steps, action_bounds=(lo, hi), action_mode=mode)
+                return action, plan, x, obs_emb
+
+        def run():
+            action, plan, x, obs_emb = core()
+            out = [action, plan, x]
+            if obs_emb.shape[1] > oh:                          # from a training batch, not inference (:447-448)
+                out.append(self._engine.mean_sq_diff(x, obs_emb[:, oh:]))
+            return out
+
+        def recompute():
+            if isinstance(prev, DeviceArray):
+                prev.complete()                                # the previous call may be the one that faulted: its x first
+            return run() + [None]                              # plan_viz re-decodes itself from the new plan
+        res, rec = self._call(run, recompute)
+        action, plan, x = (DeviceArray(t, record=rec) for t in res[:3])
+        metrics = {"plan": plan, "x": x}
+        if len(res) > 3:
+            metrics["plan_mse"] = DeviceArray(res[3], record=rec)
+        S = self._engine.image_size
+        viz = DeviceArray(thunk=lambda: self._vae_decode_t(plan.tensor), shape=tuple(plan.shape[:2]) + (3, S, S), record=rec)
+        if decode:
+            viz.tensor
+        metrics["plan_viz"] = viz
+        return action, metrics
+
+    def replanner(self, n_slots, warm_steps, sampler="ddim", n_steps=None, shift=None):
+        """A Replanner (replan.py) for closed-loop control of up to n_slots environments: it keeps every environment's previous planner
+        state on the device and runs a row warm -- the last warm_steps of n_steps planner steps -- whenever its slot holds one."""
+        from .replan import Replanner
+        if not (self.use_planner and self.use_idm):
+            raise NotImplementedError("replanner() needs both the planner and the IDM (use_planner / use_idm)")
+        return Replanner(self, n_slots, warm_steps, sampler=sampler, n_steps=n_steps, shift=shift)
+
     # ---- best-of-N planning (defined by this repository: DESIGN.md 4.14; csrc/select.hip) ----------------------------------
     def _goal_embedding(self, goal, B):
         """`goal`: normalised embeddings (B, D), or an observation dict in batch['obs'] form (embedded like the batch, frame 0)."""
@@ -894,7 +972,7 @@ class LDPAgent(_EngineCalls):
         return checked(tail) + [cost_all.t().contiguous(), x_all.reshape(N, B, T, D).transpose(0, 1).contiguous()]
 
     def sample_best_of(self, batch, eval_rng, n_candidates, score="density", bandwidth=0.5, goal=None, goal_weight=None, t_goal=None,
-                       sampler="ddpm", n_steps=None, idm_steps=None, noise=None, decode=False):
+                       sampler="ddpm", n_steps=None, idm_steps=None, noise=None, decode=False, prev=None, warm_steps=None):
         """Draw n_candidates plans per observation, score them on the GPU, act on the best one
         -> (action (B, ah, A), metrics): the action of the winning plan through the IDM, and
            metrics = {'plan' (B, ah+1, D), 'plan_viz' (lazy unless decode), 'best_index' (B,), 'best_cost' (B,), 'costs' (B, N),
@@ -910,6 +988,9 @@ class LDPAgent(_EngineCalls):
         a_noise (S, B*ah, A) for the winners' IDM rows."""
         if not (self.use_planner and self.use_idm):
             raise NotImplementedError("sample_best_of() needs both the planner and the IDM (use_planner / use_idm)")
+        if prev is not None or warm_steps is not None:
+            raise NotImplementedError("warm-started candidates are not built: a warm start (prev / warm_steps) is LDPAgent.sample_warm's "
+                                      "and LDPAgent.replanner's, one plan per observation")
         N = int(n_candidates)
         seed = _seed_of(eval_rng)
         if idm_steps is None and n_steps is not None and sampler != "ddpm":

@@ -81,6 +81,7 @@ struct IdmState {
 struct GraphKey {
   int kind, B, n_steps, sampler, noise_mode;      // kind 0 planner loop, 1 IDM loop, 2 joint sample()
   int n_steps2 = 0, noise_mode2 = 0;              // joint graph: the IDM loop's step count / noise mode
+  int begin = 0, end = -1;                        // planner loops (kind 0, 2): the executed steps [begin, end) of n_steps; (0, -1) = no planner range (the IDM loop, kind 1)
   bool operator<(const GraphKey& o) const {
     if (kind != o.kind) return kind < o.kind;
     if (B != o.B) return B < o.B;
@@ -88,7 +89,9 @@ struct GraphKey {
     if (sampler != o.sampler) return sampler < o.sampler;
     if (noise_mode != o.noise_mode) return noise_mode < o.noise_mode;
     if (n_steps2 != o.n_steps2) return n_steps2 < o.n_steps2;
-    return noise_mode2 < o.noise_mode2;
+    if (noise_mode2 != o.noise_mode2) return noise_mode2 < o.noise_mode2;
+    if (begin != o.begin) return begin < o.begin;
+    return end < o.end;
   }
 };
 
@@ -197,6 +200,7 @@ struct ldp_handle {
   ldp::Options opt;
   ldp::DevBuf plan_out, act_out, obs_last;   // joint sample(): handle-owned outputs the graph writes
   ldp::DevBuf cand_cond;                 // ldp_plan_candidates (select.hip): the condition tiled over the candidate rows (no graph node reads it)
+  ldp::DevBuf slot_buf;                  // ldp_plan_warm_init / ldp_agent_resample (replan.hip): a slot table given on the host (no graph node reads it)
   hipStream_t cap_stream = nullptr;      // internal stream used only for graph capture
   int n_cu = 256;                        // compute units of cfg.device (co-residency bound of the column split)
   // Captured loops, least-recently-used eviction at `graph_cap` entries.  Batches are bucketed to whole 16-row tiles
@@ -251,11 +255,17 @@ void reap_retired_graphs(ldp_handle* h);
 // stride is B itself: those (parity-test) calls keep the exact B.
 inline int bucket_rows(int B, bool explicit_noise) { return explicit_noise ? B : (B + 15) / 16 * 16; }
 // the pieces of ldp_plan_sample / ldp_idm_sample, shared with the joint ldp_agent_sample
-struct LoopSpec { int n_steps = 0, sampler = 0; bool explicit_noise = false; };
+// begin / end: the executed steps [begin, end) of the planner loop, 0 <= begin <= end <= n_steps (every planner caller sets them; the whole
+// loop is (0, n_steps)).  Step i is the same step whatever the range: coefficients, timestep, noise row, Philox key and exchange tag
+// all carry i itself.  idm_loop always runs all n_steps and does not read them.  The default end = -1 is no range: planner_loop refuses
+// it (LDP_EINVAL), so a planner caller that forgets the two fields fails loudly instead of running zero steps.
+struct LoopSpec { int n_steps = 0, sampler = 0; bool explicit_noise = false; int begin = 0, end = -1; };
+int check_step_range(int begin, int end, int n_steps, const char* what);
+struct WarmSpec;                                 // a warm start of the planner state (below)
 int check_sampler(int sampler, int n_steps, int n_train, const char* what);
 int entry_fault_check(ldp_handle* h);
 int planner_pre(ldp_handle* h, const float* cond, const float* x_init, const float* step_noise, uint64_t seed,
-                int64_t row_offset, const LoopSpec& L, int B, hipStream_t s);
+                int64_t row_offset, const LoopSpec& L, int B, hipStream_t s, const WarmSpec* warm = nullptr);
 int planner_loop(ldp_handle* h, int B, const LoopSpec& L, hipStream_t q);
 int idm_pre(ldp_handle* h, const float* transition, const float* a_init, const float* step_noise, uint64_t seed,
             int64_t row_offset, const LoopSpec& L, int R, hipStream_t s);
@@ -277,4 +287,21 @@ void resnet_invalidate(ldp_handle* h, int slot);
 void resnet_destroy(ldp_handle* h);
 void train_destroy(ldp_handle* h);
 void betas_squaredcos(int n, std::vector<float>& betas, std::vector<float>& alphas, std::vector<float>& acp);
+
+// ---- warm-started replanning (replan.hip) ------------------------------------------------------------------
+// Where a warm planner state comes from: rows slot_dev[b] (or b) of `x_prev`, shifted by `shift` positions with the edge held, noised with
+// the coefficients (a, s) of the first executed step (warm_coefs); the slot table is already on the device (stage_slots).
+struct WarmSpec { const float* x_prev; const int32_t* slot_dev; int shift; float a, s; };
+// a = sqrt(abar_t), s = sqrt(1 - abar_t) at t = t_begin = (n_steps - 1 - step_begin) * (n_train / n_steps): float64 from the float32 abar table, cast to float
+int warm_coefs(int n_train, int n_steps, int step_begin, float* a, float* s);
+// slot table -> device pointer: a host table is checked against 0 .. n_slots-1 (LDP_EINVAL names the entry) and copied into the handle's
+// slot buffer; a device table is passed through unchecked; NULL stays NULL
+int check_host_slots(const int32_t* slot, int n_slots, int B);      // the check alone: all B entries of a host table (NULL / device: nothing)
+int stage_slots(ldp_handle* h, const int32_t* slot, int n_slots, int B, hipStream_t s, const int32_t** dev_out);
+// dst (B, T, ld_out) <- a * x_prev[src(b), min(j + shift, T-1), c] + s * eps for c < D, 0 for D <= c < ld_out; eps = the Philox draw of
+// philox_init_kernel for global row row0 + b * T + j (row0 = row_offset * T).  ld_out is DP (the loop state) or D (caller memory).
+int plan_warm_init_launch(const float* x_prev, const int32_t* slot_dev, float* dst, int ld_out, int B, int T, int D, int DP, int shift,
+                          float a, float s, uint64_t seed, uint64_t row0, hipStream_t st);
+// dst[(slot[b] or b), j, c] <- src[b, j, c], c < D: the padded loop state (B, T, DP) into rows of an unpadded (n_slots, T, D) table
+int unpad_rows_index_launch(const float* src, float* dst, const int32_t* slot_dev, int B, int T, int D, int DP, hipStream_t st);
 }  // namespace ldp

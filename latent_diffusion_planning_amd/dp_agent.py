@@ -276,6 +276,12 @@ class DPAgent(_EngineCalls):
     def sample_viz(self, *a, **k):
         raise NotImplementedError("DPAgent has no sample_viz (agent/dp_agent.py samples actions only)")
 
+    def sample_warm(self, *a, **k):
+        raise NotImplementedError("sample_warm is built for LDPAgent only (a DP agent denoises actions, which do not shift with the world like a latent plan)")
+
+    def replanner(self, *a, **k):
+        raise NotImplementedError("replanner is built for LDPAgent only (a DP agent denoises actions, which do not shift with the world like a latent plan)")
+
     def sample_action_from_plan(self, *a, **k):
         raise NotImplementedError("DPAgent has no sample_action_from_plan")
 

@@ -167,6 +167,12 @@ class DPVAEAgent(LDPAgent):
     def sample_action_from_plan(self, *a, **k):
         raise NotImplementedError("DPVAEAgent has no sample_action_from_plan")
 
+    def sample_warm(self, *a, **k):
+        raise NotImplementedError("sample_warm is built for LDPAgent only (a DP agent denoises actions, which do not shift with the world like a latent plan)")
+
+    def replanner(self, *a, **k):
+        raise NotImplementedError("replanner is built for LDPAgent only (a DP agent denoises actions, which do not shift with the world like a latent plan)")
+
     def sample_best_of(self, *a, **k):
         raise NotImplementedError("sample_best_of is built for LDPAgent only (it scores latent plans; a DP agent samples actions)")
 

@@ -263,6 +263,104 @@ class HipEngine:
         self.call_seq += 1
         return out
 
+    # -- warm-started replanning (csrc/replan.hip) ---------------------------------------------------
+    def plan_sample_range(self, cond: Optional[torch.Tensor], step_begin: int, step_end: int, B: Optional[int] = None,
+                          x_init: Optional[torch.Tensor] = None, step_noise: Optional[torch.Tensor] = None, seed: int = 0,
+                          row_offset: int = 0, sampler: str = "ddpm", n_steps: Optional[int] = None, use_graph: bool = True) -> torch.Tensor:
+        """plan_sample restricted to the executed steps [step_begin, step_end) of n_steps; step_noise stays (n_steps, B, T, D)."""
+        cond_t = None if cond is None else _f32(cond, self.device)
+        if B is None:
+            B = cond_t.shape[0] if cond_t is not None else x_init.shape[0]
+        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
+        xi = None if x_init is None else _f32(x_init, self.device)
+        nz = None if step_noise is None else _f32(step_noise, self.device)
+        _want("cond", cond_t, (B, self.G))
+        _want("x_init", xi, (B, self.T, self.D))
+        _want("step_noise", nz, (n_steps, B, self.T, self.D))
+        out = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_plan_sample_range(self._h, _ptr(cond_t), _ptr(xi), _ptr(nz), C.c_uint64(seed & (2**64 - 1)),
+                                             C.c_int64(row_offset), _SAMPLERS[sampler], n_steps, int(step_begin), int(step_end),
+                                             _ptr(out), B, 1 if use_graph else 0, self._stream()))
+        self.call_seq += 1
+        return out
+
+    def _slots(self, slot, B: int):
+        """A slot table for the C ABI: None, a device int32 tensor (passed through: the library does not check device-side values) or
+        host integers (copied by the call, which checks them) -> (pointer, whatever must stay alive until the call returns)."""
+        if slot is None:
+            return None, None
+        if torch.is_tensor(slot) and slot.is_cuda:
+            t = slot.to(device=self.device, dtype=torch.int32).contiguous()
+            _want("slot", t, (B,))
+            return C.c_void_p(t.data_ptr()), t
+        a = np.ascontiguousarray(np.asarray(slot.cpu() if torch.is_tensor(slot) else slot, dtype=np.int32))
+        if a.shape != (B,):
+            raise ValueError(f"slot must have shape {(B,)}, got {a.shape}")
+        return a.ctypes.data_as(C.c_void_p), a
+
+    def _store(self, x_store: torch.Tensor) -> torch.Tensor:
+        if not (torch.is_tensor(x_store) and x_store.is_cuda and x_store.dtype == torch.float32 and x_store.is_contiguous()):
+            raise ValueError("x_store must be a contiguous float32 device tensor (n_slots, T, D)")
+        _want("x_store", x_store, (x_store.shape[0], self.T, self.D))
+        return x_store
+
+    def plan_warm_init(self, x_prev: torch.Tensor, step_begin: int, *, slot=None, shift: Optional[int] = None, B: Optional[int] = None,
+                       seed: int = 0, row_offset: int = 0, sampler: str = "ddim", n_steps: Optional[int] = None) -> torch.Tensor:
+        """The warm initial state of a loop that resumes at executed step step_begin (one launch): rows slot[b] (or b) of x_prev
+        (n_slots, T, D), shifted by `shift` positions (default action_horizon) with the edge held, noised to that step's level with the
+        Philox draw of plan_sample's x_T for (seed, row_offset) -> (B, T, D)."""
+        xp = self._store(_f32(x_prev, self.device))
+        n_slots = int(xp.shape[0])
+        B = (n_slots if slot is None else len(slot)) if B is None else int(B)
+        sp, keep = self._slots(slot, B)
+        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
+        out = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_plan_warm_init(self._h, _ptr(xp), sp, n_slots, self.ah if shift is None else int(shift),
+                                          C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _SAMPLERS[sampler], n_steps,
+                                          int(step_begin), _ptr(out), B, self._stream()))
+        del keep
+        return out
+
+    def agent_resample(self, obs_emb: torch.Tensor, obs_horizon: int, x_store: torch.Tensor, step_begin: int, *, slot=None,
+                       shift: Optional[int] = None, x_noise=None, a_init=None, a_noise=None, seed: int = 0, row_offset: int = 0,
+                       sampler: str = "ddim", planner_steps: Optional[int] = None, idm_steps: Optional[int] = None,
+                       action_bounds=None, action_mode: int = 0, use_graph: bool = True):
+        """agent_sample resumed from the previous plan: the planner state is the warm initial state of rows slot[b] (or b) of x_store
+        (n_slots, T, D), the planner loop runs the steps [step_begin, planner_steps), and the new full state is written back IN PLACE to
+        the same rows of x_store -> (x, plan, action) as agent_sample.  Slots must be distinct within a call."""
+        ob = _f32(obs_emb, self.device)
+        B, H = ob.shape[0], ob.shape[1]
+        _want("obs_emb", ob, (B, H, self.D))
+        xs = self._store(x_store)
+        sp, keep = self._slots(slot, B)
+        ps = self.planner_train_steps if planner_steps is None else int(planner_steps)
+        is_ = self.idm_train_steps if idm_steps is None else int(idm_steps)
+        R = B * self.ah
+        xn = None if x_noise is None else _f32(x_noise, self.device)
+        ai = None if a_init is None else _f32(a_init, self.device)
+        an = None if a_noise is None else _f32(a_noise, self.device)
+        _want("x_noise", xn, (ps, B, self.T, self.D))
+        _want("a_init", ai, (R, self.A))
+        _want("a_noise", an, (is_, R, self.A))
+        lo = hi = None
+        adim = 0
+        if action_bounds is not None:
+            lo, hi = self._bounds(*action_bounds)
+            adim = lo.numel()
+            if adim not in (1, self.A) or hi.numel() != adim:
+                raise ValueError(f"action bounds must have length 1 or {self.A}")
+        x = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
+        plan = torch.empty((B, self.ah + 1, self.D), device=self.device, dtype=torch.float32)
+        act = torch.empty((B, self.ah, self.A), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_agent_resample(self._h, _ptr(ob), H, int(obs_horizon), _ptr(xs), sp, int(xs.shape[0]),
+                                          self.ah if shift is None else int(shift), int(step_begin), _ptr(xn), _ptr(ai), _ptr(an),
+                                          C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _SAMPLERS[sampler], ps, is_,
+                                          _ptr(x), _ptr(plan), _ptr(act), _ptr(lo), _ptr(hi), adim, int(action_mode), B,
+                                          1 if use_graph else 0, self._stream()))
+        del keep
+        self.call_seq += 1
+        return x, plan, act
+
     # -- best-of-N planning (csrc/select.hip, DESIGN.md 4.14): candidate-major rows r = c * B + b ---------------------
     def plan_candidates(self, obs_emb: torch.Tensor, obs_horizon: int, n_candidates: int, *, c0: int = 0, n_loc: Optional[int] = None,
                         x_init=None, step_noise=None, seed: int = 0, sampler: str = "ddpm", n_steps: Optional[int] = None,

@@ -85,9 +85,11 @@ def _obs_keys_for_agent(env_kwargs) -> List[str]:
 
 def run_eval(env_params: dict, policy, n_rollout: int, n_proc: int, seed: int, eval_rng: int,
              env_factory: Callable, visualize_plan: Optional[bool] = None, keep_latent_keys: bool = False,
-             poll_s: float = 0.001, verbose: bool = False):
+             poll_s: float = 0.001, verbose: bool = False, replan: Optional[dict] = None):
     """-> (rollout_logs, videos) like run_robomimic_eval.  `eval_rng` is an int; every policy call
-    gets a fresh seed derived from it (the reference splits a JAX key per call)."""
+    gets a fresh seed derived from it (the reference splits a JAX key per call).
+    replan = dict(warm_steps=..., sampler=..., n_steps=...) (optional `shift`): warm-started replanning -- one slot of a
+    `policy.replanner` per worker process, reset when the worker's reset sentinel arrives; None is the reference's protocol."""
     assert n_rollout % n_proc == 0
     per = n_rollout // n_proc
     ctx = mp.get_context("spawn")
@@ -102,6 +104,7 @@ def run_eval(env_params: dict, policy, n_rollout: int, n_proc: int, seed: int, e
     if visualize_plan is None:
         visualize_plan = policy.config.get("name") in ("ldp_agent", "ldp_hier_agent")
     agent_keys = None if keep_latent_keys else _obs_keys_for_agent(env_params.get("env_kwargs", {}))
+    rp = policy.replanner(n_proc, **replan) if replan is not None else None
     t0 = time.time()
     results: Dict[int, dict] = {}
     n_calls, batch_sizes = 0, []
@@ -128,6 +131,8 @@ def run_eval(env_params: dict, policy, n_rollout: int, n_proc: int, seed: int, e
                     continue
                 pid, obs_deque = q.get()
                 if "reset" in obs_deque[0] and obs_deque[0]["reset"] is True:
+                    if rp is not None:
+                        rp.reset([pid])                               # the episode ended: this worker's next plan starts from noise
                     continue
                 for k in obs_deque[0]:
                     stacks.setdefault(k, []).append(np.stack([o[k] for o in obs_deque]))
@@ -145,7 +150,11 @@ def run_eval(env_params: dict, policy, n_rollout: int, n_proc: int, seed: int, e
             batch_sizes.append(len(idxs))
             call_seed = (int(eval_rng) * 1000003 + n_calls) & 0x7FFFFFFFFFFFFFFF
             # the reference's call-site idiom, verbatim (utils/rm_env_utils.py:183-196)
-            if visualize_plan:
+            if rp is not None:
+                batch_action, plan_dict = rp.act(dict(obs=obs), call_seed, idxs, decode=bool(visualize_plan))
+                pv = (np.clip((np.array(plan_dict["plan_viz"]) + 1) / 2, 0, 1) * 255).astype(np.uint8) if visualize_plan else None
+                action = np.array(batch_action)
+            elif visualize_plan:
                 batch_action, plan_dict = policy.sample_viz(dict(obs=obs), call_seed)
                 plan_viz = plan_dict["plan_viz"]
                 pv = (np.clip((np.array(plan_viz) + 1) / 2, 0, 1) * 255).astype(np.uint8)
@@ -208,7 +217,7 @@ def process_aloha_obs(ob_dict: dict, env_params: dict) -> dict:
 
 
 def run_aloha_eval(env_params: dict, policy, n_rollout: int, seed: int, eval_rng: int, env_factory: Callable,
-                   episode_len: int = 400, reset_hook: Optional[Callable] = None, verbose: bool = False):
+                   episode_len: int = 400, reset_hook: Optional[Callable] = None, verbose: bool = False, replan: Optional[dict] = None):
     """Counterpart of `run_aloha_eval_single` (utils/aloha_env_utils.py:51-163): ONE process, one environment, one plan per policy
     call (B = 1), `action_horizon` environment steps per call.  The simulator is injected: `env_factory(**env_kwargs)` returns a
     dm_control-style object -- `reset() -> ts`, `step(action) -> ts` with `ts.observation` (lowdim keys + 'images': {camera: HWC})
@@ -218,8 +227,11 @@ def run_aloha_eval(env_params: dict, policy, n_rollout: int, seed: int, eval_rng
     'ldp_agent', its `plan_viz` turned into uint8 HWC frames by `((plan_viz + 1) / 2 * 255).astype(np.uint8).transpose(0, 1, 3, 4, 2)`
     and pasted next to the `rgb_viz` camera frame of every executed step; otherwise `sample`, the scene cameras ('top' | 'angle' | 'vis') as the debug
     frames and the call's scalar metrics folded into the rollout's log (min over keys containing 'min', max over the rest: :97-105, 118-120, 151-152).
+    replan = dict(warm_steps=..., sampler=..., n_steps=...) (optional `shift`): warm-started replanning through ONE slot of a
+    `policy.replanner`, reset at every episode start (the first call of an episode runs the full loop); None is the reference's protocol.
     -> (rollout_logs, videos)."""
     env = env_factory(**env_params.get("env_kwargs", {}))
+    rp = policy.replanner(1, **replan) if replan is not None else None
     max_reward = env.task.max_reward
     oh = env_params["obs_horizon"]
     t0 = time.time()
@@ -231,6 +243,8 @@ def run_aloha_eval(env_params: dict, policy, n_rollout: int, seed: int, eval_rng
         if reset_hook is not None:
             reset_hook(i, env_params)
         ts = env.reset()
+        if rp is not None:
+            rp.reset([0])
         ob = process_aloha_obs(ts.observation, env_params)
         frames, total_reward, env_steps = [], 0.0, 0
         obs_deque = deque([ob] * oh, maxlen=oh)
@@ -240,7 +254,11 @@ def run_aloha_eval(env_params: dict, policy, n_rollout: int, seed: int, eval_rng
             n_calls += 1
             call_seed = (int(eval_rng) * 1000003 + n_calls) & 0x7FFFFFFFFFFFFFFF
             visualize_plan = policy.config["name"] == "ldp_agent"
-            if visualize_plan:
+            if rp is not None:
+                action, plan_dict = rp.act(dict(obs=obs_dict), call_seed, [0], decode=visualize_plan)
+                if visualize_plan:
+                    plan_viz = ((plan_dict["plan_viz"] + 1) / 2 * 255).astype(np.uint8).transpose(0, 1, 3, 4, 2)
+            elif visualize_plan:
                 action, plan_dict = policy.sample_viz(dict(obs=obs_dict), call_seed)
                 plan_viz = ((plan_dict["plan_viz"] + 1) / 2 * 255).astype(np.uint8).transpose(0, 1, 3, 4, 2)
             else:                                                   # :97-105: scalar metrics of the call, min over '*min*' keys, max over the others

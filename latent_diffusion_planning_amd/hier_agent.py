@@ -140,6 +140,12 @@ class LDPHierAgent(LDPAgent):
         return [n if n.key != "idm" else n._replace(eng=ieng, slot="planner", grad=lambda s, a, eps, t, w: ieng.train_planner_grad(a, eps, t, s, w))
                 for n in super()._nets()]
 
+    def sample_warm(self, *a, **k):
+        raise NotImplementedError("sample_warm is built for LDPAgent only (the hierarchical plan has a stride and a U-Net IDM)")
+
+    def replanner(self, *a, **k):
+        raise NotImplementedError("replanner is built for LDPAgent only (the hierarchical plan has a stride and a U-Net IDM)")
+
     def sample_best_of(self, *a, **k):
         raise NotImplementedError("sample_best_of is built for LDPAgent only (the hierarchical plan has a stride and a U-Net IDM)")
 
