@@ -125,6 +125,31 @@ LDP_API int ldp_finalize(ldp_handle* h, int32_t modules, void* stream);
 LDP_API int ldp_unet_forward(ldp_handle* h, const float* x, const int32_t* k_dev, int32_t k,
                      const float* cond, float* eps, int32_t B, void* stream);
 
+/* Test hook: ldp_unet_forward (same arguments, same contract, the same code: ldp_unet_forward IS this call without a tap) with what every
+ * launch of the evaluation wrote copied out behind the launch (hipMemcpyAsync device-to-device on `stream`) into `taps`, and one row of
+ * `table` per stage (LDP_UNET_TRACE_COLS int64 each; host memory, valid on return; -1 = does not apply):
+ *   [0] offset into taps (floats)  [1] offset of the residual projection the launch also wrote  [2] B  [3] positions
+ *   [4] stored channel stride  [5] real channels  [6] LDP_UNET_STAGE_*  [7] residual-block index  [8] level (positions = T >> level)
+ *   [9] the stage whose output it read (xa)  [10] the skip it read behind it (xb)  [11] the stage its residual came from, [12] 1: that
+ *   stage's residual projection, 0: its output
+ *   [13..21] the plan exactly as handed to tconv_launch: mode, to, nwn, ks, cpi, res, mb, kws, split
+ *   [22] cs: work-groups per GroupNorm group  [23] kw: work-groups the K loop is split over  [24] by_sample placement
+ *   [25] split tile code (0: none; 16 / 17 / 32 / 33 / 34)  [26] column of the block's (scale|bias) slice in the FiLM tensors
+ *   [27], [28] stored channels of xa / xb
+ * Tensors are (B, positions, stride) row-major; the FiLM parts (B, 1, F).  Stages: the padded input state; the FiLM global part
+ * Mish(cond) @ W[E:]; the FiLM time rows the call's timesteps select (an epilogue adds the two); per residual block its first half
+ * (conv + GroupNorm + Mish + FiLM, and the 1x1 projection of the block's input where the widths differ) and its second half
+ * (conv + GroupNorm + Mish + residual); the stride-2 convs; the transposed convs; the Conv1dBlock before the head; the 1x1 head (eps,
+ * (B, T, D) unpadded: the tensor the call returns).
+ * With taps == NULL the evaluation runs untapped and only *n_stages / *floats_needed are set (table may be NULL); they are set on every
+ * call.  Not for captured graphs; the product paths never call it. */
+#define LDP_UNET_TRACE_COLS 32
+enum { LDP_UNET_STAGE_INPUT = 0, LDP_UNET_STAGE_FILM_G, LDP_UNET_STAGE_FILM_T, LDP_UNET_STAGE_RES1, LDP_UNET_STAGE_RES2, LDP_UNET_STAGE_DOWN,
+       LDP_UNET_STAGE_UP, LDP_UNET_STAGE_FIN_BLOCK, LDP_UNET_STAGE_HEAD };
+LDP_API int ldp_unet_trace(ldp_handle* h, const float* x, const int32_t* k_dev, int32_t k, const float* cond, float* eps, int32_t B,
+                   float* taps, int64_t taps_floats, int64_t* table, int32_t table_rows, int32_t* n_stages, int64_t* floats_needed,
+                   void* stream);
+
 /* The planner fori_loop of sample_viz_step (agent/ldp_agent.py:459-476):
  *   x <- x_init (or N(0,I) from the Philox stream when x_init == NULL);
  *   for i in 0..n_steps-1: eps = unet(x, t_i, cond); x = scheduler.step(eps, t_i, x, z_i)

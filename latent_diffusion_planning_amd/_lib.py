@@ -76,6 +76,8 @@ SIGNATURES: Dict[str, tuple] = {
     "ldp_set_weight": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
     "ldp_finalize": (C.c_int, [_H, C.c_int32, C.c_void_p]),
     "ldp_unet_forward": (C.c_int, [_H, _FP, _FP, C.c_int32, _FP, _FP, C.c_int32, C.c_void_p]),
+    "ldp_unet_trace": (C.c_int, [_H, _FP, _FP, C.c_int32, _FP, _FP, C.c_int32, _FP, C.c_int64, C.c_void_p, C.c_int32,
+                                 C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_void_p]),
     "ldp_plan_sample": (C.c_int, [_H, _FP, _FP, _FP, C.c_uint64, C.c_int64, C.c_int32, C.c_int32,
                                   _FP, C.c_int32, C.c_int32, C.c_void_p]),
     "ldp_plan_sample_range": (C.c_int, [_H, _FP, _FP, _FP, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

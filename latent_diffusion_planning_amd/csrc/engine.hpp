@@ -276,9 +276,10 @@ int planner_workspace(ldp_handle* h, int B);
 int run_or_replay(ldp_handle* h, const GraphKey& key, bool use_graph, hipStream_t s,
                   const std::function<int(hipStream_t)>& enqueue);
 int planner_finalize(ldp_handle* h, hipStream_t s);
+struct UnetTap;                                  // engine.hip: the test hook of ldp_unet_trace (nullptr on every product path)
 int planner_forward_launch(ldp_handle* h, int B, const int* k_dev, int k, bool step,
                            const StepCoef* coef, const float* noise, int step_idx, float* eps_out,
-                           hipStream_t s);
+                           hipStream_t s, UnetTap* tap = nullptr);
 int idm_finalize(ldp_handle* h, hipStream_t s);
 int vae_finalize(ldp_handle* h, hipStream_t s);
 void vae_destroy(ldp_handle* h);

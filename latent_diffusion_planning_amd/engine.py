@@ -243,6 +243,49 @@ class HipEngine:
         self.call_seq += 1              # (a single evaluation can fault like a loop: column split, fp16-plane range)
         return eps
 
+    # LDP_UNET_STAGE_* of include/ldp_hip.h, by value
+    UNET_STAGE_KINDS = ("input", "film_g", "film_t", "res1", "res2", "down", "up", "fin_block", "head")
+
+    def unet_trace(self, x: torch.Tensor, k, cond: Optional[torch.Tensor]):
+        """Test hook (ldp_unet_trace): unet_forward through the same code, what every launch wrote tapped.  -> (eps, rows): rows[i] is a
+        dict with the stage's `kind`, `block` and `level`, `xa` / `xb` / `res` (the stages it read, -1: none; `res_is_proj`: the residual
+        is that stage's projection `t_res`), the `plan` handed to tconv_launch (mode, to, nwn, ks, cpi, res, mb, kws, split), `cs`, `kw`,
+        `by_sample`, `tile`, `film_off`, `ca` / `cb`, `channels`, and `t`: the stored tensor on the device, (B, positions, channel
+        stride) -- padding included -- with `t_res` the residual projection a first half wrote next to it (else None)."""
+        x = _f32(x, self.device)
+        B = x.shape[0]
+        cond_t = None if cond is None else _f32(cond, self.device)
+        _want("x", x, (B, self.T, self.D))
+        _want("cond", cond_t, (B, self.G))
+        eps = torch.empty_like(x)
+        kd, ks = None, 0
+        if torch.is_tensor(k) or isinstance(k, np.ndarray):
+            kd = torch.as_tensor(k).to(device=self.device, dtype=torch.int32).reshape(-1)
+            kd = (kd.expand(B) if kd.numel() == 1 else kd).contiguous()
+            _want("k", kd, (B,))
+        else:
+            ks = int(k)
+        ns, nf = C.c_int32(), C.c_int64()
+        args = (self._h, _ptr(x), _ptr(kd) if kd is not None else None, ks, _ptr(cond_t), _ptr(eps), B)
+        check(self.lib.ldp_unet_trace(*args, None, 0, None, 0, C.byref(ns), C.byref(nf), self._stream()))
+        taps = torch.empty(nf.value, device=self.device, dtype=torch.float32)
+        cols = 32                                                                   # LDP_UNET_TRACE_COLS
+        table = np.full((ns.value, cols), -7, np.int64)
+        check(self.lib.ldp_unet_trace(*args, _ptr(taps), nf.value, table.ctypes.data_as(C.c_void_p), ns.value, C.byref(ns), C.byref(nf),
+                                      self._stream()))
+        self.call_seq += 2
+        assert ns.value == len(table) and nf.value == taps.numel()
+        rows = []
+        for r in table:
+            r = [int(v) for v in r]
+            off, off_res, n, pos, ld, ch, kind = r[:7]
+            numel = n * pos * ld
+            rows.append(dict(kind=self.UNET_STAGE_KINDS[kind], block=r[7], level=r[8], xa=r[9], xb=r[10], res=r[11], res_is_proj=r[12] == 1,
+                             plan=tuple(r[13:22]), cs=r[22], kw=r[23], by_sample=r[24], tile=r[25], film_off=r[26], ca=r[27], cb=r[28],
+                             channels=ch, t=taps[off:off + numel].view(n, pos, ld),
+                             t_res=taps[off_res:off_res + numel].view(n, pos, ld) if off_res >= 0 else None))
+        return eps, rows
+
     def plan_sample(self, cond: Optional[torch.Tensor], B: Optional[int] = None,
                     x_init: Optional[torch.Tensor] = None, step_noise: Optional[torch.Tensor] = None,
                     seed: int = 0, row_offset: int = 0, sampler: str = "ddpm",

@@ -144,6 +144,127 @@ def unet_forward(P: TorchParams, x_btc, k, global_cond, down_dims=(256, 512, 102
     return x.transpose(1, 2).contiguous()
 
 
+# The same computation as an ordered list of stages (tests/test_hip_planner_stages.py checks every launch of the engine on its own):
+# (kind, name, inputs, fn) with `inputs` the indices of the stages whose outputs `fn(P, *inputs)` takes -- UNET_IN_X / UNET_IN_K /
+# UNET_IN_COND: the call's x (channels first), timesteps and global condition -- and every activation (B, C, T) in P.dtype.  The FiLM
+# vectors of all blocks are one stage, (B, F) with block i's (scale|bias) slice at column sum_{j<i} 2 Cout_j, and an input of every block's
+# first half.  Built from the functions above, so chaining the stages IS unet_forward (tests/test_oracle_planner_stages.py).  Kinds: the
+# engine's (include/ldp_hip.h LDP_UNET_STAGE_*), with its two FiLM parts as the one stage "film" and the residual projection a first
+# half also writes as the stage "proj" of its own.
+UNET_IN_X, UNET_IN_K, UNET_IN_COND = -1, -2, -3
+
+
+def _time_embed(P, k, b, embed_dim, dev):
+    kk = _ksteps(k, b, dev)
+    arg = kk[:, None] * _freqs(embed_dim, dev)[None, :]
+    e = torch.cat([torch.sin(arg), torch.cos(arg)], dim=-1).to(P.dtype)
+    e = F.mish(F.linear(e, P.t("Dense_0/kernel").t(), P.t("Dense_0/bias")))
+    return F.linear(e, P.t("Dense_1/kernel").t(), P.t("Dense_1/bias"))
+
+
+def unet_film(P, k, global_cond, n_blocks, embed_dim=256):
+    """(B, F): Dense_0(Mish([temb(k), cond])) of every residual block, side by side."""
+    b = global_cond.shape[0] if global_cond is not None else int(torch.as_tensor(k).numel())
+    e = _time_embed(P, k, b, embed_dim, global_cond.device if global_cond is not None else "cpu")
+    g = torch.cat([e, global_cond.to(P.dtype)], dim=-1) if global_cond is not None else e
+    gm = F.mish(g)
+    return torch.cat([F.linear(gm, P.t(f"ConditionalResidualBlock1D_{i}/Dense_0/kernel").t(), P.t(f"ConditionalResidualBlock1D_{i}/Dense_0/bias"))
+                      for i in range(n_blocks)], dim=-1)
+
+
+def unet_film_parts(P, k, global_cond, n_blocks, embed_dim=256):
+    """The two addends the engine keeps apart: (Mish(temb(k)) @ W[:E] + b, Mish(cond) @ W[E:]), each (B, F)."""
+    b = global_cond.shape[0]
+    em = F.mish(_time_embed(P, k, b, embed_dim, global_cond.device))
+    cm = F.mish(global_cond.to(P.dtype))
+    ws = [P.t(f"ConditionalResidualBlock1D_{i}/Dense_0/kernel") for i in range(n_blocks)]
+    bs = [P.t(f"ConditionalResidualBlock1D_{i}/Dense_0/bias") for i in range(n_blocks)]
+    E = em.shape[1]
+    return (torch.cat([em @ w[:E] + c for w, c in zip(ws, bs)], dim=-1), torch.cat([cm @ w[E:] for w in ws], dim=-1))
+
+
+def _unet_res_first(P, x, film, prefix, off, groups, k):
+    """FiLM(Conv1dBlock_0(x)) with the block's slice of the FiLM stage"""
+    out = _conv_block(P, x, f"{prefix}/Conv1dBlock_0", groups, k)
+    c = out.shape[1]
+    emb = film[:, off:off + 2 * c]
+    return emb[:, :c, None] * out + emb[:, c:, None]
+
+
+def _unet_res_proj(P, x, prefix):
+    return F.conv1d(x, P.conv1d_w(f"{prefix}/Conv_0/kernel"), P.t(f"{prefix}/Conv_0/bias"))
+
+
+def _unet_res_second(P, h, res, prefix, groups, k):
+    return _conv_block(P, h, f"{prefix}/Conv1dBlock_1", groups, k) + res
+
+
+def _unet_down(P, x, lvl):
+    xp = F.pad(x, (0, 1)) if x.shape[-1] % 2 == 0 else F.pad(x, (1, 1))
+    return F.conv1d(xp, P.conv1d_w(f"Downsample1d_{lvl}/Conv_0/kernel"), P.t(f"Downsample1d_{lvl}/Conv_0/bias"), stride=2)
+
+
+def _unet_up(P, x, lvl):
+    return F.conv_transpose1d(x, P.convT_w(f"Upsample1d_{lvl}/ConvTranspose_0/kernel"), P.t(f"Upsample1d_{lvl}/ConvTranspose_0/bias"),
+                              stride=2, padding=1)
+
+
+def unet_stages(P, down_dims=(256, 512, 1024), kernel_size=5, n_groups=8, embed_dim=256):
+    nl = len(down_dims)
+    n_blocks = 2 * nl + 2 + 2 * (nl - 1)
+    st = [("input", "x", (UNET_IN_X,), lambda P, x: x),
+          ("film", "film", (UNET_IN_K, UNET_IN_COND), lambda P, k, c: unet_film(P, k, c, n_blocks, embed_dim))]
+    FILM = 1
+    off = [0]
+
+    def block(idx, xs, cout, proj):
+        """xs: the stage(s) whose outputs, concatenated over channels, the block reads -> the stage of its output"""
+        p = f"ConditionalResidualBlock1D_{idx}"
+        cat = (lambda *t: t[0]) if len(xs) == 1 else (lambda *t: torch.cat(t, dim=1))
+        st.append(("res1", f"{p}/Conv1dBlock_0", tuple(xs) + (FILM,),
+                   lambda P, *t, p=p, o=off[0]: _unet_res_first(P, cat(*t[:-1]), t[-1], p, o, n_groups, kernel_size)))
+        h = len(st) - 1
+        off[0] += 2 * cout
+        if proj:
+            st.append(("proj", f"{p}/Conv_0", tuple(xs), lambda P, *t, p=p: _unet_res_proj(P, cat(*t), p)))
+        res = len(st) - 1 if proj else xs[0]
+        st.append(("res2", f"{p}/Conv1dBlock_1", (h, res), lambda P, h, r, p=p: _unet_res_second(P, h, r, p, n_groups, kernel_size)))
+        return len(st) - 1
+
+    cur, idx, skips = 0, 0, []
+    for lvl in range(nl):
+        for proj in (True, False):
+            cur = block(idx, [cur], down_dims[lvl], proj)
+            idx += 1
+        skips.append(cur)
+        if lvl < nl - 1:
+            st.append(("down", f"Downsample1d_{lvl}", (cur,), lambda P, x, l=lvl: _unet_down(P, x, l)))
+            cur = len(st) - 1
+    for _ in range(2):
+        cur = block(idx, [cur], down_dims[-1], False)
+        idx += 1
+    for lvl in range(nl - 1):
+        cur = block(idx, [cur, skips.pop()], down_dims[nl - 2 - lvl], True)
+        idx += 1
+        cur = block(idx, [cur], down_dims[nl - 2 - lvl], False)
+        idx += 1
+        st.append(("up", f"Upsample1d_{lvl}", (cur,), lambda P, x, l=lvl: _unet_up(P, x, l)))
+        cur = len(st) - 1
+    st.append(("fin_block", "Conv1dBlock_0", (cur,), lambda P, x: _conv_block(P, x, "Conv1dBlock_0", 8, kernel_size)))
+    st.append(("head", "Conv_0", (len(st) - 1,), lambda P, x: F.conv1d(x, P.conv1d_w("Conv_0/kernel"), P.t("Conv_0/bias"))))
+    return st
+
+
+@torch.no_grad()
+def run_unet_stages(P, stages, x_btc, k, global_cond):
+    """Every stage's output, chained from the call's inputs; the last one transposed back is unet_forward's result."""
+    ext = {UNET_IN_X: x_btc.to(P.dtype).transpose(1, 2), UNET_IN_K: k, UNET_IN_COND: global_cond}
+    outs = []
+    for kind, name, inputs, fn in stages:
+        outs.append(fn(P, *[ext[i] if i < 0 else outs[i] for i in inputs]))
+    return outs
+
+
 # ------------------------------------------------------------------------------ IDM
 def idm_forward(P: TorchParams, s, a, k, time_dim=256, n_blocks=3):
     dev = s.device
