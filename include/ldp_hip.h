@@ -54,6 +54,7 @@ extern "C" {
 #define LDP_PHILOX_STREAM_VAE_EPS 9u   /* eps of the StableVAE posterior draw z = mean + std * eps (ldp_vae_posterior) */
 #define LDP_PHILOX_STREAM_VAE_SAMPLE 10u /* the latents StableVAEModel.sample decodes (drawn through ldp_philox_normal)  */
 #define LDP_PHILOX_STREAM_DATA 11u     /* the window indices of a training batch (ldp_data_draw / ldp_data_sample)   */
+#define LDP_PHILOX_STREAM_CONSTRAIN 12u /* the noise of a repainted constraint at level j (ldp_plan_constrain, step = j)  */
 
 /* Index of each scalar in the 11-float result of ldp_vae_metrics: the keys of StableVAEModel.loss
  * (model/stable_vae_model.py:42-53), in the reference's order. */
@@ -300,6 +301,54 @@ LDP_API int ldp_agent_resample(ldp_handle* h, const float* obs_emb, int32_t obs_
                                int32_t planner_steps, int32_t idm_steps, float* x_out, float* plan_out, float* action_out,
                                const float* act_lo, const float* act_hi, int32_t act_dim, int32_t act_mode, int32_t B,
                                int32_t use_graph, void* stream);
+
+/* -- constrained planning (defined by this repo; the reference has nothing of the kind) -------------------------
+ * A diffusion planner over states can be told where to be: after every denoising step the constrained entries of the trajectory are
+ * overwritten with the known values at that step's noise level (inpainting: Janner et al. 2022 "Diffuser", Lugmayr et al. 2022
+ * "RePaint").  One loop, the constraint met exactly: whole goal states, partial ones (some columns of one step), several waypoints.
+ *
+ * A loop of n executed steps has the levels 0 .. n: level j is the state in front of executed step j, level n the result.  Level j < n has
+ * the timestep t_j = (n-1-j) * (planner_train_steps / n) and the coefficients a_j = sqrt(abar_t_j), s_j = sqrt(1 - abar_t_j), computed on
+ * the host in float64 from the float32 abar table and cast to float32 (ldp_plan_warm_init's convention); level n has a = 1, s = 0.
+ * target (B, T, D) float32, in the normalised embedding units of the plan itself (the scheduler clips its own x0 estimate to [-1, 1]:
+ * targets belong there; the range is not checked); mask (B, T, D) uint8.  The constraint operation C_j replaces x[b, t, c] where
+ * mask[b, t, c] != 0 and leaves every other element bit for bit as it was (a select, never a blend: a NaN in target under a zero mask
+ * does not reach the state):
+ *   LDP_CONSTRAIN_CLAMP    the replacement is target[b, t, c]                                             (Diffuser)
+ *   LDP_CONSTRAIN_REPAINT  fma(a_j, target, s_j * z_j) with two fp32 roundings (the product s_j * z_j, then the fused sum);
+ *                          z_j = the LDP_PHILOX_STREAM_CONSTRAIN draw for (seed, element ((row_offset + b) * T + t) * 32-padded width
+ *                          + c, step j): the element index of the step noise, so a draw depends on the global row only.  At level n
+ *                          the value written is target itself.
+ * The constrained loop over the executed steps [begin, end):  x <- C_begin(x);  for i in begin .. end-1:  x <- C_{i+1}(step_i(x)).
+ * step_i is ldp_plan_sample_range's step i; C_j is deterministic, so ranges compose bitwise and applying it twice is harmless.
+ *
+ * ldp_plan_constrain: C_level alone on caller memory, ONE launch (csrc/constrain.hip plan_constrain_kernel); x, x_out (B, T, D), x_out may
+ * be x.  Exists for tests and tools: the loops below run the same kernel on their padded state, one launch behind every step, inside the
+ * captured graph (seed and first row are read from the handle's control block there: a graph never bakes a seed).
+ * LDP_EINVAL, naming the argument: a mode that is neither of the two, a NULL target or mask, a level outside 0 .. n_steps. */
+#define LDP_CONSTRAIN_CLAMP 1
+#define LDP_CONSTRAIN_REPAINT 2
+LDP_API int ldp_plan_constrain(ldp_handle* h, const float* x, const float* target, const uint8_t* mask, int32_t mode, int32_t sampler,
+                               int32_t n_steps, int32_t level, uint64_t seed, int64_t row_offset, float* x_out, int32_t B, void* stream);
+
+/* ldp_plan_sample_range with the constraint: the constrained loop above over [step_begin, step_end); an empty range returns C_begin of
+ * the drawn or given initial state.  target and mask are copied by the call into handle-owned padded buffers (graph nodes reference
+ * handle memory only).  One captured graph per (B bucket, steps, sampler, noise mode, range, mode); an all-zero mask gives
+ * ldp_plan_sample_range's bits.  (end - begin) + 1 launches more than the free loop.  A split batch hands each part its rows of target
+ * and mask and its own row_offset. */
+LDP_API int ldp_plan_sample_constrained(ldp_handle* h, const float* cond, const float* x_init, const float* step_noise, const float* target,
+                                        const uint8_t* mask, int32_t mode, uint64_t seed, int64_t row_offset, int32_t sampler,
+                                        int32_t n_steps, int32_t step_begin, int32_t step_end, float* out, int32_t B, int32_t use_graph,
+                                        void* stream);
+
+/* ldp_agent_sample whose planner loop is the constrained loop over (0, planner_steps): the plan assembly, the IDM loop and the action
+ * un-normalisation are ldp_agent_sample's, on the constrained plan.  x_out, plan_out and action_out as there. */
+LDP_API int ldp_agent_sample_constrained(ldp_handle* h, const float* obs_emb, int32_t obs_frames, int32_t obs_horizon, const float* x_init,
+                                         const float* x_noise, const float* a_init, const float* a_noise, const float* target,
+                                         const uint8_t* mask, int32_t mode, uint64_t seed, int64_t row_offset, int32_t sampler,
+                                         int32_t planner_steps, int32_t idm_steps, float* x_out, float* plan_out, float* action_out,
+                                         const float* act_lo, const float* act_hi, int32_t act_dim, int32_t act_mode, int32_t B,
+                                         int32_t use_graph, void* stream);
 
 /* -- StableVAE ----------------------------------------------------------------------------
  * FlaxAutoencoderKL.encode(x).latent_dist.mean   (call site agent/ldp_agent.py:55-60)

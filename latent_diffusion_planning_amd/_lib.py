@@ -25,7 +25,9 @@ VAE_TRAIN_MAX_FRAMES = 256                    # frames per ldp_train_vae_grad(_p
 RESNET_CHUNK = 64                             # frames per pass of ldp_resnet_encode (csrc/resnet.hip RN_CHUNK)
 PHILOX_STREAM_VAE_EPS = 9          # LDP_PHILOX_STREAM_VAE_EPS: eps of the StableVAE posterior draw
 PHILOX_STREAM_DATA = 11            # LDP_PHILOX_STREAM_DATA: the window indices of a training batch (data.py)
-DATA_MAX_KEYS, DATA_MAX_SETS = 16, 8          # LDP_DATA_MAX_KEYS / LDP_DATA_MAX_SETS
+PHILOX_STREAM_CONSTRAIN = 12       # LDP_PHILOX_STREAM_CONSTRAIN: the noise of a repainted constraint (constrain.py)
+CONSTRAIN_CLAMP, CONSTRAIN_REPAINT = 1, 2     # LDP_CONSTRAIN_*
+DATA_MAX_KEYS, DATA_MAX_SETS = 16, 8         # LDP_DATA_MAX_KEYS / LDP_DATA_MAX_SETS
 # LDP_VAE_METRIC_*: the keys of StableVAEModel.loss (model/stable_vae_model.py:42-53) in the order ldp_vae_metrics writes them
 VAE_METRIC_KEYS = ("img_min", "img_max", "img_mean", "img_std", "loss", "loss_mse", "loss_kl", "z_min", "z_max", "z_mean", "z_std")
 
@@ -87,6 +89,13 @@ SIGNATURES: Dict[str, tuple] = {
     "ldp_agent_resample": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, _FP, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP,
                                      C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ldp_plan_constrain": (C.c_int, [_H, _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, _FP, C.c_int32,
+                                     C.c_void_p]),
+    "ldp_plan_sample_constrained": (C.c_int, [_H, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, _FP, C.c_int32, C.c_int32, C.c_void_p]),
+    "ldp_agent_sample_constrained": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_uint64, C.c_int64,
+                                               C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_int32, C.c_void_p]),
     "ldp_plan_candidates": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_uint64, C.c_int32,
                                       C.c_int32, _FP, C.c_int32, C.c_void_p]),
     "ldp_plan_cost_density": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _FP, C.c_void_p]),

@@ -894,6 +894,59 @@ class LDPAgent(_EngineCalls):
             raise NotImplementedError("replanner() needs both the planner and the IDM (use_planner / use_idm)")
         return Replanner(self, n_slots, warm_steps, sampler=sampler, n_steps=n_steps, shift=shift)
 
+    # ---- constrained planning (defined by this repository: DESIGN.md 4.17; csrc/constrain.hip, constrain.py) -------------------
+    def sample_constrained(self, batch, eval_rng, target=None, mask=None, goal=None, t_goal=None, goal_dims=None, mode="repaint",
+                           sampler="ddpm", n_steps=None, idm_steps=None, noise=None, row_offset=0, decode=False):
+        """sample() with goals and waypoints inpainted in the planner loop -> (action, metrics): metrics is sample_warm()'s ('plan', 'x'
+        the full planner state (B, T, D), lazy 'plan_viz', 'plan_mse' for a training batch).  After every denoising step the constrained
+        entries of the trajectory are overwritten with the known values at that step's noise level (mode 'repaint'; 'clamp' writes the
+        values themselves at every level): one planner loop, and metrics['x'] meets the constraint exactly.
+        The constraint is constrain.build_constraint's: `target` (B, T, D) with `mask` broadcast from (D,), (T, D) or (B, T, D), and / or
+        `goal` -- normalised embeddings (B, D) or an observation dict in batch['obs'] form -- written at step(s) `t_goal` (default
+        action_horizon - 1) into the columns `goal_dims` (None / 'all', 'latent', 'lowdim', an index list, a bool (D,) array).  Values
+        are in the normalised embedding units of the plan; they belong in [-1, 1], where the scheduler clips its own estimate.  With
+        nothing given the call is sample()'s.  noise: optional dict(x_init, x_noise, a_init, a_noise) as in sample_viz.
+        The control quality of inpainted plans has not been evaluated."""
+        from .constrain import MODES, build_constraint
+        if not (self.use_planner and self.use_idm):
+            raise NotImplementedError("sample_constrained() needs both the planner and the IDM (use_planner / use_idm)")
+        if mode not in MODES:
+            raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+        seed = _seed_of(eval_rng)
+        cfg = self.config
+        oh = cfg["obs_horizon"]
+        if idm_steps is None and n_steps is not None and sampler != "ddpm":
+            idm_steps = n_steps                                # one schedule for both loops unless told otherwise
+        nz = dict(noise or {})
+
+        def run():
+            self._sync_weights()
+            obs_emb = self.get_obs_cond(self._vae_encode_t(self._postprocess(batch)["obs"])).contiguous()
+            B = obs_emb.shape[0]
+            g = None if goal is None else self._goal_embedding(goal, B)
+            tg, mk = build_constraint(cfg, B, target=None if target is None else self._t(target), mask=mask, goal=g, t_goal=t_goal,
+                                      goal_dims=goal_dims)
+            lo, hi, amode = self._action_bounds()
+            x, plan, action = self._engine.agent_sample_constrained(
+                obs_emb, oh, tg, mk, mode=mode, x_init=nz.get("x_init"), x_noise=nz.get("x_noise"), a_init=nz.get("a_init"),
+                a_noise=nz.get("a_noise"), seed=seed, row_offset=row_offset, sampler=sampler, planner_steps=n_steps, idm_steps=idm_steps,
+                action_bounds=(lo, hi), action_mode=amode)
+            out = [action, plan, x]
+            if obs_emb.shape[1] > oh:                          # from a training batch, not inference (:447-448)
+                out.append(self._engine.mean_sq_diff(x, obs_emb[:, oh:]))
+            return out
+        res, rec = self._call(run, lambda: run() + [None])             # plan_viz re-decodes itself from the new plan
+        action, plan, x = (DeviceArray(t, record=rec) for t in res[:3])
+        metrics = {"plan": plan, "x": x}
+        if len(res) > 3:
+            metrics["plan_mse"] = DeviceArray(res[3], record=rec)
+        S = self._engine.image_size
+        viz = DeviceArray(thunk=lambda: self._vae_decode_t(plan.tensor), shape=tuple(plan.shape[:2]) + (3, S, S), record=rec)
+        if decode:
+            viz.tensor
+        metrics["plan_viz"] = viz
+        return action, metrics
+
     # ---- best-of-N planning (defined by this repository: DESIGN.md 4.14; csrc/select.hip) ----------------------------------
     def _goal_embedding(self, goal, B):
         """`goal`: normalised embeddings (B, D), or an observation dict in batch['obs'] form (embedded like the batch, frame 0)."""

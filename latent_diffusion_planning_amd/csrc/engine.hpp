@@ -58,6 +58,7 @@ struct PlannerState {
   // workspaces (sized for ws_B samples)
   int ws_B = 0;
   DevBuf state, cond, film_g, bufA, bufB, bufC, bufR, noise, xchg, kw_slab;
+  DevBuf ctarget, cmask;          // constrained planning (constrain.hip): the call's target (float) and mask (uint8) padded like `state`, zero beyond D and the real rows
   size_t xchg_stride = 0;         // granules per conv launch
   uint64_t calls = 0;             // planner calls on this handle (slab hygiene, see planner_prepare)
   std::vector<DevBuf> skip;
@@ -82,6 +83,7 @@ struct GraphKey {
   int kind, B, n_steps, sampler, noise_mode;      // kind 0 planner loop, 1 IDM loop, 2 joint sample()
   int n_steps2 = 0, noise_mode2 = 0;              // joint graph: the IDM loop's step count / noise mode
   int begin = 0, end = -1;                        // planner loops (kind 0, 2): the executed steps [begin, end) of n_steps; (0, -1) = no planner range (the IDM loop, kind 1)
+  int constrain = 0;                              // planner loops: 0 = the free loop, else the LDP_CONSTRAIN_* mode whose launches the graph carries (constrain.hip)
   bool operator<(const GraphKey& o) const {
     if (kind != o.kind) return kind < o.kind;
     if (B != o.B) return B < o.B;
@@ -91,7 +93,8 @@ struct GraphKey {
     if (n_steps2 != o.n_steps2) return n_steps2 < o.n_steps2;
     if (noise_mode2 != o.noise_mode2) return noise_mode2 < o.noise_mode2;
     if (begin != o.begin) return begin < o.begin;
-    return end < o.end;
+    if (end != o.end) return end < o.end;
+    return constrain < o.constrain;
   }
 };
 
@@ -259,7 +262,9 @@ inline int bucket_rows(int B, bool explicit_noise) { return explicit_noise ? B :
 // loop is (0, n_steps)).  Step i is the same step whatever the range: coefficients, timestep, noise row, Philox key and exchange tag
 // all carry i itself.  idm_loop always runs all n_steps and does not read them.  The default end = -1 is no range: planner_loop refuses
 // it (LDP_EINVAL), so a planner caller that forgets the two fields fails loudly instead of running zero steps.
-struct LoopSpec { int n_steps = 0, sampler = 0; bool explicit_noise = false; int begin = 0, end = -1; };
+// constrain: 0, or the LDP_CONSTRAIN_* mode of a constrained loop (constrain.hip): C_begin in front of the first step and C_{i+1} behind
+// step i, on the target / mask staged into P.ctarget / P.cmask.
+struct LoopSpec { int n_steps = 0, sampler = 0; bool explicit_noise = false; int begin = 0, end = -1; int constrain = 0; };
 int check_step_range(int begin, int end, int n_steps, const char* what);
 struct WarmSpec;                                 // a warm start of the planner state (below)
 int check_sampler(int sampler, int n_steps, int n_train, const char* what);
@@ -305,4 +310,18 @@ int plan_warm_init_launch(const float* x_prev, const int32_t* slot_dev, float* d
                           float a, float s, uint64_t seed, uint64_t row0, hipStream_t st);
 // dst[(slot[b] or b), j, c] <- src[b, j, c], c < D: the padded loop state (B, T, DP) into rows of an unpadded (n_slots, T, D) table
 int unpad_rows_index_launch(const float* src, float* dst, const int32_t* slot_dev, int B, int T, int D, int DP, hipStream_t st);
+
+// ---- constrained planning (constrain.hip) -------------------------------------------------------------------
+int check_constrain_mode(int mode);              // LDP_EINVAL unless LDP_CONSTRAIN_CLAMP / LDP_CONSTRAIN_REPAINT
+// level j in 0 .. n_steps: (a, s) = warm_coefs at t_j for j < n_steps, exactly (1, 0) at j = n_steps; LDP_EINVAL names `level` outside
+int level_coefs(int n_train, int n_steps, int level, float* a, float* s);
+// out <- mask != 0 ? (noise ? fma(a, target, rn(s * z)) : target) : x, all four with row stride ld; z = philox_normal(seed, (row0 + r) * DP
+// + c, level, LDP_PHILOX_STREAM_CONSTRAIN) with (seed, row0) read from `ctl` when it is given (captured loops), else the arguments
+int plan_constrain_launch(const float* x, const float* target, const uint8_t* mask, float* out, int ld, int64_t rows, int D, int DP, float a,
+                          float s, int level, bool noise, const uint64_t* ctl, uint64_t seed, uint64_t row0, hipStream_t st);
+// target / mask (B, T, D) in caller memory -> P.ctarget / P.cmask (Bg, T, DP), zero beyond D and beyond the B real rows (eager, one launch;
+// the buffers grow with the workspace and drop the captured graphs when they move)
+int constrain_stage(ldp_handle* h, const float* target, const uint8_t* mask, int B, int Bg, hipStream_t st);
+// C_level on the loop state, read from the staged buffers and the planner's control block: one launch, counted in last_total_launches
+int planner_constrain_level(ldp_handle* h, int Bg, const LoopSpec& L, int level, hipStream_t q);
 }  // namespace ldp

@@ -17,6 +17,7 @@ from ._lib import (LDPHipError, LDPHipFault, LdpConfig, MOD_ENCODER, MOD_IDM, MO
                    SAMPLER_DDIM, SAMPLER_DDPM, check)
 
 _SAMPLERS = {"ddpm": SAMPLER_DDPM, "ddim": SAMPLER_DDIM}
+_CONSTRAIN_MODES = {"clamp": _lib.CONSTRAIN_CLAMP, "repaint": _lib.CONSTRAIN_REPAINT}
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -401,6 +402,103 @@ class HipEngine:
                                           _ptr(x), _ptr(plan), _ptr(act), _ptr(lo), _ptr(hi), adim, int(action_mode), B,
                                           1 if use_graph else 0, self._stream()))
         del keep
+        self.call_seq += 1
+        return x, plan, act
+
+    # -- constrained planning (csrc/constrain.hip) ----------------------------------------------------
+    def _constraint(self, target, mask, mode, B: int):
+        """target (B, T, D) float32, mask (B, T, D) uint8 (bool is taken as 0 / 1) and the LDP_CONSTRAIN_* mode for the C ABI.  `mode` is
+        'clamp' / 'repaint' (anything else is a ValueError here) or the integer itself (the library checks it)."""
+        if target is None or mask is None:
+            raise ValueError("target and mask are both required")
+        if isinstance(mode, str):
+            if mode not in _CONSTRAIN_MODES:
+                raise ValueError(f"mode must be one of {sorted(_CONSTRAIN_MODES)}, got {mode!r}")
+            mode = _CONSTRAIN_MODES[mode]
+        tg = _f32(target, self.device)
+        mk = mask if torch.is_tensor(mask) else torch.as_tensor(np.asarray(mask))
+        if mk.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f"mask must be uint8 or bool, got {mk.dtype}")
+        mk = mk.to(device=self.device, dtype=torch.uint8).contiguous()
+        _want("target", tg, (B, self.T, self.D))
+        _want("mask", mk, (B, self.T, self.D))
+        return tg, mk, int(mode)
+
+    def plan_constrain(self, x: torch.Tensor, target, mask, level: int, *, mode="repaint", seed: int = 0, row_offset: int = 0,
+                       sampler: str = "ddim", n_steps: Optional[int] = None) -> torch.Tensor:
+        """The constraint operation C_level alone (one launch): x (B, T, D) with the entries under `mask` replaced by `target` at the
+        noise level of `level` in 0 .. n_steps -> a new (B, T, D) tensor; every other element keeps its bits."""
+        xt = _f32(x, self.device)
+        B = int(xt.shape[0])
+        _want("x", xt, (B, self.T, self.D))
+        tg, mk, md = self._constraint(target, mask, mode, B)
+        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
+        out = torch.empty_like(xt)
+        check(self.lib.ldp_plan_constrain(self._h, _ptr(xt), _ptr(tg), _ptr(mk), md, _SAMPLERS[sampler], n_steps, int(level),
+                                          C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _ptr(out), B, self._stream()))
+        return out
+
+    def plan_sample_constrained(self, cond: Optional[torch.Tensor], target, mask, *, mode="repaint", step_begin: int = 0,
+                                step_end: Optional[int] = None, B: Optional[int] = None, x_init: Optional[torch.Tensor] = None,
+                                step_noise: Optional[torch.Tensor] = None, seed: int = 0, row_offset: int = 0, sampler: str = "ddpm",
+                                n_steps: Optional[int] = None, use_graph: bool = True) -> torch.Tensor:
+        """plan_sample_range with the constraint applied in the loop: C_begin in front of the first executed step and C_{i+1} behind
+        step i, inside the captured graph (default range: the whole loop).  An empty range returns C_begin of the initial state."""
+        cond_t = None if cond is None else _f32(cond, self.device)
+        if B is None:
+            B = cond_t.shape[0] if cond_t is not None else x_init.shape[0]
+        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
+        step_end = n_steps if step_end is None else int(step_end)
+        xi = None if x_init is None else _f32(x_init, self.device)
+        nz = None if step_noise is None else _f32(step_noise, self.device)
+        _want("cond", cond_t, (B, self.G))
+        _want("x_init", xi, (B, self.T, self.D))
+        _want("step_noise", nz, (n_steps, B, self.T, self.D))
+        tg, mk, md = self._constraint(target, mask, mode, B)
+        out = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_plan_sample_constrained(self._h, _ptr(cond_t), _ptr(xi), _ptr(nz), _ptr(tg), _ptr(mk), md,
+                                                   C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _SAMPLERS[sampler], n_steps,
+                                                   int(step_begin), step_end, _ptr(out), B, 1 if use_graph else 0, self._stream()))
+        self.call_seq += 1
+        return out
+
+    def agent_sample_constrained(self, obs_emb: torch.Tensor, obs_horizon: int, target, mask, *, mode="repaint", x_init=None,
+                                 x_noise=None, a_init=None, a_noise=None, seed: int = 0, row_offset: int = 0, sampler: str = "ddpm",
+                                 planner_steps: Optional[int] = None, idm_steps: Optional[int] = None, action_bounds=None,
+                                 action_mode: int = 0, use_graph: bool = True, x_store=None):
+        """agent_sample whose planner loop is the constrained one -> (x, plan, action) as agent_sample.  x_store (a warm start's table,
+        agent_resample) is refused: a constraint together with a warm start is not built."""
+        if x_store is not None:
+            raise ValueError("a constraint (target / mask) together with a warm start (x_store) is not built")
+        ob = _f32(obs_emb, self.device)
+        B, H = ob.shape[0], ob.shape[1]
+        _want("obs_emb", ob, (B, H, self.D))
+        tg, mk, md = self._constraint(target, mask, mode, B)
+        ps = self.planner_train_steps if planner_steps is None else int(planner_steps)
+        is_ = self.idm_train_steps if idm_steps is None else int(idm_steps)
+        R = B * self.ah
+        xi = None if x_init is None else _f32(x_init, self.device)
+        xn = None if x_noise is None else _f32(x_noise, self.device)
+        ai = None if a_init is None else _f32(a_init, self.device)
+        an = None if a_noise is None else _f32(a_noise, self.device)
+        _want("x_init", xi, (B, self.T, self.D))
+        _want("x_noise", xn, (ps, B, self.T, self.D))
+        _want("a_init", ai, (R, self.A))
+        _want("a_noise", an, (is_, R, self.A))
+        lo = hi = None
+        adim = 0
+        if action_bounds is not None:
+            lo, hi = self._bounds(*action_bounds)
+            adim = lo.numel()
+            if adim not in (1, self.A) or hi.numel() != adim:
+                raise ValueError(f"action bounds must have length 1 or {self.A}")
+        x = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
+        plan = torch.empty((B, self.ah + 1, self.D), device=self.device, dtype=torch.float32)
+        act = torch.empty((B, self.ah, self.A), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_agent_sample_constrained(self._h, _ptr(ob), H, int(obs_horizon), _ptr(xi), _ptr(xn), _ptr(ai), _ptr(an),
+                                                    _ptr(tg), _ptr(mk), md, C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset),
+                                                    _SAMPLERS[sampler], ps, is_, _ptr(x), _ptr(plan), _ptr(act), _ptr(lo), _ptr(hi), adim,
+                                                    int(action_mode), B, 1 if use_graph else 0, self._stream()))
         self.call_seq += 1
         return x, plan, act
 
