@@ -42,6 +42,8 @@ extern "C" {
 
 #define LDP_SAMPLER_DDPM 0 /* FlaxDDPMScheduler.step semantics (reference) */
 #define LDP_SAMPLER_DDIM 1 /* eta = 0, defined by this repo */
+#define LDP_SAMPLER_DPMPP 2 /* DPM-Solver++(2M) on the clipped data prediction over a registered timestep table, defined by this repo
+                             * ("solver sampler" below) */
 
 #define LDP_MAX_LEVELS 4
 
@@ -349,6 +351,43 @@ LDP_API int ldp_agent_sample_constrained(ldp_handle* h, const float* obs_emb, in
                                          int32_t planner_steps, int32_t idm_steps, float* x_out, float* plan_out, float* action_out,
                                          const float* act_lo, const float* act_hi, int32_t act_dim, int32_t act_mode, int32_t B,
                                          int32_t use_graph, void* stream);
+
+/* -- solver sampler (defined by this repo; the reference has DDPM only) -----------------------------------------
+ * LDP_SAMPLER_DPMPP is DPM-Solver++(2M) (Lu et al. 2022) on the clipped data prediction: a second-order multistep solver of the
+ * probability-flow ODE that costs one U-Net evaluation per step, like DDIM, and pays off on a timestep grid uniform in log-SNR, which
+ * t_i = (n-1-i) * stride cannot express.  The sampler therefore runs over a REGISTERED timestep table, one per step count.
+ *
+ * ldp_solver_timesteps: registers ts (n_steps int32 on the host; first executed step first) as the table sampler 2 uses whenever it is
+ * called with this n_steps, and computes its coefficient rows (host, float64 from the float32 abar table, cast to float32), with
+ * alpha = sqrt(abar), sigma = sqrt(1 - abar), lambda = 1/2 log(abar / (1 - abar)), row i the step from t = ts[i] to s = ts[i+1] and
+ * h_i = lambda_s - lambda_t:
+ *   inv_a = 1 / alpha_t,  sg = sigma_t,  c_x = sigma_s / sigma_t,  c_D = alpha_s - sigma_s alpha_t / sigma_t,  w = h_i / (2 h_{i-1})
+ * The last row goes to the clean level (alpha_s = 1, sigma_s = 0: c_x = 0, c_D = 1); w = 0 in row 0 and in the last row.
+ * LDP_EINVAL, naming the entry: n_steps outside 1 .. planner_train_steps, an entry outside 0 .. planner_train_steps-1, a table that is
+ * not strictly decreasing, a last entry that is not 0.  Registering the same table again does nothing; a different table for an
+ * n_steps that already has one replaces it and drops the captured graphs.
+ *
+ * The update of executed step i, ONE elementwise launch (csrc/solver.hip plan_solver_kernel), each operation rounded to fp32 once:
+ *   x0     = clamp(fma(-sg, eps, x) * inv_a, -1, 1)             (the scheduler's clip_sample)
+ *   Dv     = second ? fma(w, x0 - x0_prev, x0) : x0
+ *   x_out  = fma(c_x, x, c_D * Dv);    x0_out = x0
+ * ldp_plan_solver_step: that update on caller memory with row `step` of the table of n_steps; x, eps, x_out, x0_out (B, T, D), x0_prev
+ * (B, T, D) or NULL; second = x0_prev != NULL && step < n_steps-1.  x_out may be x and x0_out may be x0_prev.  Exists for tests and
+ * tools: the loop runs the same kernel on its own buffers.  LDP_ESTATE without a table for n_steps; LDP_EINVAL for a step outside
+ * 0 .. n_steps-1.
+ *
+ * Under sampler 2, ldp_plan_sample / ldp_plan_sample_range (and through them ldp_plan_candidates), ldp_policy_sample and
+ * ldp_agent_sample run, per executed step i of [begin, end): the U-Net at t = ts[i] writing eps only, then the solver launch, which
+ * updates the loop state and the x0 history in place (one launch more per step than DDIM; no step noise is drawn
+ * and step_noise is ignored, as for DDIM).  Step i is second order iff i > begin and i < n_steps-1.  EVERY CALL STARTS WITH AN EMPTY
+ * HISTORY, so a range that starts at begin > 0 starts first order: under this sampler ranges do NOT compose bit for bit ((0, m) then
+ * (m, n) differs from (0, n) in step m).  x_T is ldp_plan_sample's Philox draw, whatever the sampler.  ldp_agent_sample's IDM loop
+ * then runs DDIM with idm_steps.  Without a table for n_steps these calls fail with LDP_ESTATE, naming ldp_solver_timesteps.
+ * ldp_idm_sample, ldp_plan_warm_init, ldp_agent_resample, ldp_plan_constrain, ldp_plan_sample_constrained and
+ * ldp_agent_sample_constrained refuse sampler 2 with LDP_EINVAL (not built: their level coefficients assume the uniform grid). */
+LDP_API int ldp_solver_timesteps(ldp_handle* h, const int32_t* ts_host, int32_t n_steps);
+LDP_API int ldp_plan_solver_step(ldp_handle* h, const float* x, const float* eps, const float* x0_prev, int32_t n_steps, int32_t step,
+                                 float* x_out, float* x0_out, int32_t B, void* stream);
 
 /* -- StableVAE ----------------------------------------------------------------------------
  * FlaxAutoencoderKL.encode(x).latent_dist.mean   (call site agent/ldp_agent.py:55-60)

@@ -18,6 +18,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ldp_hip.h")
 
 LDP_MAX_LEVELS = 4
 SAMPLER_DDPM, SAMPLER_DDIM = 0, 1
+SAMPLER_DPMPP = 2                   # LDP_SAMPLER_DPMPP: DPM-Solver++(2M) over a registered timestep table (csrc/solver.hip)
 MOD_PLANNER, MOD_IDM, MOD_VAE, MOD_ENCODER = 1, 2, 4, 8
 RESNET_SLOTS, RESNET_FEATURES = 4, 1024       # encoder0 .. encoder3 of a handle; [expected_x (512) | expected_y (512)] per frame
 RESNET_TRAIN_MAX_FRAMES = 1024                # frames per ldp_train_encoder_forward (csrc/resnet_train.hpp RNT_MAX_FRAMES)
@@ -96,6 +97,8 @@ SIGNATURES: Dict[str, tuple] = {
     "ldp_agent_sample_constrained": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_uint64, C.c_int64,
                                                C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32,
                                                C.c_int32, C.c_void_p]),
+    "ldp_solver_timesteps": (C.c_int, [_H, C.c_void_p, C.c_int32]),
+    "ldp_plan_solver_step": (C.c_int, [_H, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP, C.c_int32, C.c_void_p]),
     "ldp_plan_candidates": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_uint64, C.c_int32,
                                       C.c_int32, _FP, C.c_int32, C.c_void_p]),
     "ldp_plan_cost_density": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _FP, C.c_void_p]),

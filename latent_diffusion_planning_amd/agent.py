@@ -720,6 +720,8 @@ class LDPAgent(_EngineCalls):
         if noise is not None:
             a_init, a_noise = noise.get("a_init"), noise.get("a_noise")
         rows_per = trans.shape[0] // B
+        if sampler == "dpmpp":                                 # the solver is the planner's: the IDM loop of such a call is DDIM
+            sampler = "ddim"
         a = self._engine.idm_sample(trans, a_init=a_init, step_noise=a_noise, seed=seed,
                                     row_offset=row_offset * rows_per, sampler=sampler, n_steps=n_steps)
         a = a.reshape(B, -1, a.shape[-1])
@@ -762,6 +764,35 @@ class LDPAgent(_EngineCalls):
         """Alias named by BASELINE.json's north_star (the reference has no such method)."""
         return self.sample(batch, eval_rng, **kw)[0]
 
+    def _solver_setup(self, sampler, n_steps, idm_steps, timesteps):
+        """The host side of sampler="dpmpp" (DPM-Solver++(2M) over a timestep table: DESIGN.md 4.18), before any GPU work: the IDM loop
+        of such a call is DDIM with idm_steps, which must divide idm_n_diffusion_steps; timesteps = "logsnr" / "uniform" / a sequence of
+        n_steps integers is registered with every engine of this agent as the table of n_steps (None: the table the engine holds, or
+        the log-SNR grid when it holds none)."""
+        if sampler != "dpmpp":
+            if timesteps is not None:
+                raise ValueError('timesteps= belongs to sampler="dpmpp"')
+            return
+        from .schedule import solver_timesteps
+        cfg = self.config
+        ns = int(cfg["planner_n_diffusion_steps"] if n_steps is None else n_steps)
+        if self.use_idm:
+            idm_n = int(cfg["idm_n_diffusion_steps"])
+            k = idm_n if idm_steps is None else int(idm_steps)
+            if k < 1 or idm_n % k != 0:
+                raise ValueError(f"idm_steps = {k} must divide idm_n_diffusion_steps = {idm_n} (the IDM loop of a \"dpmpp\" call is DDIM; "
+                                 "idm_steps defaults to n_steps)")
+        if timesteps is None:
+            return
+        if isinstance(timesteps, str):
+            ts = solver_timesteps(int(cfg["planner_n_diffusion_steps"]), ns, timesteps)
+        else:
+            ts = np.asarray(timesteps, dtype=np.int64).reshape(-1)
+            if len(ts) != ns:
+                raise ValueError(f"timesteps must have n_steps = {ns} entries, got {len(ts)}")
+        for e in self._engines():
+            e.set_solver_timesteps(ts)
+
     def _sample_core(self, batch, seed, noise, row_offset, sampler, n_steps, idm_steps):
         """normalize -> vae_encode -> get_obs_cond -> ONE ldp_agent_sample (planner loop, plan assembly,
         IDM loop, action un-normalisation as one captured graph).  -> (action, plan, x, obs_emb) tensors."""
@@ -779,7 +810,7 @@ class LDPAgent(_EngineCalls):
         return action, plan, x, obs_emb
 
     def sample_viz(self, batch, eval_rng, noise=None, decode=True, row_offset=0,
-                   sampler="ddpm", n_steps=None, idm_steps=None):
+                   sampler="ddpm", n_steps=None, idm_steps=None, timesteps=None):
         """-> (action (B, ah, A), {'plan' (B, ah+1, D), 'plan_viz' (B, ah+1, 3, S, S)[, 'plan_mse']}), all
         DeviceArrays.
         noise: optional dict(x_init (B,T,D), x_noise (S,B,T,D), a_init (B*ah,A), a_noise (S,B*ah,A))
@@ -787,14 +818,16 @@ class LDPAgent(_EngineCalls):
         reference always does, agent/ldp_agent.py:483); False = leave metrics['plan_viz'] lazy (the
         decode is 5 x 24.9 GFLOP per plan and callers such as eval_bc.py:144 discard it).
         row_offset: global index of this batch's first plan (keeps the Philox stream independent of how
-        candidates are sharded over GPUs).  n_steps / idm_steps: denoising steps (DDIM only; DDPM
-        visits every training timestep)."""
+        candidates are sharded over GPUs).  n_steps / idm_steps: denoising steps (DDIM and DPM-Solver++; DDPM
+        visits every training timestep).  sampler="dpmpp": the planner loop is DPM-Solver++(2M) over the timestep
+        table `timesteps` (None / "logsnr" / "uniform" / n_steps integers: _solver_setup), the IDM loop DDIM."""
         if not (self.use_planner and self.use_idm):
             raise NotImplementedError("sample() needs both the planner and the IDM (use_planner / use_idm)")
         seed = _seed_of(eval_rng)
         oh = self.config["obs_horizon"]
         if idm_steps is None and n_steps is not None and sampler != "ddpm":
             idm_steps = n_steps                                # one schedule for both loops unless told otherwise
+        self._solver_setup(sampler, n_steps, idm_steps, timesteps)
 
         def run():
             action, plan, x, obs_emb = self._sample_core(batch, seed, noise, row_offset, sampler, n_steps, idm_steps)
@@ -828,6 +861,8 @@ class LDPAgent(_EngineCalls):
         initial state is the warm one: no x_init).
         prev=None, warm_steps=None is the cold call that also returns 'x' (the existing path)."""
         from .replan import check_warm_steps
+        if sampler == "dpmpp":
+            raise NotImplementedError('a warm start under sampler="dpmpp" is not built: its noise levels assume the uniform timestep grid')
         if not (self.use_planner and self.use_idm):
             raise NotImplementedError("sample_warm() needs both the planner and the IDM (use_planner / use_idm)")
         if (prev is None) != (warm_steps is None):
@@ -890,6 +925,8 @@ class LDPAgent(_EngineCalls):
         """A Replanner (replan.py) for closed-loop control of up to n_slots environments: it keeps every environment's previous planner
         state on the device and runs a row warm -- the last warm_steps of n_steps planner steps -- whenever its slot holds one."""
         from .replan import Replanner
+        if sampler == "dpmpp":
+            raise NotImplementedError('a warm start under sampler="dpmpp" is not built: its noise levels assume the uniform timestep grid')
         if not (self.use_planner and self.use_idm):
             raise NotImplementedError("replanner() needs both the planner and the IDM (use_planner / use_idm)")
         return Replanner(self, n_slots, warm_steps, sampler=sampler, n_steps=n_steps, shift=shift)
@@ -908,6 +945,8 @@ class LDPAgent(_EngineCalls):
         nothing given the call is sample()'s.  noise: optional dict(x_init, x_noise, a_init, a_noise) as in sample_viz.
         The control quality of inpainted plans has not been evaluated."""
         from .constrain import MODES, build_constraint
+        if sampler == "dpmpp":
+            raise NotImplementedError('a constraint under sampler="dpmpp" is not built: its noise levels assume the uniform timestep grid')
         if not (self.use_planner and self.use_idm):
             raise NotImplementedError("sample_constrained() needs both the planner and the IDM (use_planner / use_idm)")
         if mode not in MODES:
@@ -1025,7 +1064,7 @@ class LDPAgent(_EngineCalls):
         return checked(tail) + [cost_all.t().contiguous(), x_all.reshape(N, B, T, D).transpose(0, 1).contiguous()]
 
     def sample_best_of(self, batch, eval_rng, n_candidates, score="density", bandwidth=0.5, goal=None, goal_weight=None, t_goal=None,
-                       sampler="ddpm", n_steps=None, idm_steps=None, noise=None, decode=False, prev=None, warm_steps=None):
+                       sampler="ddpm", n_steps=None, idm_steps=None, noise=None, decode=False, prev=None, warm_steps=None, timesteps=None):
         """Draw n_candidates plans per observation, score them on the GPU, act on the best one
         -> (action (B, ah, A), metrics): the action of the winning plan through the IDM, and
            metrics = {'plan' (B, ah+1, D), 'plan_viz' (lazy unless decode), 'best_index' (B,), 'best_cost' (B,), 'costs' (B, N),
@@ -1038,7 +1077,7 @@ class LDPAgent(_EngineCalls):
                a callable -- receives the candidates (B, N, T, D) as a device tensor and returns costs (B, N) as a device tensor.
         Ties go to the lowest candidate index, a NaN cost counts as +inf.
         noise: explicit-noise dict with x_init (N*B, T, D) / x_noise (S, N*B, T, D) in candidate-major rows and a_init (B*ah, A) /
-        a_noise (S, B*ah, A) for the winners' IDM rows."""
+        a_noise (S, B*ah, A) for the winners' IDM rows.  sampler="dpmpp" / timesteps: as in sample_viz."""
         if not (self.use_planner and self.use_idm):
             raise NotImplementedError("sample_best_of() needs both the planner and the IDM (use_planner / use_idm)")
         if prev is not None or warm_steps is not None:
@@ -1048,6 +1087,7 @@ class LDPAgent(_EngineCalls):
         seed = _seed_of(eval_rng)
         if idm_steps is None and n_steps is not None and sampler != "ddpm":
             idm_steps = n_steps
+        self._solver_setup(sampler, n_steps, idm_steps, timesteps)
 
         def run():
             return self._best_of(batch, seed, N, score, bandwidth, goal, goal_weight, t_goal, sampler, n_steps, idm_steps, noise)

@@ -58,6 +58,7 @@ struct PlannerState {
   // workspaces (sized for ws_B samples)
   int ws_B = 0;
   DevBuf state, cond, film_g, bufA, bufB, bufC, bufR, noise, xchg, kw_slab;
+  DevBuf solver_eps, solver_x0;   // sampler 2 (solver.hip): the evaluation's eps (B, T, D) unpadded, and the previous step's clipped x0 padded like `state`
   DevBuf ctarget, cmask;          // constrained planning (constrain.hip): the call's target (float) and mask (uint8) padded like `state`, zero beyond D and the real rows
   size_t xchg_stride = 0;         // granules per conv launch
   uint64_t calls = 0;             // planner calls on this handle (slab hygiene, see planner_prepare)
@@ -162,6 +163,13 @@ struct Options {
 
 constexpr int LDP_STAT_GEMM_FUSED = 15, LDP_STAT_GEMM_REDUCE = 16;      // ldp_handle::stat_train_gemm
 
+// sampler 2 (solver.hip): one row of schedule.solver_coefficients, and the table registered for one step count
+struct SolverCoef { float t, inv_a, sg, c_x, c_D, w; };
+struct SolverTable {
+  std::vector<int32_t> ts;        // timesteps, first executed step first: strictly decreasing, the last is 0
+  std::vector<SolverCoef> rows;
+};
+
 struct GraphEntry {
   hipGraphExec_t exec;
   int64_t conv_launches, total_launches;
@@ -201,6 +209,7 @@ struct ldp_handle {
   bool f16_planner() const { return opt.planner_split_f16 != 0 && !range_fallback; }
   bool f16_vae() const { return opt.vae_split_f16 != 0 && !range_fallback; }
   ldp::Options opt;
+  std::map<int, ldp::SolverTable> solver_tabs;   // ldp_solver_timesteps: n_steps -> the table sampler 2 runs with that step count
   ldp::DevBuf plan_out, act_out, obs_last;   // joint sample(): handle-owned outputs the graph writes
   ldp::DevBuf cand_cond;                 // ldp_plan_candidates (select.hip): the condition tiled over the candidate rows (no graph node reads it)
   ldp::DevBuf slot_buf;                  // ldp_plan_warm_init / ldp_agent_resample (replan.hip): a slot table given on the host (no graph node reads it)
@@ -267,7 +276,9 @@ inline int bucket_rows(int B, bool explicit_noise) { return explicit_noise ? B :
 struct LoopSpec { int n_steps = 0, sampler = 0; bool explicit_noise = false; int begin = 0, end = -1; int constrain = 0; };
 int check_step_range(int begin, int end, int n_steps, const char* what);
 struct WarmSpec;                                 // a warm start of the planner state (below)
-int check_sampler(int sampler, int n_steps, int n_train, const char* what);
+// solver_h: the handle whose registered tables may serve LDP_SAMPLER_DPMPP (LDP_ESTATE when it has none for n_steps); nullptr where that
+// sampler is not built (the IDM loop, warm starts, constraints: LDP_EINVAL)
+int check_sampler(int sampler, int n_steps, int n_train, const char* what, const ldp_handle* solver_h = nullptr);
 int entry_fault_check(ldp_handle* h);
 int planner_pre(ldp_handle* h, const float* cond, const float* x_init, const float* step_noise, uint64_t seed,
                 int64_t row_offset, const LoopSpec& L, int B, hipStream_t s, const WarmSpec* warm = nullptr);
@@ -324,4 +335,15 @@ int plan_constrain_launch(const float* x, const float* target, const uint8_t* ma
 int constrain_stage(ldp_handle* h, const float* target, const uint8_t* mask, int B, int Bg, hipStream_t st);
 // C_level on the loop state, read from the staged buffers and the planner's control block: one launch, counted in last_total_launches
 int planner_constrain_level(ldp_handle* h, int Bg, const LoopSpec& L, int level, hipStream_t q);
+// ---- DPM-Solver++(2M) sampler (solver.hip) -------------------------------------------------------------------
+const SolverTable* solver_table(const ldp_handle* h, int n_steps);      // the table registered for n_steps, or nullptr
+void make_solver_coefs(int n_train, const std::vector<int32_t>& ts, std::vector<SolverCoef>& out);
+// x0 = clamp(fma(-sg, eps, x) * inv_a, -1, 1); Dv = second ? fma(w, x0 - x0_prev, x0) : x0; x_out = fma(c_x, x, c_D * Dv); x0_out = x0 over the
+// columns c < D of `rows` rows; row strides ldx (x, x_out), ldh (x0_prev, x0_out), lde (eps).  x_out may be x, x0_out may be x0_prev.
+int plan_solver_launch(const float* x, const float* eps, const float* x0_prev, float* x_out, float* x0_out, int ldx, int ldh, int lde,
+                       int64_t rows, int D, const SolverCoef& k, bool second, hipStream_t st);
+// P.solver_eps / P.solver_x0 for Bg rows (they grow with the workspace and drop the captured graphs when they move)
+int solver_workspace(ldp_handle* h, int Bg);
+// the update of step i on the loop state, eps read from P.solver_eps, history in P.solver_x0: one launch, counted in last_total_launches
+int planner_solver_step(ldp_handle* h, int Bg, const SolverTable& tab, int i, bool second, hipStream_t q);
 }  // namespace ldp

@@ -96,10 +96,13 @@ def sample_best_of_sharded(agent, batch: dict, eval_rng, n_candidates: int, grou
     world = dist.get_world_size(group) if on else 1
     rank = dist.get_rank(group) if on else 0
     decode = kw.pop("decode", False)
+    timesteps = kw.pop("timesteps", None)
     kw = dict(dict(score="density", bandwidth=0.5, goal=None, goal_weight=None, t_goal=None, sampler="ddpm", n_steps=None,
                    idm_steps=None, noise=None), **kw)
     if kw["idm_steps"] is None and kw["n_steps"] is not None and kw["sampler"] != "ddpm":
         kw["idm_steps"] = kw["n_steps"]
+    # sampler="dpmpp": every rank registers the same timestep table (the log-SNR grid unless `timesteps` says otherwise)
+    agent._solver_setup(kw["sampler"], kw["n_steps"], kw["idm_steps"], timesteps)
     res = agent._best_of(batch, _seed_of(eval_rng), int(n_candidates), shard=(group, world, rank), **kw)
     return agent._best_of_result(res, None, decode)
 

@@ -14,9 +14,10 @@ import torch
 
 from . import _lib
 from ._lib import (LDPHipError, LDPHipFault, LdpConfig, MOD_ENCODER, MOD_IDM, MOD_PLANNER, MOD_VAE, RESNET_FEATURES, RESNET_SLOTS,
-                   SAMPLER_DDIM, SAMPLER_DDPM, check)
+                   SAMPLER_DDIM, SAMPLER_DDPM, SAMPLER_DPMPP, check)
+from .schedule import solver_timesteps
 
-_SAMPLERS = {"ddpm": SAMPLER_DDPM, "ddim": SAMPLER_DDIM}
+_SAMPLERS = {"ddpm": SAMPLER_DDPM, "ddim": SAMPLER_DDIM, "dpmpp": SAMPLER_DPMPP}
 _CONSTRAIN_MODES = {"clamp": _lib.CONSTRAIN_CLAMP, "repaint": _lib.CONSTRAIN_REPAINT}
 
 
@@ -108,6 +109,7 @@ class HipEngine:
         self.fault_kinds = 0                          # every kind of fault this handle ever reported (poll_fault_kinds)
         self.last_fault_kinds = 0
         self._bounds_cache = {}
+        self.solver_tables = {}                       # n_steps -> the timestep table registered for sampler "dpmpp" (set_solver_timesteps)
         self._h = C.c_void_p()
         check(self.lib.ldp_create(C.byref(cfg), C.byref(self._h)))
 
@@ -287,6 +289,48 @@ class HipEngine:
                              t_res=taps[off_res:off_res + numel].view(n, pos, ld) if off_res >= 0 else None))
         return eps, rows
 
+    # -- DPM-Solver++(2M) sampler (csrc/solver.hip) ---------------------------------------------------
+    def set_solver_timesteps(self, ts) -> np.ndarray:
+        """Registers `ts` (strictly decreasing integers ending in 0, first executed step first) as the timestep table sampler "dpmpp"
+        uses whenever it is called with n_steps = len(ts).  The same table again does nothing; another one replaces it (and drops the
+        captured graphs)."""
+        a = np.ascontiguousarray(np.asarray(ts.cpu() if torch.is_tensor(ts) else ts, dtype=np.int64).reshape(-1).astype(np.int32))
+        check(self.lib.ldp_solver_timesteps(self._h, a.ctypes.data_as(C.c_void_p), int(a.size)))
+        self.solver_tables[int(a.size)] = a.astype(np.int64)
+        return self.solver_tables[int(a.size)]
+
+    def _sampler(self, sampler: str, n_steps: int) -> int:
+        """The sampler id of the C ABI.  "dpmpp" runs over a registered timestep table: when this engine holds none for n_steps, the
+        log-SNR grid of schedule.solver_timesteps is registered first -- here, so every caller that passes `sampler` through gets it."""
+        sid = _SAMPLERS[sampler]
+        if sid == SAMPLER_DPMPP and int(n_steps) not in self.solver_tables:
+            self.set_solver_timesteps(solver_timesteps(self.planner_train_steps, int(n_steps), "logsnr"))
+        return sid
+
+    def plan_solver_step(self, x: torch.Tensor, eps: torch.Tensor, step: int, n_steps: int, x0_prev: Optional[torch.Tensor] = None, *,
+                         inplace: bool = False):
+        """One solver update (one launch) with row `step` of the table registered for n_steps: x, eps (B, T, D), x0_prev (B, T, D) or None
+        (first order) -> (x_next, x0), x0 the clipped data prediction the next step takes as x0_prev.  inplace: x and x0_prev (float32
+        device tensors) are overwritten and returned."""
+        if inplace:
+            xt, hp = x, x0_prev
+            for name, t in (("x", xt), ("x0_prev", hp)):
+                if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                    raise ValueError(f"inplace: {name} must be a contiguous float32 device tensor")
+        else:
+            xt = _f32(x, self.device)
+            hp = None if x0_prev is None else _f32(x0_prev, self.device)
+        B = int(xt.shape[0])
+        ep = _f32(eps, self.device)
+        _want("x", xt, (B, self.T, self.D))
+        _want("eps", ep, (B, self.T, self.D))
+        _want("x0_prev", hp, (B, self.T, self.D))
+        x_out = xt if inplace else torch.empty_like(xt)
+        x0_out = hp if inplace else torch.empty_like(xt)
+        check(self.lib.ldp_plan_solver_step(self._h, _ptr(xt), _ptr(ep), _ptr(hp), int(n_steps), int(step), _ptr(x_out), _ptr(x0_out), B,
+                                            self._stream()))
+        return x_out, x0_out
+
     def plan_sample(self, cond: Optional[torch.Tensor], B: Optional[int] = None,
                     x_init: Optional[torch.Tensor] = None, step_noise: Optional[torch.Tensor] = None,
                     seed: int = 0, row_offset: int = 0, sampler: str = "ddpm",
@@ -302,7 +346,7 @@ class HipEngine:
         _want("step_noise", nz, (n_steps, B, self.T, self.D))
         out = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
         check(self.lib.ldp_plan_sample(self._h, _ptr(cond_t), _ptr(xi), _ptr(nz), C.c_uint64(seed & (2**64 - 1)),
-                                       C.c_int64(row_offset), _SAMPLERS[sampler], n_steps, _ptr(out), B,
+                                       C.c_int64(row_offset), self._sampler(sampler, n_steps), n_steps, _ptr(out), B,
                                        1 if use_graph else 0, self._stream()))
         self.call_seq += 1
         return out
@@ -323,7 +367,7 @@ class HipEngine:
         _want("step_noise", nz, (n_steps, B, self.T, self.D))
         out = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
         check(self.lib.ldp_plan_sample_range(self._h, _ptr(cond_t), _ptr(xi), _ptr(nz), C.c_uint64(seed & (2**64 - 1)),
-                                             C.c_int64(row_offset), _SAMPLERS[sampler], n_steps, int(step_begin), int(step_end),
+                                             C.c_int64(row_offset), self._sampler(sampler, n_steps), n_steps, int(step_begin), int(step_end),
                                              _ptr(out), B, 1 if use_graph else 0, self._stream()))
         self.call_seq += 1
         return out
@@ -522,7 +566,7 @@ class HipEngine:
         _want("step_noise", nz, (n_steps, rows, self.T, self.D))
         out = torch.empty((rows, self.T, self.D), device=self.device, dtype=torch.float32)
         check(self.lib.ldp_plan_candidates(self._h, _ptr(ob), H, int(obs_horizon), B, int(c0), n_loc, _ptr(xi), _ptr(nz),
-                                           C.c_uint64(seed & (2**64 - 1)), _SAMPLERS[sampler], n_steps, _ptr(out),
+                                           C.c_uint64(seed & (2**64 - 1)), self._sampler(sampler, n_steps), n_steps, _ptr(out),
                                            1 if use_graph else 0, self._stream()))
         self.call_seq += 1
         return out
@@ -642,7 +686,7 @@ class HipEngine:
         plan = torch.empty((B, self.ah + 1, self.D), device=self.device, dtype=torch.float32)
         act = torch.empty((B, self.ah, self.A), device=self.device, dtype=torch.float32)
         check(self.lib.ldp_agent_sample(self._h, _ptr(ob), H, int(obs_horizon), _ptr(xi), _ptr(xn), _ptr(ai), _ptr(an),
-                                        C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _SAMPLERS[sampler], ps, is_,
+                                        C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), self._sampler(sampler, ps), ps, is_,
                                         _ptr(x), _ptr(plan), _ptr(act), _ptr(lo), _ptr(hi), adim, int(action_mode), B,
                                         1 if use_graph else 0, self._stream()))
         self.call_seq += 1
@@ -673,7 +717,7 @@ class HipEngine:
                 raise ValueError(f"action bounds must have length 1 or {self.D}")
         act = torch.empty((B, self.ah, self.D), device=self.device, dtype=torch.float32)
         check(self.lib.ldp_policy_sample(self._h, _ptr(ob), H, int(obs_horizon), int(img_width), _ptr(xi), _ptr(xn),
-                                         C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _SAMPLERS[sampler], n_steps, _ptr(act),
+                                         C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), self._sampler(sampler, n_steps), n_steps, _ptr(act),
                                          _ptr(lo), _ptr(hi), adim, int(action_mode), B, 1 if use_graph else 0, self._stream()))
         self.call_seq += 1
         return act

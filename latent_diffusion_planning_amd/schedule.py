@@ -96,6 +96,80 @@ def step_coefficients(sched: NoiseSchedule, n_steps: int, sampler: int) -> np.nd
     return out.astype(np.float32)
 
 
+# ---- DPM-Solver++(2M) on a registered timestep table (csrc/solver.hip) ------------------------------------------
+SAMPLER_DPMPP = 2
+
+
+def log_snr(sched: NoiseSchedule) -> np.ndarray:
+    """lambda_t = 1/2 log(abar_t / (1 - abar_t)), float64 from the float32 abar table."""
+    ac = sched.alphas_cumprod.astype(np.float64)
+    return 0.5 * np.log(ac / (1.0 - ac))
+
+
+def solver_timesteps(n_train: int, n_steps: int, spacing: str = "logsnr", t_first=None) -> np.ndarray:
+    """The timesteps a solver loop of n_steps visits, first executed step first: int64 (n_steps,), strictly decreasing, from t_first
+    (default n_train - max(1, n_train // n_steps): DDIM's first timestep when n_steps | n_train) down to 0.  'uniform' is DDIM's grid;
+    'logsnr' takes n_steps points linearly spaced in lambda from lambda(t_first) to lambda(0), maps each to the timestep with the
+    nearest lambda (ties to the lower timestep) and then forces the table strictly decreasing and long enough to reach 0."""
+    n_train, n_steps = int(n_train), int(n_steps)
+    if n_steps < 1:
+        raise ValueError(f"n_steps must be >= 1, got {n_steps}")
+    if spacing == "uniform":
+        if n_train % n_steps != 0:
+            raise ValueError(f"the uniform grid needs n_steps | n_train ({n_steps} vs {n_train})")
+        if t_first is not None and int(t_first) != n_train - n_train // n_steps:
+            raise ValueError(f"the uniform grid starts at {n_train - n_train // n_steps}, got t_first = {t_first}")
+        return step_timesteps(n_train, n_steps, SAMPLER_DDIM)
+    if spacing != "logsnr":
+        raise ValueError(f"spacing must be 'logsnr' or 'uniform', got {spacing!r}")
+    t_first = n_train - max(1, n_train // n_steps) if t_first is None else int(t_first)
+    if not 0 <= t_first < n_train:
+        raise ValueError(f"t_first must lie in 0..{n_train - 1}, got {t_first}")
+    if n_steps > t_first + 1:
+        raise ValueError(f"n_steps = {n_steps} distinct timesteps do not fit into t_first = {t_first} .. 0")
+    if n_steps == 1:
+        if t_first != 0:
+            raise ValueError(f"a one-step table is [0]: t_first must be 0, got {t_first}")
+        return np.zeros(1, dtype=np.int64)
+    lam = log_snr(make_schedule(n_train))
+    ts = np.zeros(n_steps, dtype=np.int64)
+    for i, p in enumerate(np.linspace(lam[t_first], lam[0], n_steps)):
+        ts[i] = int(np.argmin(np.abs(lam - p)))            # (argmin returns the first, i.e. the lower, timestep of a tie)
+    ts[0], ts[-1] = t_first, 0
+    for i in range(1, n_steps):
+        ts[i] = max(min(ts[i], ts[i - 1] - 1), n_steps - 1 - i)
+    return ts
+
+
+def solver_coefficients(sched: NoiseSchedule, ts, dtype=np.float32) -> np.ndarray:
+    """float32 (n, 8) rows of the solver kernel: [t, 1/alpha_t, sigma_t, c_x = sigma_s / sigma_t, c_D = alpha_s - sigma_s alpha_t /
+    sigma_t, w = h_i / (2 h_{i-1}), 0, 0] for the step from t = ts[i] to s = ts[i+1]; the last step goes to the clean level (alpha_s = 1,
+    sigma_s = 0: c_x = 0, c_D = 1).  w = 0 in row 0 and in the last row.  float64 until the final cast (dtype=np.float64: no cast)."""
+    ts = np.asarray(ts, dtype=np.int64)
+    n = len(ts)
+    ac = sched.alphas_cumprod.astype(np.float64)
+    lam = log_snr(sched)
+    out = np.zeros((n, COEF_STRIDE), dtype=np.float64)
+    h_prev = 0.0
+    for i, t in enumerate(ts):
+        a_t, s_t = math.sqrt(ac[t]), math.sqrt(1.0 - ac[t])
+        out[i, 0] = float(t)
+        out[i, 1] = 1.0 / a_t
+        out[i, 2] = s_t
+        if i == n - 1:
+            out[i, 3], out[i, 4] = 0.0, 1.0
+            continue
+        s = ts[i + 1]
+        a_s, s_s = math.sqrt(ac[s]), math.sqrt(1.0 - ac[s])
+        h = lam[s] - lam[t]
+        out[i, 3] = s_s / s_t
+        out[i, 4] = a_s - s_s * a_t / s_t
+        if i > 0:
+            out[i, 5] = h / (2.0 * h_prev)
+        h_prev = h
+    return out.astype(dtype)
+
+
 def _freqs(dim: int) -> np.ndarray:
     """exp(-j * ln(1e4)/(half-1)), evaluated in float32 like the reference's traced graph."""
     half = dim // 2
