@@ -730,7 +730,8 @@ LDP_API int64_t ldp_range_fallbacks(void);
  * StableVAE), "planner_split_mb2", "planner_split_t16"; the IDM above 256 plans: "idm_f16" (1: its MLPResNet blocks on two fp16 planes over 32-row
  * tiles, 0: exact fp32), "idm_f16_min_rows", "idm_f16_hs"; and the A/B switches listed in
  * csrc/engine.hpp; read-only counters "stat_mb2_launches", "stat_f16_launches", "stat_train_gemm_<nn|nt|tn>_<32|64|128>[_ki2]",
- * "stat_train_gemm_fused", "stat_train_gemm_reduce" (training GEMM launches per kernel instantiation).  Timing ablations for
+ * "stat_train_gemm_fused", "stat_train_gemm_reduce" (training GEMM launches per kernel instantiation), "stat_idm_f32_hs<1|2|4|8>[_ring][_nt]",
+ * "stat_idm_f16_hs<2|4>", "stat_idm_unfused" (fused IDM launches per kernel instantiation; calls of the unfused path).  Timing ablations for
  * tools/ (results WRONG by construction): "dbg" (bit mask), "repeat".  Test hook: "inject_fault" (1: an
  * exchange fault, 2: a range fault).
  * Read-only through ldp_get_option: "any_debug", "faults_seen", "range_faults_seen", "n_cu", "graphs".

@@ -162,6 +162,8 @@ struct Options {
 };
 
 constexpr int LDP_STAT_GEMM_FUSED = 15, LDP_STAT_GEMM_REDUCE = 16;      // ldp_handle::stat_train_gemm
+constexpr int LDP_STAT_IDM_F16_HS2 = 16, LDP_STAT_IDM_F16_HS4 = 17, LDP_STAT_IDM_UNFUSED = 18;      // ldp_handle::stat_idm
+inline int stat_idm_f32(int hs, bool ringed, bool stream) { return (hs == 1 ? 0 : hs == 2 ? 4 : hs == 4 ? 8 : 12) + (ringed ? 2 : 0) + (stream ? 1 : 0); }
 
 // sampler 2 (solver.hip): one row of schedule.solver_coefficients, and the table registered for one step count
 struct SolverCoef { float t, inv_a, sg, c_x, c_D, w; };
@@ -233,6 +235,10 @@ struct ldp_handle {
   // 64-row, 64-row KI = 2, 128 x 128}], then launches that finished split K in-launch and reduce_parts_kernel launches.  Read-only options
   // "stat_train_gemm_<nn|nt|tn>_<32|64|128>[_ki2]", "stat_train_gemm_fused", "stat_train_gemm_reduce"; the dry walk of a tape counts nothing.
   int64_t stat_train_gemm[17] = {};
+  // fused IDM launches (with IF_BLOCK and tail-only alike) enqueued since ldp_create, per instantiation of idm.hip's block kernels:
+  // idm_block_kernel<HS, RINGED, STREAM> at [4 log2(HS) + 2 RINGED + STREAM], idm_block_h16_kernel<2 / 4> at [16] / [17], and calls of
+  // idm_forward_unfused at [18].  Read-only options "stat_idm_f32_hs<1|2|4|8>[_ring][_nt]", "stat_idm_f16_hs<2|4>", "stat_idm_unfused".
+  int64_t stat_idm[19] = {};
   void* vae = nullptr;                   // VaeState (vae.hip)
   void* train = nullptr;                 // Trainer (train.hip): master parameters, gradients, Adam moments, launch tables; created by ldp_train_init
   void* resnet = nullptr;                // RnState (resnet.hip): the ResNet-18 image encoders of DPAgent (weight modules encoder0 .. encoder3)

@@ -919,6 +919,7 @@ static int idm_forward_unfused(ldp_handle* h, int R, const int* k_dev, int k, bo
   IdmState& I = h->idm;
   const int H = I.H, Bq = (R + 3) / 4;
   const bool fuse_ln0 = I.NB > 0 && H <= 1024;        // first block's LayerNorm rides in the input kernel
+  h->stat_idm[LDP_STAT_IDM_UNFUSED]++;
   if (fuse_ln0) {
     hipLaunchKernelGGL(idm_in_ln_kernel, dim3(R), dim3(256), 0, s, I.state.f(), I.AP, I.in_a.w.f(), I.A,
                        I.spart.f(), I.ctab.f(), k_dev, k, I.blks[0].ln_s.f(), I.blks[0].ln_b.f(), I.h0.f(),
@@ -983,6 +984,8 @@ struct FusedSeq {            // ping-pong bookkeeping of one enqueue sequence (h
     const bool ringed = hs >= 4 && nrt * hs <= h->n_cu && nrt >= 16 && !h->opt.idm_noring;
     const int r = f16 ? idm_block_h16_launch(hs, a, nrt, s) : idm_block_launch(hs, ringed, a, nrt, s);
     if (f16 && (a.flags & IF_BLOCK)) h->stat_f16_launches++;
+    // which instantiation was enqueued (ldp_handle::stat_idm: read-only options, host side only); hs is one of what the launchers know
+    if (r == 0) h->stat_idm[f16 ? (hs == 2 ? LDP_STAT_IDM_F16_HS2 : LDP_STAT_IDM_F16_HS4) : stat_idm_f32(hs, ringed && hs >= 4, a.stream_parts == 2)]++;
     h->last_total_launches++;
     if (a.flags & IF_BLOCK) h->last_conv_launches++;
     if (r != 0) return fail(LDP_EHIP, "fused IDM block launch failed: %s", hipGetErrorString((hipError_t)r));

@@ -61,10 +61,15 @@ class TorchParams:
         return key in self.raw
 
 
-def _freqs(dim, device):
+def _freqs(dim, device, exact=False):
+    """exact: exp itself in float64, rounded to float32 once.  A float32 exp is that value or an ulp off, by library and machine: NumPy's
+    vectorised one differs from it in up to 59 of 128 entries, libm's expf -- which fills the device's table (csrc/engine.hip
+    sinusoid_table) -- in none, and an ulp of f moves the argument k f by up to 7.6e-6.  The default stays the float32 exp the committed goldens
+    were made with; a test that bounds the device's error by float32 round-off asks for the device's own frequencies."""
     half = dim // 2
     step = np.float32(np.log(np.float32(10000.0))) / np.float32(half - 1)
-    f = np.exp(np.arange(half, dtype=np.float32) * -step).astype(np.float32)
+    x = np.arange(half, dtype=np.float32) * -step
+    f = np.exp(x.astype(np.float64)).astype(np.float32) if exact else np.exp(x).astype(np.float32)
     return torch.as_tensor(f, device=device)
 
 
@@ -266,11 +271,11 @@ def run_unet_stages(P, stages, x_btc, k, global_cond):
 
 
 # ------------------------------------------------------------------------------ IDM
-def idm_forward(P: TorchParams, s, a, k, time_dim=256, n_blocks=3):
+def idm_forward(P: TorchParams, s, a, k, time_dim=256, n_blocks=3, exact_freqs=False):
     dev = s.device
     r = s.shape[0]
     kk = _ksteps(k, r, dev)
-    arg = kk[:, None] * _freqs(time_dim, dev)[None, :]
+    arg = kk[:, None] * _freqs(time_dim, dev, exact_freqs)[None, :]
     tff = torch.cat([torch.cos(arg), torch.sin(arg)], dim=-1).to(P.dtype)
     c = F.mish(F.linear(tff, P.t("MLP_0/Dense_0/kernel").t(), P.t("MLP_0/Dense_0/bias")))
     c = F.linear(c, P.t("MLP_0/Dense_1/kernel").t(), P.t("MLP_0/Dense_1/bias"))
@@ -338,13 +343,13 @@ def planner_sample(P, obs_cond, x_init, step_noise=None, n_train=100, n_steps=10
 
 @torch.no_grad()
 def idm_sample(P, transition, a_init, step_noise=None, n_train=100, n_steps=100, sampler="ddpm",
-               stop_after=None):
+               stop_after=None, exact_freqs=False):
     tables = _tables(n_train)
     a = a_init.to(P.dtype)
     stride = n_train // n_steps
     for i in range(n_steps if stop_after is None else min(stop_after, n_steps)):
         k = (n_steps - 1 - i) * stride
-        eps = idm_forward(P, transition, a, k)
+        eps = idm_forward(P, transition, a, k, exact_freqs=exact_freqs)
         if sampler == "ddpm":
             a = ddpm_step(eps, k, a, step_noise[i] if k > 0 else None, tables)
         else:
