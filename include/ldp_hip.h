@@ -389,6 +389,57 @@ LDP_API int ldp_solver_timesteps(ldp_handle* h, const int32_t* ts_host, int32_t 
 LDP_API int ldp_plan_solver_step(ldp_handle* h, const float* x, const float* eps, const float* x0_prev, int32_t n_steps, int32_t step,
                                  float* x_out, float* x0_out, int32_t B, void* stream);
 
+/* -- guided planning (defined by this repo; the reference has nothing of the kind) ------------------------------
+ * The guided sampling of "Planning with Diffusion" (Janner et al. 2022, Alg. 1) with analytic costs: every denoising step moves the
+ * clipped data prediction one projected gradient step down a cost, then takes the scheduler's own step from there.  The cost of sample b
+ * on y (T, D), all weights >= 0:
+ *   J_b(y) = 1/2 sum_{t,c} wg[b,t,c] (y[t,c] - target[b,t,c])^2                                             soft goals / waypoints
+ *          + 1/2 sum_c lam[c] ( sum_{t=0..T-2} (y[t+1,c] - y[t,c])^2 + [anchor] (y[0,c] - anchor[b,c])^2 )   smoothness, continuity
+ *          + 1/2 sum_{t,c} beta[c] ( max(y - hi[c], 0)^2 + max(lo[c] - y, 0)^2 )                             box bounds
+ * g = grad_y J: elementwise plus a three-point stencil along T (row 0 has only its forward difference without an anchor).  Executed
+ * step i of a guided loop, with row i of the scheduler's coefficients (DDPM or DDIM) and the step size rho[i]:
+ *   y  = clip((x - sqrt(1 - abar_t) eps) / sqrt(abar_t), -1, 1);    y' = clip(y - rho[i] g(y), -1, 1)
+ *   x <- c_x0 y' + c_x x + c_eps eps + sigma z
+ * eps is used as the network wrote it; z is the fused step's draw (LDP_PHILOX_STREAM_STEP, step i, element (row_offset * T + r) * padded
+ * width + c) or the explicit step noise, so with rho = 0 the guided loop is the free loop up to rounding.  Every operation is rounded to
+ * fp32 once, in the order csrc/guide.hip states.  With L = max wg + 4 max lam + max beta, rho[i] L <= 1 guarantees J(y') <= J(y); the
+ * library does not check this bound (guide.build_guide does).
+ *
+ * ldp_plan_guide_step: that step on caller memory, ONE launch (csrc/guide.hip plan_guide_step_kernel: a work-group owns whole samples,
+ * the stencil goes through LDS).  All pointers are device memory: x, x_out (B, T, ldx) with ldx >= D (x_out may be x; columns beyond D
+ * are neither read nor written), eps and noise (B, T, D; noise NULL: the Philox draw of (seed, row_offset)), target, wg (B, T, ldg) and
+ * anchor (B, ldg) or NULL with ldg >= D, lam, beta, lo, hi (D), rho (n_steps; entry `step` is read).  pred_horizon <= 16, obs_dim <= 128.
+ * ldp_plan_guide_cost: out[r] = J of row r of x (rows, T, D) under guide row r / n_per (rows = B * n_per: n_per candidates per
+ * observation), ONE launch, one wave per sample with a fixed summation order: bitwise the same whatever the batch.  target, wg
+ * (B, T, D), anchor (B, D) or NULL.
+ *
+ * ldp_plan_sample_guided: ldp_plan_sample_range with the guided loop over [step_begin, step_end): per executed step the U-Net writing
+ * eps only, then the guided step -- one launch more per step than the free loop; step i is the same step whatever the range, so ranges
+ * compose bit for bit.  target, wg, anchor (NULL: no continuity term) are device memory, copied by the call into handle-owned padded
+ * buffers; lam, beta, lo, hi (D) and rho (n_rho) are HOST arrays, checked and copied by the call.  One captured graph per (B bucket,
+ * steps, sampler, noise mode, range, anchor or not); a graph bakes no value of the guide.  The free loops keep their graphs and launches.
+ * ldp_agent_sample_guided: ldp_agent_sample whose planner loop is the guided loop over (0, planner_steps).
+ * LDP_EINVAL, naming the argument: sampler 2 (not built), a NULL array, n_rho != n_steps, a negative or non-finite lam / beta / rho
+ * entry, lo[c] > hi[c], ldx or ldg below D.  A guide together with a constraint or a warm start is not built. */
+LDP_API int ldp_plan_guide_step(ldp_handle* h, const float* x, const float* eps, const float* noise, const float* target, const float* wg,
+                                const float* anchor, const float* lam, const float* beta, const float* lo, const float* hi,
+                                const float* rho, int32_t sampler, int32_t n_steps, int32_t step, uint64_t seed, int64_t row_offset,
+                                float* x_out, int32_t ldx, int32_t ldg, int32_t B, void* stream);
+LDP_API int ldp_plan_guide_cost(ldp_handle* h, const float* x, const float* target, const float* wg, const float* anchor, const float* lam,
+                                const float* beta, const float* lo, const float* hi, int64_t rows, int32_t n_per, float* out, void* stream);
+LDP_API int ldp_plan_sample_guided(ldp_handle* h, const float* cond, const float* x_init, const float* step_noise, const float* target,
+                                   const float* wg, const float* anchor, const float* lam, const float* beta, const float* lo,
+                                   const float* hi, const float* rho, int32_t n_rho, uint64_t seed, int64_t row_offset, int32_t sampler,
+                                   int32_t n_steps, int32_t step_begin, int32_t step_end, float* out, int32_t B, int32_t use_graph,
+                                   void* stream);
+LDP_API int ldp_agent_sample_guided(ldp_handle* h, const float* obs_emb, int32_t obs_frames, int32_t obs_horizon, const float* x_init,
+                                    const float* x_noise, const float* a_init, const float* a_noise, const float* target, const float* wg,
+                                    const float* anchor, const float* lam, const float* beta, const float* lo, const float* hi,
+                                    const float* rho, int32_t n_rho, uint64_t seed, int64_t row_offset, int32_t sampler,
+                                    int32_t planner_steps, int32_t idm_steps, float* x_out, float* plan_out, float* action_out,
+                                    const float* act_lo, const float* act_hi, int32_t act_dim, int32_t act_mode, int32_t B,
+                                    int32_t use_graph, void* stream);
+
 /* -- StableVAE ----------------------------------------------------------------------------
  * FlaxAutoencoderKL.encode(x).latent_dist.mean   (call site agent/ldp_agent.py:55-60)
  * img (N, S, S, 3) NHWC already normalised to [-1,1] -> mean (N, S/32, S/32, latent_channels)

@@ -99,6 +99,15 @@ SIGNATURES: Dict[str, tuple] = {
                                                C.c_int32, C.c_void_p]),
     "ldp_solver_timesteps": (C.c_int, [_H, C.c_void_p, C.c_int32]),
     "ldp_plan_solver_step": (C.c_int, [_H, _FP, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP, C.c_int32, C.c_void_p]),
+    "ldp_plan_guide_step": (C.c_int, [_H, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
+                                      C.c_int64, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ldp_plan_guide_cost": (C.c_int, [_H, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, C.c_int64, C.c_int32, _FP, C.c_void_p]),
+    "ldp_plan_sample_guided": (C.c_int, [_H, _FP, _FP, _FP, _FP, _FP, _FP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, C.c_int32,
+                                         C.c_int32, C.c_void_p]),
+    "ldp_agent_sample_guided": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP,
+                                          _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ldp_plan_candidates": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_uint64, C.c_int32,
                                       C.c_int32, _FP, C.c_int32, C.c_void_p]),
     "ldp_plan_cost_density": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _FP, C.c_void_p]),

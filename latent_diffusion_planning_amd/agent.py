@@ -986,6 +986,88 @@ class LDPAgent(_EngineCalls):
         metrics["plan_viz"] = viz
         return action, metrics
 
+    # ---- guided planning (defined by this repository: DESIGN.md 4.19; csrc/guide.hip, guide.py) --------------------------------
+    def build_guide(self, B, **kw):
+        """guide.build_guide for this agent's config, bound to its engine: the result is sample_guided's `guide=` and, being a cost
+        function on candidates, sample_best_of's `score=`."""
+        from .guide import build_guide
+        if not self.use_planner:
+            raise NotImplementedError("a guide needs the planner (use_planner)")
+        if isinstance(kw.get("goal"), Mapping):
+            kw["goal"] = self._goal_embedding(kw["goal"], int(B))
+        return build_guide(self.config, B, engine=self._engine, **kw)
+
+    def sample_guided(self, batch, eval_rng, guide=None, target=None, weight=None, goal=None, t_goal=None, goal_dims=None, goal_weight=None,
+                      smooth=None, anchor=None, lo=None, hi=None, bound_weight=None, scale=None, schedule="sigma2", sampler="ddim",
+                      n_steps=None, idm_steps=None, noise=None, row_offset=0, decode=False):
+        """sample() with the plan moved down the gradient of a cost inside every denoising step -> (action, metrics): metrics is
+        sample_constrained()'s ('plan', 'x', lazy 'plan_viz', 'plan_mse' for a training batch) plus 'guide_cost' (B,), the cost J of the
+        final planner state.  The cost is a guide.Guide -- `guide=`, or built here from guide.build_guide's arguments: soft goals and
+        waypoints (target / weight, goal / t_goal / goal_dims / goal_weight, goal as embeddings (B, D) or an observation dict),
+        smoothness (smooth, anchor=True: continuity with the batch's own last observation embedding, the state that precedes x[:, 0] in
+        'plan') and box bounds (lo, hi, bound_weight).  scale / schedule: the step sizes (guide.Guide.step_sizes); a step size beyond the
+        descent bound is a ValueError before the planner loop is enqueued.  The planner loop has one launch more per step than sample()'s; the IDM
+        loop, the plan assembly and the un-normalisation are sample()'s.  noise: optional dict(x_init, x_noise, a_init, a_noise) as in
+        sample_viz.  Not built (NotImplementedError): sampler="dpmpp".  The control quality of guided plans has not been evaluated."""
+        from .guide import Guide, build_guide
+        if sampler == "dpmpp":
+            raise NotImplementedError('guidance under sampler="dpmpp" is not built: the guided step is the DDPM / DDIM scheduler step')
+        if not (self.use_planner and self.use_idm):
+            raise NotImplementedError("sample_guided() needs both the planner and the IDM (use_planner / use_idm)")
+        built = dict(target=target, weight=weight, goal=goal, t_goal=t_goal, goal_dims=goal_dims, goal_weight=goal_weight, smooth=smooth,
+                     anchor=anchor, lo=lo, hi=hi, bound_weight=bound_weight, scale=scale)
+        if guide is not None:
+            given = [k for k, v in built.items() if v is not None] + ([] if schedule == "sigma2" else ["schedule"])
+            if given:
+                raise ValueError(f"guide= already holds the cost and its step sizes: {', '.join(given)} cannot be given with it")
+            if not isinstance(guide, Guide):
+                raise ValueError(f"guide must be a guide.Guide (guide.build_guide / LDPAgent.build_guide), got {type(guide).__name__}")
+        seed = _seed_of(eval_rng)
+        cfg = self.config
+        oh = cfg["obs_horizon"]
+        ns = int(cfg["planner_n_diffusion_steps"] if n_steps is None else n_steps)
+        if idm_steps is None and n_steps is not None and sampler != "ddpm":
+            idm_steps = n_steps                                # one schedule for both loops unless told otherwise
+        nz = dict(noise or {})
+        rho = None if guide is None else guide.step_sizes(ns, sampler)      # (a given guide: every host check before any GPU work)
+
+        def run():
+            self._sync_weights()
+            obs_emb = self.get_obs_cond(self._vae_encode_t(self._postprocess(batch)["obs"])).contiguous()
+            B = obs_emb.shape[0]
+            gd, rh = guide, rho
+            if gd is None:
+                g = None if goal is None else self._goal_embedding(goal, B)
+                gd = build_guide(cfg, B, **dict(built, target=None if target is None else self._t(target), goal=g,
+                                                anchor=anchor if anchor is None or anchor is True else self._t(anchor)),
+                                 schedule=schedule, engine=self._engine)
+                rh = gd.step_sizes(ns, sampler)
+            if gd.B != B:
+                raise ValueError(f"the guide was built for B = {gd.B} plans, the batch holds {B}")
+            if gd.anchor is True:                              # this batch's own current observation: a copy of the guide, not the caller's
+                gd = Guide(gd.cfg, gd.B, gd.target, gd.weight, obs_emb[:, oh - 1].contiguous(), gd.lam, gd.beta, gd.lo, gd.hi, gd.scale,
+                           gd.schedule, self._engine, gd.wmax)
+            lo_a, hi_a, amode = self._action_bounds()
+            x, plan, action = self._engine.agent_sample_guided(
+                obs_emb, oh, gd, rh, x_init=nz.get("x_init"), x_noise=nz.get("x_noise"), a_init=nz.get("a_init"), a_noise=nz.get("a_noise"),
+                seed=seed, row_offset=row_offset, sampler=sampler, planner_steps=n_steps, idm_steps=idm_steps, action_bounds=(lo_a, hi_a),
+                action_mode=amode)
+            out = [action, plan, x, self._engine.plan_guide_cost(x, gd)]
+            if obs_emb.shape[1] > oh:                          # from a training batch, not inference (:447-448)
+                out.append(self._engine.mean_sq_diff(x, obs_emb[:, oh:]))
+            return out
+        res, rec = self._call(run, lambda: run() + [None])             # plan_viz re-decodes itself from the new plan
+        action, plan, x, cost = (DeviceArray(t, record=rec) for t in res[:4])
+        metrics = {"plan": plan, "x": x, "guide_cost": cost}
+        if len(res) > 4:
+            metrics["plan_mse"] = DeviceArray(res[4], record=rec)
+        S = self._engine.image_size
+        viz = DeviceArray(thunk=lambda: self._vae_decode_t(plan.tensor), shape=tuple(plan.shape[:2]) + (3, S, S), record=rec)
+        if decode:
+            viz.tensor
+        metrics["plan_viz"] = viz
+        return action, metrics
+
     # ---- best-of-N planning (defined by this repository: DESIGN.md 4.14; csrc/select.hip) ----------------------------------
     def _goal_embedding(self, goal, B):
         """`goal`: normalised embeddings (B, D), or an observation dict in batch['obs'] form (embedded like the batch, frame 0)."""

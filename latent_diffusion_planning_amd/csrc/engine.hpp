@@ -60,6 +60,8 @@ struct PlannerState {
   DevBuf state, cond, film_g, bufA, bufB, bufC, bufR, noise, xchg, kw_slab;
   DevBuf solver_eps, solver_x0;   // sampler 2 (solver.hip): the evaluation's eps (B, T, D) unpadded, and the previous step's clipped x0 padded like `state`
   DevBuf ctarget, cmask;          // constrained planning (constrain.hip): the call's target (float) and mask (uint8) padded like `state`, zero beyond D and the real rows
+  DevBuf gtarget, gwg, ganchor;   // guided planning (guide.hip): the call's target and weights (B, T, DP) and anchor (B, DP), padded like `state`
+  DevBuf gcol;                    // ... and its host vectors: [lam | beta | lo | hi] at 128 floats each, then the step sizes rho[n_steps]
   size_t xchg_stride = 0;         // granules per conv launch
   uint64_t calls = 0;             // planner calls on this handle (slab hygiene, see planner_prepare)
   std::vector<DevBuf> skip;
@@ -85,6 +87,7 @@ struct GraphKey {
   int n_steps2 = 0, noise_mode2 = 0;              // joint graph: the IDM loop's step count / noise mode
   int begin = 0, end = -1;                        // planner loops (kind 0, 2): the executed steps [begin, end) of n_steps; (0, -1) = no planner range (the IDM loop, kind 1)
   int constrain = 0;                              // planner loops: 0 = the free loop, else the LDP_CONSTRAIN_* mode whose launches the graph carries (constrain.hip)
+  int guide = 0;                                  // planner loops: 0 = no guide, else LDP_GUIDE_ON / LDP_GUIDE_ANCHOR: the guided loop's launches (guide.hip)
   bool operator<(const GraphKey& o) const {
     if (kind != o.kind) return kind < o.kind;
     if (B != o.B) return B < o.B;
@@ -95,7 +98,8 @@ struct GraphKey {
     if (noise_mode2 != o.noise_mode2) return noise_mode2 < o.noise_mode2;
     if (begin != o.begin) return begin < o.begin;
     if (end != o.end) return end < o.end;
-    return constrain < o.constrain;
+    if (constrain != o.constrain) return constrain < o.constrain;
+    return guide < o.guide;
   }
 };
 
@@ -279,7 +283,10 @@ inline int bucket_rows(int B, bool explicit_noise) { return explicit_noise ? B :
 // it (LDP_EINVAL), so a planner caller that forgets the two fields fails loudly instead of running zero steps.
 // constrain: 0, or the LDP_CONSTRAIN_* mode of a constrained loop (constrain.hip): C_begin in front of the first step and C_{i+1} behind
 // step i, on the target / mask staged into P.ctarget / P.cmask.
-struct LoopSpec { int n_steps = 0, sampler = 0; bool explicit_noise = false; int begin = 0, end = -1; int constrain = 0; };
+// guide: 0, or LDP_GUIDE_ON / LDP_GUIDE_ANCHOR for a guided loop (guide.hip): the U-Net writes eps only and the guided step behind it
+// updates the state, on the guide staged into P.gtarget / P.gwg / P.ganchor / P.gcol (ANCHOR: with the continuity term).
+struct LoopSpec { int n_steps = 0, sampler = 0; bool explicit_noise = false; int begin = 0, end = -1; int constrain = 0; int guide = 0; };
+constexpr int LDP_GUIDE_ON = 1, LDP_GUIDE_ANCHOR = 2;
 int check_step_range(int begin, int end, int n_steps, const char* what);
 struct WarmSpec;                                 // a warm start of the planner state (below)
 // solver_h: the handle whose registered tables may serve LDP_SAMPLER_DPMPP (LDP_ESTATE when it has none for n_steps); nullptr where that
@@ -352,4 +359,19 @@ int plan_solver_launch(const float* x, const float* eps, const float* x0_prev, f
 int solver_workspace(ldp_handle* h, int Bg);
 // the update of step i on the loop state, eps read from P.solver_eps, history in P.solver_x0: one launch, counted in last_total_launches
 int planner_solver_step(ldp_handle* h, int Bg, const SolverTable& tab, int i, bool second, hipStream_t q);
+// ---- guided planning (guide.hip) ----------------------------------------------------------------------------
+// A call's guide as the sampling entry points receive it: target, wg (B, T, D) and anchor (B, D; nullptr: no continuity term) in device
+// memory, lam, beta, lo, hi (D) and rho (n_rho) on the host.
+struct GuideSpec {
+  const float* target; const float* wg; const float* anchor;
+  const float* lam; const float* beta; const float* lo; const float* hi;
+  const float* rho; int n_rho;
+};
+// LDP_EINVAL naming the argument: sampler 2, a missing array, n_rho != n_steps, a negative or non-finite lam / beta / rho, lo > hi
+int check_guide(const GuideSpec* g, int D, int n_steps, int sampler);
+// the guide into the handle's buffers, padded like the loop state (eager: pad launches and one host copy; the buffers grow with the
+// workspace and drop the captured graphs when they move)
+int guide_stage(ldp_handle* h, const GuideSpec& g, int B, int Bg, hipStream_t st);
+// the guided step i on the loop state, eps read from P.solver_eps, explicit noise (B, T, D) or nullptr: one launch, counted
+int planner_guide_step(ldp_handle* h, int Bg, const LoopSpec& L, const StepCoef& k, const float* noise, int i, hipStream_t q);
 }  // namespace ldp

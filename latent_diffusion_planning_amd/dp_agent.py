@@ -282,6 +282,12 @@ class DPAgent(_EngineCalls):
     def replanner(self, *a, **k):
         raise NotImplementedError("replanner is built for LDPAgent only (a DP agent denoises actions, which do not shift with the world like a latent plan)")
 
+    def sample_guided(self, *a, **k):
+        raise NotImplementedError("sample_guided is built for LDPAgent only (its costs are stated on latent plans; a DP agent denoises actions)")
+
+    def build_guide(self, *a, **k):
+        raise NotImplementedError("build_guide is built for LDPAgent only (its costs are stated on latent plans; a DP agent denoises actions)")
+
     def sample_action_from_plan(self, *a, **k):
         raise NotImplementedError("DPAgent has no sample_action_from_plan")
 

@@ -176,6 +176,12 @@ class DPVAEAgent(LDPAgent):
     def sample_best_of(self, *a, **k):
         raise NotImplementedError("sample_best_of is built for LDPAgent only (it scores latent plans; a DP agent samples actions)")
 
+    def sample_guided(self, *a, **k):
+        raise NotImplementedError("sample_guided is built for LDPAgent only (its costs are stated on latent plans; a DP agent denoises actions)")
+
+    def build_guide(self, *a, **k):
+        raise NotImplementedError("build_guide is built for LDPAgent only (its costs are stated on latent plans; a DP agent denoises actions)")
+
     def update_mixed(self, *a, **k):
         raise NotImplementedError("DPVAEAgent has no update_mixed")
 

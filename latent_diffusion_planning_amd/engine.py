@@ -546,6 +546,137 @@ class HipEngine:
         self.call_seq += 1
         return x, plan, act
 
+    # -- guided planning (csrc/guide.hip) --------------------------------------------------------------
+    def _guide(self, guide, B: int, ld: Optional[int] = None):
+        """A guide (guide.Guide, or anything with its fields) for the C ABI: target, weight (B, T, D) and anchor (B, D) or None as device
+        tensors -- (B, T, ld) / (B, ld) when a padded stride is asked for -- and lam, beta, lo, hi (D,) as host float32 arrays."""
+        if getattr(guide, "anchor", None) is True:
+            raise ValueError("anchor=True is resolved by LDPAgent.sample_guided (the batch's last observation embedding): give the "
+                             "embeddings (B, D) here")
+        tg, wg = _f32(guide.target, self.device), _f32(guide.weight, self.device)
+        an = None if guide.anchor is None else _f32(guide.anchor, self.device)
+        _want("target", tg, (B, self.T, self.D))
+        _want("weight", wg, (B, self.T, self.D))
+        _want("anchor", an, (B, self.D))
+        if ld is not None and ld != self.D:
+            pad = lambda t: torch.nn.functional.pad(t, (0, ld - self.D)).contiguous()
+            tg, wg, an = pad(tg), pad(wg), None if an is None else pad(an)
+        cols = []
+        for name in ("lam", "beta", "lo", "hi"):
+            a = np.ascontiguousarray(np.asarray(getattr(guide, name), dtype=np.float32))
+            if a.shape != (self.D,):
+                raise ValueError(f"{name} must have shape {(self.D,)}, got {a.shape}")
+            cols.append(a)
+        return tg, wg, an, cols
+
+    @staticmethod
+    def _host_ptr(a: np.ndarray):
+        return a.ctypes.data_as(C.c_void_p)
+
+    def plan_guide_step(self, x: torch.Tensor, eps: torch.Tensor, guide, rho, step: int, *, noise=None, seed: int = 0, row_offset: int = 0,
+                        sampler: str = "ddim", n_steps: Optional[int] = None, ldg: Optional[int] = None, inplace: bool = False) -> torch.Tensor:
+        """One guided step (one launch): x (B, T, ldx) with ldx >= D (a padded state: the columns beyond D keep their bits), eps (B, T, D),
+        rho (n_steps,) step sizes of which entry `step` is used, noise (B, T, D) or None (the Philox draw of (seed, row_offset)) -> the
+        new x.  ldg: the row stride the guide's target / weight / anchor are handed over with (default D).  inplace: x is overwritten."""
+        xt = x if inplace else _f32(x, self.device).clone()
+        if not (torch.is_tensor(xt) and xt.is_cuda and xt.dtype == torch.float32 and xt.is_contiguous()):
+            raise ValueError("inplace: x must be a contiguous float32 device tensor")
+        B, ldx = int(xt.shape[0]), int(xt.shape[-1])
+        if xt.dim() != 3 or xt.shape[1] != self.T or ldx < self.D:
+            raise ValueError(f"x must have shape {(B, self.T, self.D)} (or a wider last axis), got {tuple(xt.shape)}")
+        ep = _f32(eps, self.device)
+        nz = None if noise is None else _f32(noise, self.device)
+        _want("eps", ep, (B, self.T, self.D))
+        _want("noise", nz, (B, self.T, self.D))
+        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
+        ldg = self.D if ldg is None else int(ldg)
+        tg, wg, an, cols = self._guide(guide, B, ldg)
+        dev = [torch.as_tensor(a).to(self.device) for a in cols]
+        rh = _f32(np.asarray(rho, dtype=np.float32).reshape(-1), self.device)
+        _want("rho", rh, (n_steps,))
+        check(self.lib.ldp_plan_guide_step(self._h, _ptr(xt), _ptr(ep), _ptr(nz), _ptr(tg), _ptr(wg), _ptr(an), _ptr(dev[0]), _ptr(dev[1]),
+                                           _ptr(dev[2]), _ptr(dev[3]), _ptr(rh), _SAMPLERS[sampler], n_steps, int(step),
+                                           C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _ptr(xt), ldx, ldg, B, self._stream()))
+        return xt
+
+    def plan_guide_cost(self, x: torch.Tensor, guide, n_per: int = 1) -> torch.Tensor:
+        """J of every row of x (rows, T, D) under row r // n_per of the guide (rows = B * n_per) -> (rows,) device costs, one launch."""
+        xt = _f32(x, self.device)
+        rows, n_per = int(xt.shape[0]), int(n_per)
+        if n_per < 1 or rows < 1 or rows % n_per:
+            raise ValueError(f"x must hold a positive multiple of n_per = {n_per} rows, got {rows}")
+        _want("x", xt, (rows, self.T, self.D))
+        tg, wg, an, cols = self._guide(guide, rows // n_per)
+        dev = [torch.as_tensor(a).to(self.device) for a in cols]
+        out = torch.empty((rows,), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_plan_guide_cost(self._h, _ptr(xt), _ptr(tg), _ptr(wg), _ptr(an), _ptr(dev[0]), _ptr(dev[1]), _ptr(dev[2]),
+                                           _ptr(dev[3]), C.c_int64(rows), n_per, _ptr(out), self._stream()))
+        return out
+
+    def plan_sample_guided(self, cond: Optional[torch.Tensor], guide, rho, *, step_begin: int = 0, step_end: Optional[int] = None,
+                           B: Optional[int] = None, x_init: Optional[torch.Tensor] = None, step_noise: Optional[torch.Tensor] = None,
+                           seed: int = 0, row_offset: int = 0, sampler: str = "ddim", n_steps: Optional[int] = None,
+                           use_graph: bool = True) -> torch.Tensor:
+        """plan_sample_range with the guided loop: per executed step the U-Net's eps, then one guided step with the step size rho[i]
+        (default range: the whole loop).  rho: n_steps step sizes (the library checks the count)."""
+        cond_t = None if cond is None else _f32(cond, self.device)
+        if B is None:
+            B = cond_t.shape[0] if cond_t is not None else x_init.shape[0]
+        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
+        step_end = n_steps if step_end is None else int(step_end)
+        xi = None if x_init is None else _f32(x_init, self.device)
+        nz = None if step_noise is None else _f32(step_noise, self.device)
+        _want("cond", cond_t, (B, self.G))
+        _want("x_init", xi, (B, self.T, self.D))
+        _want("step_noise", nz, (n_steps, B, self.T, self.D))
+        tg, wg, an, cols = self._guide(guide, B)
+        rh = np.ascontiguousarray(np.asarray(rho, dtype=np.float32).reshape(-1))
+        out = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_plan_sample_guided(self._h, _ptr(cond_t), _ptr(xi), _ptr(nz), _ptr(tg), _ptr(wg), _ptr(an),
+                                              *(self._host_ptr(a) for a in cols), self._host_ptr(rh), int(rh.size),
+                                              C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _SAMPLERS[sampler], n_steps,
+                                              int(step_begin), step_end, _ptr(out), B, 1 if use_graph else 0, self._stream()))
+        self.call_seq += 1
+        return out
+
+    def agent_sample_guided(self, obs_emb: torch.Tensor, obs_horizon: int, guide, rho, *, x_init=None, x_noise=None, a_init=None,
+                            a_noise=None, seed: int = 0, row_offset: int = 0, sampler: str = "ddim", planner_steps: Optional[int] = None,
+                            idm_steps: Optional[int] = None, action_bounds=None, action_mode: int = 0, use_graph: bool = True):
+        """agent_sample whose planner loop is the guided one -> (x, plan, action) as agent_sample."""
+        ob = _f32(obs_emb, self.device)
+        B, H = ob.shape[0], ob.shape[1]
+        _want("obs_emb", ob, (B, H, self.D))
+        tg, wg, an, cols = self._guide(guide, B)
+        rh = np.ascontiguousarray(np.asarray(rho, dtype=np.float32).reshape(-1))
+        ps = self.planner_train_steps if planner_steps is None else int(planner_steps)
+        is_ = self.idm_train_steps if idm_steps is None else int(idm_steps)
+        R = B * self.ah
+        xi = None if x_init is None else _f32(x_init, self.device)
+        xn = None if x_noise is None else _f32(x_noise, self.device)
+        ai = None if a_init is None else _f32(a_init, self.device)
+        an_ = None if a_noise is None else _f32(a_noise, self.device)
+        _want("x_init", xi, (B, self.T, self.D))
+        _want("x_noise", xn, (ps, B, self.T, self.D))
+        _want("a_init", ai, (R, self.A))
+        _want("a_noise", an_, (is_, R, self.A))
+        lo = hi = None
+        adim = 0
+        if action_bounds is not None:
+            lo, hi = self._bounds(*action_bounds)
+            adim = lo.numel()
+            if adim not in (1, self.A) or hi.numel() != adim:
+                raise ValueError(f"action bounds must have length 1 or {self.A}")
+        x = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
+        plan = torch.empty((B, self.ah + 1, self.D), device=self.device, dtype=torch.float32)
+        act = torch.empty((B, self.ah, self.A), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_agent_sample_guided(self._h, _ptr(ob), H, int(obs_horizon), _ptr(xi), _ptr(xn), _ptr(ai), _ptr(an_), _ptr(tg),
+                                               _ptr(wg), _ptr(an), *(self._host_ptr(a) for a in cols), self._host_ptr(rh), int(rh.size),
+                                               C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _SAMPLERS[sampler], ps, is_,
+                                               _ptr(x), _ptr(plan), _ptr(act), _ptr(lo), _ptr(hi), adim, int(action_mode), B,
+                                               1 if use_graph else 0, self._stream()))
+        self.call_seq += 1
+        return x, plan, act
+
     # -- best-of-N planning (csrc/select.hip, DESIGN.md 4.14): candidate-major rows r = c * B + b ---------------------
     def plan_candidates(self, obs_emb: torch.Tensor, obs_horizon: int, n_candidates: int, *, c0: int = 0, n_loc: Optional[int] = None,
                         x_init=None, step_noise=None, seed: int = 0, sampler: str = "ddpm", n_steps: Optional[int] = None,

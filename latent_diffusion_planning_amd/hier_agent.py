@@ -149,6 +149,12 @@ class LDPHierAgent(LDPAgent):
     def sample_best_of(self, *a, **k):
         raise NotImplementedError("sample_best_of is built for LDPAgent only (the hierarchical plan has a stride and a U-Net IDM)")
 
+    def sample_guided(self, *a, **k):
+        raise NotImplementedError("sample_guided is built for LDPAgent only (the hierarchical plan has a stride and a U-Net IDM)")
+
+    def build_guide(self, *a, **k):
+        raise NotImplementedError("build_guide is built for LDPAgent only (the hierarchical plan has a stride and a U-Net IDM)")
+
     # ---- agent/ldp_hier_agent.py:385-461 -----------------------------------------------------------
     def sample(self, batch, eval_rng, **kw):
         kw.setdefault("decode", False)
