@@ -440,6 +440,65 @@ LDP_API int ldp_agent_sample_guided(ldp_handle* h, const float* obs_emb, int32_t
                                     const float* act_lo, const float* act_hi, int32_t act_dim, int32_t act_mode, int32_t B,
                                     int32_t use_graph, void* stream);
 
+/* -- composed planning (defined by this repo; the reference has nothing of the kind) ----------------------------
+ * A warm start, a constraint and a guide in ONE planner call, under any of the three samplers.  The calls above keep their refusals;
+ * these take the optional parts in one struct.  A part is absent when its device arrays are NULL.
+ *   warm start   x_store (n_slots, T, D), slot (B; host or device; NULL: rows 0 .. B-1), n_slots, shift      (ldp_agent_resample's)
+ *   constraint   target (B, T, D) float32, mask (B, T, D) uint8, mode LDP_CONSTRAIN_*                        (ldp_plan_sample_constrained's)
+ *   guide        g_target, g_wg (B, T, D), g_anchor (B, D) or NULL, lam, beta, lo, hi (D), rho (n_rho = n_steps)   (ldp_plan_sample_guided's)
+ * The composed step i of n, ONE launch (csrc/compose.hip plan_compose_step_kernel), is the existing operations in sequence, every
+ * operation rounded to fp32 once:
+ *   1  y  = clip((x - s_i eps) / a_i, -1, 1)             the data prediction; (a_i, s_i) of the scheduler's row i (DDPM / DDIM) or of the
+ *                                                        registered timestep table (sampler 2)
+ *   2  y' = clip(y - rho[i] g(y), -1, 1)                 with a guide (g: ldp_plan_guide_step's gradient), else y' = y
+ *   3  DDPM / DDIM:  x' = c_x0 y' + c_x x + c_eps eps + sigma z                      (z: the step noise of ldp_plan_sample)
+ *      sampler 2:    Dv = second ? y' + w (y' - x0_prev) : y';  x' = c_x x + c_D Dv;  x0_out = y'
+ *                    -- the history holds the GUIDED data prediction (the denoiser the loop actually follows)
+ *   4  where mask != 0:  x' = C_{i+1}: target, or under LDP_CONSTRAIN_REPAINT below level n  a_{i+1} target + s_{i+1} z_c  with
+ *      ldp_plan_constrain's draw z_c at level i + 1.  A select, never a blend; the history is not overwritten.
+ * Constraint levels under sampler 2: level j < n has (sqrt(abar_ts[j]), sqrt(1 - abar_ts[j])) of the registered table (float64 from the
+ * float32 abar table, cast once), level n exactly (1, 0).  The constraint is NOT imposed on y in front of the guide (the smoothness
+ * stencil does not see the pinned goal): a possible follow-up.
+ *
+ * ldp_plan_compose_step: that step on caller memory.  EVERY pointer of `parts` is device memory here (as in ldp_plan_guide_step: lam,
+ * beta, lo, hi, rho too), and its warm-start fields are not read.  x, x_out, x0_prev, x0_out (B, T, ldx) with ldx >= D (x_out may be x,
+ * x0_out may be x0_prev; columns beyond D are neither read nor written), eps and noise (B, T, D; noise NULL: the Philox draw of (seed,
+ * row_offset)), the guide's arrays with row stride ldg, the constraint's target and mask with row stride ldc.  Under sampler 2 x0_out is
+ * required and the step is second order iff second != 0 (then x0_prev is required) and step < n_steps-1; under DDPM / DDIM second,
+ * x0_prev and x0_out are ignored.
+ *
+ * ldp_plan_sample_composed: ldp_plan_sample_range with the parts.  In these two calls lam, beta, lo, hi, rho are HOST arrays (as in
+ * ldp_plan_sample_guided); a warm start is read from x_store (not written back) and noised to the level of step_begin.  Where a guide
+ * meets a constraint, or either meets sampler 2, the loop is the composed one: C_begin once in front, then per executed step the U-Net
+ * writing eps only and one composed launch -- (end - begin) launches more than the free DDIM loop, plus 1 with a constraint.  Every
+ * other combination runs the loop the dedicated call runs (bit-identical to it).  One captured graph per (B bucket, steps, sampler, noise
+ * mode, range, mode, anchor or not, composed or not); a graph bakes nothing of a guide, a constraint or a seed.  Under DDPM / DDIM step
+ * ranges compose bit for bit; UNDER SAMPLER 2 THE HISTORY STARTS EMPTY WITH EVERY CALL, so ranges do not compose there.
+ * ldp_agent_sample_composed: ldp_agent_sample (no warm start: step_begin must be 0) / ldp_agent_resample (warm start: the planner loop
+ * is [step_begin, planner_steps) and the new planner state is written back to the same rows of x_store) with the parts; the IDM loop,
+ * the plan assembly and the action un-normalisation are theirs.
+ * LDP_EINVAL, naming the argument: whatever the dedicated calls refuse for their part (a negative or non-finite lam / beta / rho entry,
+ * lo[c] > hi[c], n_rho != n_steps, a bad mode, a NULL array of a part that is present, a host slot outside the table, x_init together
+ * with a warm start); LDP_ESTATE under sampler 2 without a registered table for n_steps. */
+typedef struct ldp_plan_compose {
+  float* x_store; const int32_t* slot; int32_t n_slots, shift;                                        /* warm start */
+  const float* target; const uint8_t* mask; int32_t mode;                                             /* constraint */
+  const float* g_target; const float* g_wg; const float* g_anchor;                                    /* guide */
+  const float* lam; const float* beta; const float* lo; const float* hi; const float* rho; int32_t n_rho;
+} ldp_plan_compose;
+LDP_API int ldp_plan_compose_step(ldp_handle* h, const float* x, const float* eps, const float* noise, const float* x0_prev,
+                                  const ldp_plan_compose* parts, int32_t sampler, int32_t n_steps, int32_t step, int32_t second,
+                                  uint64_t seed, int64_t row_offset, float* x_out, float* x0_out, int32_t ldx, int32_t ldg, int32_t ldc,
+                                  int32_t B, void* stream);
+LDP_API int ldp_plan_sample_composed(ldp_handle* h, const float* cond, const float* x_init, const float* step_noise,
+                                     const ldp_plan_compose* parts, uint64_t seed, int64_t row_offset, int32_t sampler, int32_t n_steps,
+                                     int32_t step_begin, int32_t step_end, float* out, int32_t B, int32_t use_graph, void* stream);
+LDP_API int ldp_agent_sample_composed(ldp_handle* h, const float* obs_emb, int32_t obs_frames, int32_t obs_horizon, const float* x_init,
+                                      const float* x_noise, const float* a_init, const float* a_noise, const ldp_plan_compose* parts,
+                                      int32_t step_begin, uint64_t seed, int64_t row_offset, int32_t sampler, int32_t planner_steps,
+                                      int32_t idm_steps, float* x_out, float* plan_out, float* action_out, const float* act_lo,
+                                      const float* act_hi, int32_t act_dim, int32_t act_mode, int32_t B, int32_t use_graph, void* stream);
+
 /* -- StableVAE ----------------------------------------------------------------------------
  * FlaxAutoencoderKL.encode(x).latent_dist.mean   (call site agent/ldp_agent.py:55-60)
  * img (N, S, S, 3) NHWC already normalised to [-1,1] -> mean (N, S/32, S/32, latent_channels)

@@ -67,6 +67,13 @@ class LdpDataKey(C.Structure):                 # ldp_data_key: one key of ldp_da
     _fields_ = [("table", C.c_void_p), ("out", C.c_void_p), ("row_bytes", C.c_int64), ("first_row", C.c_int32), ("n_rows", C.c_int32)]
 
 
+class LdpPlanCompose(C.Structure):             # ldp_plan_compose: the optional parts of a composed planner call (NULL = absent)
+    _fields_ = [("x_store", C.c_void_p), ("slot", C.c_void_p), ("n_slots", C.c_int32), ("shift", C.c_int32),
+                ("target", C.c_void_p), ("mask", C.c_void_p), ("mode", C.c_int32),
+                ("g_target", C.c_void_p), ("g_wg", C.c_void_p), ("g_anchor", C.c_void_p),
+                ("lam", C.c_void_p), ("beta", C.c_void_p), ("lo", C.c_void_p), ("hi", C.c_void_p), ("rho", C.c_void_p), ("n_rho", C.c_int32)]
+
+
 _FP = C.c_void_p       # device float*/int* passed as integers from tensor.data_ptr()
 _H = C.c_void_p        # ldp_handle*
 
@@ -108,6 +115,13 @@ SIGNATURES: Dict[str, tuple] = {
     "ldp_agent_sample_guided": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP,
                                           _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ldp_plan_compose_step": (C.c_int, [_H, _FP, _FP, _FP, _FP, C.POINTER(LdpPlanCompose), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
+                                        C.c_int64, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ldp_plan_sample_composed": (C.c_int, [_H, _FP, _FP, _FP, C.POINTER(LdpPlanCompose), C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, _FP, C.c_int32, C.c_int32, C.c_void_p]),
+    "ldp_agent_sample_composed": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, C.POINTER(LdpPlanCompose), C.c_int32, C.c_uint64,
+                                            C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_int32, C.c_void_p]),
     "ldp_plan_candidates": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_uint64, C.c_int32,
                                       C.c_int32, _FP, C.c_int32, C.c_void_p]),
     "ldp_plan_cost_density": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _FP, C.c_void_p]),

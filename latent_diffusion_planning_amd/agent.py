@@ -1068,6 +1068,129 @@ class LDPAgent(_EngineCalls):
         metrics["plan_viz"] = viz
         return action, metrics
 
+    # ---- composed planning (defined by this repository: DESIGN.md 4.20; csrc/compose.hip) -----------------------------------
+    def _guide_step_sizes(self, guide, sampler, n_steps):
+        """The step sizes of `guide` for a loop of n_steps under `sampler`: Guide.step_sizes on the uniform grid, Guide.step_sizes_on at
+        the entries of the timestep table under "dpmpp" (the table the engine holds for n_steps, else the log-SNR grid it would
+        register).  The descent-bound refusal is theirs."""
+        if sampler != "dpmpp":
+            return guide.step_sizes(n_steps, sampler)
+        from .schedule import solver_timesteps
+        ts = self._engine.solver_tables.get(int(n_steps))
+        if ts is None:
+            ts = solver_timesteps(int(self.config["planner_n_diffusion_steps"]), int(n_steps), "logsnr")
+        return guide.step_sizes_on(ts)
+
+    def plan(self, batch, eval_rng, *, guide=None, target=None, mask=None, goal=None, t_goal=None, goal_dims=None, mode="repaint",
+             prev=None, warm_steps=None, shift=None, sampler="ddim", n_steps=None, idm_steps=None, timesteps=None, noise=None,
+             row_offset=0, decode=False):
+        """sample() with any of a warm start, a constraint and a guide in ONE planner loop, under any sampler -> (action, metrics):
+        metrics holds 'plan', 'x' (the full planner state (B, T, D): the `prev` of the next call), a lazy 'plan_viz', 'guide_cost' (B,)
+        when guided, and 'plan_mse' for a training batch.
+        guide: a guide.Guide (LDPAgent.build_guide).  target / mask / goal / t_goal / goal_dims / mode: sample_constrained's constraint.
+        prev / warm_steps / shift: sample_warm's warm start.  sampler "dpmpp" runs over the timestep table `timesteps` (sample_viz); the
+        guide's "sigma2" step sizes and the constraint's noise levels are then taken at the entries of that table.
+        Where a guide meets a constraint, or either meets "dpmpp", every denoising step is the U-Net evaluation plus one composed launch
+        (csrc/compose.hip): data prediction, guide, scheduler or solver update, constraint, in that order.  Every other combination runs
+        the loop of the dedicated method and returns its bits.  Every refusal is raised before any GPU work.
+        The control quality of such plans has not been evaluated."""
+        from .constrain import MODES, build_constraint
+        from .guide import Guide
+        from .replan import check_warm_steps
+        if not (self.use_planner and self.use_idm):
+            raise NotImplementedError("plan() needs both the planner and the IDM (use_planner / use_idm)")
+        if mode not in MODES:
+            raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+        if guide is not None and not isinstance(guide, Guide):
+            raise ValueError(f"guide must be a guide.Guide (guide.build_guide / LDPAgent.build_guide), got {type(guide).__name__}")
+        if (prev is None) != (warm_steps is None):
+            raise ValueError("prev and warm_steps go together: both None (a cold call) or both given")
+        if (target is None) != (mask is None):
+            raise ValueError("target and mask go together: give both or neither")
+        if goal is None and (t_goal is not None or goal_dims is not None):
+            raise ValueError("t_goal and goal_dims describe `goal`: give goal too")
+        seed = _seed_of(eval_rng)
+        cfg = self.config
+        oh = cfg["obs_horizon"]
+        ns = int(cfg["planner_n_diffusion_steps"] if n_steps is None else n_steps)
+        if idm_steps is None and n_steps is not None and sampler != "ddpm":
+            idm_steps = n_steps                                # one schedule for both loops unless told otherwise
+        nz = dict(noise or {})
+        step_begin, sh = 0, None
+        if prev is not None:
+            step_begin = check_warm_steps(warm_steps, ns)
+            if "x_init" in nz:
+                raise ValueError("a warm call has no x_init: its initial state is the shifted, noised previous plan")
+            sh = int(cfg["action_horizon"] if shift is None else shift)
+            if sh < 0:
+                raise ValueError(f"shift must be >= 0, got {shift}")
+        elif shift is not None:
+            raise ValueError("shift describes a warm start: give prev and warm_steps too")
+        self._solver_setup(sampler, n_steps, idm_steps, timesteps)
+        rho = None if guide is None else self._guide_step_sizes(guide, sampler, ns)
+        constrained = target is not None or goal is not None
+
+        def run():
+            self._sync_weights()
+            obs_emb = self.get_obs_cond(self._vae_encode_t(self._postprocess(batch)["obs"])).contiguous()
+            B = obs_emb.shape[0]
+            gd = guide
+            if gd is not None:
+                if gd.B != B:
+                    raise ValueError(f"the guide was built for B = {gd.B} plans, the batch holds {B}")
+                if gd.anchor is True:                          # this batch's own current observation: a copy of the guide, not the caller's
+                    gd = Guide(gd.cfg, gd.B, gd.target, gd.weight, obs_emb[:, oh - 1].contiguous(), gd.lam, gd.beta, gd.lo, gd.hi, gd.scale,
+                               gd.schedule, self._engine, gd.wmax)
+            tg = mk = None
+            if constrained:
+                g = None if goal is None else self._goal_embedding(goal, B)
+                tg, mk = build_constraint(cfg, B, target=None if target is None else self._t(target), mask=mask, goal=g, t_goal=t_goal,
+                                          goal_dims=goal_dims)
+            store = None
+            if prev is not None:
+                store = self._t(prev).clone()                  # the engine writes the new state back in place: not into the caller's prev
+                if tuple(store.shape) != (B, cfg["pred_horizon"], cfg["obs_dim"]):
+                    raise ValueError(f"prev must have shape {(B, cfg['pred_horizon'], cfg['obs_dim'])}, got {tuple(store.shape)}")
+            lo_a, hi_a, amode = self._action_bounds()
+            x, plan, action = self._engine.agent_sample_composed(
+                obs_emb, oh, guide=gd, rho=rho, target=tg, mask=mk, mode=mode, x_store=store, shift=sh, step_begin=step_begin,
+                x_init=nz.get("x_init"), x_noise=nz.get("x_noise"), a_init=nz.get("a_init"), a_noise=nz.get("a_noise"), seed=seed,
+                row_offset=row_offset, sampler=sampler, planner_steps=ns, idm_steps=idm_steps, action_bounds=(lo_a, hi_a), action_mode=amode)
+            out = [action, plan, x]
+            if gd is not None:
+                out.append(self._engine.plan_guide_cost(x, gd))
+            if obs_emb.shape[1] > oh:                          # from a training batch, not inference (:447-448)
+                out.append(self._engine.mean_sq_diff(x, obs_emb[:, oh:]))
+            return out
+
+        def recompute():
+            if isinstance(prev, DeviceArray):
+                prev.complete()                                # the previous call may be the one that faulted: its x first
+            return run() + [None]                              # plan_viz re-decodes itself from the new plan
+        res, rec = self._call(run, recompute)
+        action, plan, x = (DeviceArray(t, record=rec) for t in res[:3])
+        metrics = {"plan": plan, "x": x}
+        rest = list(res[3:])
+        if guide is not None:
+            metrics["guide_cost"] = DeviceArray(rest.pop(0), record=rec)
+        if rest:
+            metrics["plan_mse"] = DeviceArray(rest[0], record=rec)
+        S = self._engine.image_size
+        viz = DeviceArray(thunk=lambda: self._vae_decode_t(plan.tensor), shape=tuple(plan.shape[:2]) + (3, S, S), record=rec)
+        if decode:
+            viz.tensor
+        metrics["plan_viz"] = viz
+        return action, metrics
+
+    def controller(self, n_slots, warm_steps, sampler="ddim", n_steps=None, timesteps=None, shift=None):
+        """A Controller (replan.py) for closed-loop control of up to n_slots environments: a Replanner whose act() also takes a guide and
+        a constraint, under any sampler ("dpmpp": over the timestep table `timesteps`, as in sample_viz)."""
+        from .replan import Controller
+        if not (self.use_planner and self.use_idm):
+            raise NotImplementedError("controller() needs both the planner and the IDM (use_planner / use_idm)")
+        self._solver_setup(sampler, n_steps, n_steps, timesteps)
+        return Controller(self, n_slots, warm_steps, sampler=sampler, n_steps=n_steps, shift=shift)
+
     # ---- best-of-N planning (defined by this repository: DESIGN.md 4.14; csrc/select.hip) ----------------------------------
     def _goal_embedding(self, goal, B):
         """`goal`: normalised embeddings (B, D), or an observation dict in batch['obs'] form (embedded like the batch, frame 0)."""

@@ -35,6 +35,22 @@ def level_coefs(n_train: int, n_steps: int) -> np.ndarray:
     return out
 
 
+def table_level_coefs(n_train: int, timesteps) -> np.ndarray:
+    """level_coefs over a timestep table (sampler "dpmpp", csrc/constrain.hip table_level_coefs): (n + 1, 2) float32 for the n entries of
+    `timesteps` (first executed step first): row j < n = (sqrt(abar_ts[j]), sqrt(1 - abar_ts[j])), float64 from the float32 abar table and
+    cast once; row n is exactly (1, 0)."""
+    ts = [int(t) for t in np.asarray(timesteps).reshape(-1)]
+    if any(not 0 <= t < n_train for t in ts):
+        raise ValueError(f"timesteps must lie in 0..{n_train - 1}, got {ts}")
+    acp = schedule.make_schedule(n_train).alphas_cumprod
+    out = np.empty((len(ts) + 1, 2), np.float32)
+    for j, t in enumerate(ts):
+        a_t = float(np.float32(acp[t]))
+        out[j] = (math.sqrt(a_t), math.sqrt(1.0 - a_t))
+    out[len(ts)] = (1.0, 0.0)
+    return out
+
+
 def _is_torch(a) -> bool:
     return type(a).__module__.split(".")[0] == "torch"
 

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <vector>
 
 #include "engine.hpp"
 
@@ -117,6 +118,19 @@ int level_coefs(int n_train, int n_steps, int level, float* a, float* s) {
   if (level < 0 || level > n_steps) return fail(LDP_EINVAL, "level %d outside 0..n_steps = %d", level, n_steps);
   if (level == n_steps) { *a = 1.0f; *s = 0.0f; return LDP_OK; }
   return warm_coefs(n_train, n_steps, level, a, s);      // t_level = (n_steps - 1 - level) * (n_train / n_steps): warm_coefs' convention
+}
+
+// the same over a registered timestep table (sampler 2, compose.hip): level j < n has the timestep ts[j]
+int table_level_coefs(int n_train, const std::vector<int32_t>& ts, int level, float* a, float* s) {
+  const int n_steps = (int)ts.size();
+  if (level < 0 || level > n_steps) return fail(LDP_EINVAL, "level %d outside 0..n_steps = %d", level, n_steps);
+  if (level == n_steps) { *a = 1.0f; *s = 0.0f; return LDP_OK; }
+  std::vector<float> betas, alphas, acp;
+  betas_squaredcos(n_train, betas, alphas, acp);
+  const double a_t = acp[ts[level]];              // float32 table, float64 from here (warm_coefs' convention)
+  *a = (float)std::sqrt(a_t);
+  *s = (float)std::sqrt(1.0 - a_t);
+  return LDP_OK;
 }
 
 int plan_constrain_launch(const float* x, const float* target, const uint8_t* mask, float* out, int ld, int64_t rows, int D, int DP, float a,

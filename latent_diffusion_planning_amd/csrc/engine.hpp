@@ -88,6 +88,7 @@ struct GraphKey {
   int begin = 0, end = -1;                        // planner loops (kind 0, 2): the executed steps [begin, end) of n_steps; (0, -1) = no planner range (the IDM loop, kind 1)
   int constrain = 0;                              // planner loops: 0 = the free loop, else the LDP_CONSTRAIN_* mode whose launches the graph carries (constrain.hip)
   int guide = 0;                                  // planner loops: 0 = no guide, else LDP_GUIDE_ON / LDP_GUIDE_ANCHOR: the guided loop's launches (guide.hip)
+  int composed = 0;                               // planner loops: 1 = the composed loop (compose.hip): one composed step behind every U-Net evaluation
   bool operator<(const GraphKey& o) const {
     if (kind != o.kind) return kind < o.kind;
     if (B != o.B) return B < o.B;
@@ -99,7 +100,8 @@ struct GraphKey {
     if (begin != o.begin) return begin < o.begin;
     if (end != o.end) return end < o.end;
     if (constrain != o.constrain) return constrain < o.constrain;
-    return guide < o.guide;
+    if (guide != o.guide) return guide < o.guide;
+    return composed < o.composed;
   }
 };
 
@@ -285,7 +287,9 @@ inline int bucket_rows(int B, bool explicit_noise) { return explicit_noise ? B :
 // step i, on the target / mask staged into P.ctarget / P.cmask.
 // guide: 0, or LDP_GUIDE_ON / LDP_GUIDE_ANCHOR for a guided loop (guide.hip): the U-Net writes eps only and the guided step behind it
 // updates the state, on the guide staged into P.gtarget / P.gwg / P.ganchor / P.gcol (ANCHOR: with the continuity term).
-struct LoopSpec { int n_steps = 0, sampler = 0; bool explicit_noise = false; int begin = 0, end = -1; int constrain = 0; int guide = 0; };
+// composed: the composed loop (compose.hip): `constrain` and `guide` keep their meaning, C_begin runs once in front and ONE composed step
+// behind every U-Net evaluation does the rest.  Set by the composed entry points where a guide meets a constraint, or either meets sampler 2.
+struct LoopSpec { int n_steps = 0, sampler = 0; bool explicit_noise = false; int begin = 0, end = -1; int constrain = 0; int guide = 0; bool composed = false; };
 constexpr int LDP_GUIDE_ON = 1, LDP_GUIDE_ANCHOR = 2;
 int check_step_range(int begin, int end, int n_steps, const char* what);
 struct WarmSpec;                                 // a warm start of the planner state (below)
@@ -339,6 +343,8 @@ int unpad_rows_index_launch(const float* src, float* dst, const int32_t* slot_de
 int check_constrain_mode(int mode);              // LDP_EINVAL unless LDP_CONSTRAIN_CLAMP / LDP_CONSTRAIN_REPAINT
 // level j in 0 .. n_steps: (a, s) = warm_coefs at t_j for j < n_steps, exactly (1, 0) at j = n_steps; LDP_EINVAL names `level` outside
 int level_coefs(int n_train, int n_steps, int level, float* a, float* s);
+// the same over a registered timestep table ts (sampler 2): level j < n_steps has the timestep ts[j], level n_steps is exactly (1, 0)
+int table_level_coefs(int n_train, const std::vector<int32_t>& ts, int level, float* a, float* s);
 // out <- mask != 0 ? (noise ? fma(a, target, rn(s * z)) : target) : x, all four with row stride ld; z = philox_normal(seed, (row0 + r) * DP
 // + c, level, LDP_PHILOX_STREAM_CONSTRAIN) with (seed, row0) read from `ctl` when it is given (captured loops), else the arguments
 int plan_constrain_launch(const float* x, const float* target, const uint8_t* mask, float* out, int ld, int64_t rows, int D, int DP, float a,
@@ -374,4 +380,13 @@ int check_guide(const GuideSpec* g, int D, int n_steps, int sampler);
 int guide_stage(ldp_handle* h, const GuideSpec& g, int B, int Bg, hipStream_t st);
 // the guided step i on the loop state, eps read from P.solver_eps, explicit noise (B, T, D) or nullptr: one launch, counted
 int planner_guide_step(ldp_handle* h, int Bg, const LoopSpec& L, const StepCoef& k, const float* noise, int i, hipStream_t q);
+// ---- composed planning (compose.hip) ------------------------------------------------------------------------
+// (a, s) of constraint level `level` under `sampler`: level_coefs on the uniform grid, table_level_coefs of the registered table under sampler 2
+int compose_level_coefs(const ldp_handle* h, int sampler, int n_steps, int level, float* a, float* s);
+// C_level on the loop state in front of a composed loop: planner_constrain_level, or its table-level counterpart under sampler 2; one launch, counted
+int planner_constrain_begin(ldp_handle* h, int Bg, const LoopSpec& L, int level, hipStream_t q);
+// the composed step i on the loop state: eps from P.solver_eps, the guide / constraint from the staged buffers as L names them, the
+// history in P.solver_x0; k (DDPM / DDIM) or ks (sampler 2) is the step's coefficient row; one launch, counted
+int planner_compose_step(ldp_handle* h, int Bg, const LoopSpec& L, const StepCoef* k, const SolverCoef* ks, const float* noise, int i,
+                         bool second, hipStream_t q);
 }  // namespace ldp

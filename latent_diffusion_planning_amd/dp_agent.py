@@ -288,6 +288,12 @@ class DPAgent(_EngineCalls):
     def build_guide(self, *a, **k):
         raise NotImplementedError("build_guide is built for LDPAgent only (its costs are stated on latent plans; a DP agent denoises actions)")
 
+    def plan(self, *a, **k):
+        raise NotImplementedError("plan is built for LDPAgent only (its parts are stated on latent plans; a DP agent denoises actions)")
+
+    def controller(self, *a, **k):
+        raise NotImplementedError("controller is built for LDPAgent only (its parts are stated on latent plans; a DP agent denoises actions)")
+
     def sample_action_from_plan(self, *a, **k):
         raise NotImplementedError("DPAgent has no sample_action_from_plan")
 

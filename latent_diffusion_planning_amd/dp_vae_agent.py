@@ -182,6 +182,12 @@ class DPVAEAgent(LDPAgent):
     def build_guide(self, *a, **k):
         raise NotImplementedError("build_guide is built for LDPAgent only (its costs are stated on latent plans; a DP agent denoises actions)")
 
+    def plan(self, *a, **k):
+        raise NotImplementedError("plan is built for LDPAgent only (its parts are stated on latent plans; a DP agent denoises actions)")
+
+    def controller(self, *a, **k):
+        raise NotImplementedError("controller is built for LDPAgent only (its parts are stated on latent plans; a DP agent denoises actions)")
+
     def update_mixed(self, *a, **k):
         raise NotImplementedError("DPVAEAgent has no update_mixed")
 

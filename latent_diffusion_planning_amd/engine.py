@@ -677,6 +677,152 @@ class HipEngine:
         self.call_seq += 1
         return x, plan, act
 
+    # -- composed planning (csrc/compose.hip) ----------------------------------------------------------
+    def _compose(self, B: int, n_steps: int, *, guide=None, rho=None, target=None, mask=None, mode="repaint", x_store=None, slot=None,
+                 shift: Optional[int] = None, ldg: Optional[int] = None, ldc: Optional[int] = None, device_cols: bool = False):
+        """The ldp_plan_compose of a call and whatever must stay alive until it returns.  guide with rho (n_steps step sizes), target with
+        mask, x_store (with slot / shift): each part is optional.  device_cols: lam, beta, lo, hi, rho as device tensors (the stand-alone
+        step) instead of host arrays (the sampling calls).  ldg / ldc: padded row strides of the guide's / the constraint's arrays."""
+        pc, keep = _lib.LdpPlanCompose(), []
+        if x_store is not None:
+            xs = self._store(x_store)
+            sp, k = self._slots(slot, B)
+            keep += [xs, k]
+            pc.x_store, pc.slot, pc.n_slots = xs.data_ptr(), sp, int(xs.shape[0])
+            pc.shift = self.ah if shift is None else int(shift)
+        elif slot is not None or shift is not None:
+            raise ValueError("slot and shift describe a warm start: give x_store too")
+        if (target is None) != (mask is None):
+            raise ValueError("target and mask are both required")
+        if target is not None:
+            tg, mk, md = self._constraint(target, mask, mode, B)
+            if ldc is not None and ldc != self.D:
+                tg = torch.nn.functional.pad(tg, (0, ldc - self.D)).contiguous()
+                mk = torch.nn.functional.pad(mk, (0, ldc - self.D)).contiguous()
+            keep += [tg, mk]
+            pc.target, pc.mask, pc.mode = tg.data_ptr(), mk.data_ptr(), md
+        if (guide is None) != (rho is None):
+            raise ValueError("guide and rho go together: give both or neither")
+        if guide is not None:
+            tg, wg, an, cols = self._guide(guide, B, ldg)
+            rh = np.ascontiguousarray(np.asarray(rho, dtype=np.float32).reshape(-1))
+            keep += [tg, wg, an]
+            pc.g_target, pc.g_wg, pc.g_anchor = tg.data_ptr(), wg.data_ptr(), None if an is None else an.data_ptr()
+            if device_cols:
+                dev = [torch.as_tensor(a).to(self.device) for a in cols + [rh]]
+                ptrs = [t.data_ptr() for t in dev]
+                keep += dev
+            else:
+                ptrs = [a.ctypes.data for a in cols + [rh]]
+                keep += cols + [rh]
+            pc.lam, pc.beta, pc.lo, pc.hi, pc.rho = ptrs
+            pc.n_rho = int(rh.size)
+        return pc, keep
+
+    def plan_compose_step(self, x: torch.Tensor, eps: torch.Tensor, step: int, *, guide=None, rho=None, target=None, mask=None,
+                          mode="repaint", noise=None, x0_prev=None, second: bool = False, seed: int = 0, row_offset: int = 0,
+                          sampler: str = "ddim", n_steps: Optional[int] = None, ldg: Optional[int] = None, ldc: Optional[int] = None,
+                          inplace: bool = False):
+        """One composed step (one launch): x (B, T, ldx) with ldx >= D (a padded state: the columns beyond D keep their bits), eps
+        (B, T, D) -> the new x; under sampler "dpmpp" -> (x, x0) with x0 (B, T, ldx) the guided data prediction the next step takes as
+        x0_prev (second: this step is second order, on x0_prev (B, T, ldx)).  guide with rho (n_steps,), target with mask: the optional
+        parts.  noise (B, T, D) or None (the Philox draw of (seed, row_offset)).  inplace: x (and x0_prev, when given) are overwritten."""
+        xt = x if inplace else _f32(x, self.device).clone()
+        if not (torch.is_tensor(xt) and xt.is_cuda and xt.dtype == torch.float32 and xt.is_contiguous()):
+            raise ValueError("inplace: x must be a contiguous float32 device tensor")
+        B, ldx = int(xt.shape[0]), int(xt.shape[-1])
+        if xt.dim() != 3 or xt.shape[1] != self.T or ldx < self.D:
+            raise ValueError(f"x must have shape {(B, self.T, self.D)} (or a wider last axis), got {tuple(xt.shape)}")
+        ep = _f32(eps, self.device)
+        nz = None if noise is None else _f32(noise, self.device)
+        _want("eps", ep, (B, self.T, self.D))
+        _want("noise", nz, (B, self.T, self.D))
+        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
+        sid = self._sampler(sampler, n_steps)
+        hp = h_out = None
+        if sid == SAMPLER_DPMPP:
+            if x0_prev is not None:
+                hp = x0_prev if inplace else _f32(x0_prev, self.device).clone()
+                if not (torch.is_tensor(hp) and hp.is_cuda and hp.dtype == torch.float32 and hp.is_contiguous()):
+                    raise ValueError("inplace: x0_prev must be a contiguous float32 device tensor")
+                _want("x0_prev", hp, tuple(xt.shape))
+            h_out = hp if hp is not None else torch.zeros_like(xt)
+        pc, keep = self._compose(B, n_steps, guide=guide, rho=rho, target=target, mask=mask, mode=mode, ldg=ldg, ldc=ldc, device_cols=True)
+        check(self.lib.ldp_plan_compose_step(self._h, _ptr(xt), _ptr(ep), _ptr(nz), _ptr(hp), C.byref(pc), sid, n_steps, int(step),
+                                             1 if second else 0, C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _ptr(xt), _ptr(h_out),
+                                             ldx, self.D if ldg is None else int(ldg), self.D if ldc is None else int(ldc), B, self._stream()))
+        del keep
+        return (xt, h_out) if sid == SAMPLER_DPMPP else xt
+
+    def plan_sample_composed(self, cond: Optional[torch.Tensor], *, guide=None, rho=None, target=None, mask=None, mode="repaint",
+                             x_store=None, slot=None, shift: Optional[int] = None, step_begin: int = 0, step_end: Optional[int] = None,
+                             B: Optional[int] = None, x_init: Optional[torch.Tensor] = None, step_noise: Optional[torch.Tensor] = None,
+                             seed: int = 0, row_offset: int = 0, sampler: str = "ddim", n_steps: Optional[int] = None,
+                             use_graph: bool = True) -> torch.Tensor:
+        """plan_sample_range with any of a guide (with rho), a constraint (target, mask, mode) and a warm start (x_store, slot, shift: the
+        initial state is the warm one at the level of step_begin; x_store is not written), under any sampler.  A guide with a
+        constraint, and either under "dpmpp", run the composed loop (one composed launch behind every U-Net evaluation); every other
+        combination runs the dedicated loop."""
+        cond_t = None if cond is None else _f32(cond, self.device)
+        if B is None:
+            B = cond_t.shape[0] if cond_t is not None else x_init.shape[0]
+        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
+        step_end = n_steps if step_end is None else int(step_end)
+        xi = None if x_init is None else _f32(x_init, self.device)
+        nz = None if step_noise is None else _f32(step_noise, self.device)
+        _want("cond", cond_t, (B, self.G))
+        _want("x_init", xi, (B, self.T, self.D))
+        _want("step_noise", nz, (n_steps, B, self.T, self.D))
+        pc, keep = self._compose(B, n_steps, guide=guide, rho=rho, target=target, mask=mask, mode=mode, x_store=x_store, slot=slot, shift=shift)
+        out = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_plan_sample_composed(self._h, _ptr(cond_t), _ptr(xi), _ptr(nz), C.byref(pc), C.c_uint64(seed & (2**64 - 1)),
+                                                C.c_int64(row_offset), self._sampler(sampler, n_steps), n_steps, int(step_begin), step_end,
+                                                _ptr(out), B, 1 if use_graph else 0, self._stream()))
+        del keep
+        self.call_seq += 1
+        return out
+
+    def agent_sample_composed(self, obs_emb: torch.Tensor, obs_horizon: int, *, guide=None, rho=None, target=None, mask=None,
+                              mode="repaint", x_store=None, slot=None, shift: Optional[int] = None, step_begin: int = 0, x_init=None,
+                              x_noise=None, a_init=None, a_noise=None, seed: int = 0, row_offset: int = 0, sampler: str = "ddim",
+                              planner_steps: Optional[int] = None, idm_steps: Optional[int] = None, action_bounds=None,
+                              action_mode: int = 0, use_graph: bool = True):
+        """agent_sample (no x_store) / agent_resample (x_store: the planner loop is [step_begin, planner_steps) from the warm state, and
+        the new state is written back IN PLACE to the same rows of x_store) with any of a guide and a constraint, under any sampler
+        -> (x, plan, action)."""
+        ob = _f32(obs_emb, self.device)
+        B, H = ob.shape[0], ob.shape[1]
+        _want("obs_emb", ob, (B, H, self.D))
+        ps = self.planner_train_steps if planner_steps is None else int(planner_steps)
+        is_ = self.idm_train_steps if idm_steps is None else int(idm_steps)
+        R = B * self.ah
+        xi = None if x_init is None else _f32(x_init, self.device)
+        xn = None if x_noise is None else _f32(x_noise, self.device)
+        ai = None if a_init is None else _f32(a_init, self.device)
+        an = None if a_noise is None else _f32(a_noise, self.device)
+        _want("x_init", xi, (B, self.T, self.D))
+        _want("x_noise", xn, (ps, B, self.T, self.D))
+        _want("a_init", ai, (R, self.A))
+        _want("a_noise", an, (is_, R, self.A))
+        pc, keep = self._compose(B, ps, guide=guide, rho=rho, target=target, mask=mask, mode=mode, x_store=x_store, slot=slot, shift=shift)
+        lo = hi = None
+        adim = 0
+        if action_bounds is not None:
+            lo, hi = self._bounds(*action_bounds)
+            adim = lo.numel()
+            if adim not in (1, self.A) or hi.numel() != adim:
+                raise ValueError(f"action bounds must have length 1 or {self.A}")
+        x = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
+        plan = torch.empty((B, self.ah + 1, self.D), device=self.device, dtype=torch.float32)
+        act = torch.empty((B, self.ah, self.A), device=self.device, dtype=torch.float32)
+        check(self.lib.ldp_agent_sample_composed(self._h, _ptr(ob), H, int(obs_horizon), _ptr(xi), _ptr(xn), _ptr(ai), _ptr(an), C.byref(pc),
+                                                 int(step_begin), C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset),
+                                                 self._sampler(sampler, ps), ps, is_, _ptr(x), _ptr(plan), _ptr(act), _ptr(lo), _ptr(hi), adim,
+                                                 int(action_mode), B, 1 if use_graph else 0, self._stream()))
+        del keep
+        self.call_seq += 1
+        return x, plan, act
+
     # -- best-of-N planning (csrc/select.hip, DESIGN.md 4.14): candidate-major rows r = c * B + b ---------------------
     def plan_candidates(self, obs_emb: torch.Tensor, obs_horizon: int, n_candidates: int, *, c0: int = 0, n_loc: Optional[int] = None,
                         x_init=None, step_noise=None, seed: int = 0, sampler: str = "ddpm", n_steps: Optional[int] = None,

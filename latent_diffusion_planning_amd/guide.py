@@ -66,6 +66,27 @@ class Guide:
         None is 1 / L, the largest constant step the descent bound allows (0 for the empty guide).  ValueError when max rho * L > 1."""
         n_steps = int(n_steps)
         n_train = int(self.cfg.get("planner_n_diffusion_steps", 100) if n_train is None else n_train)
+        if isinstance(self.schedule, str) and self.schedule == "sigma2":
+            if sampler not in ("ddpm", "ddim"):
+                raise NotImplementedError(f'guidance under sampler="{sampler}" is not built: it runs under "ddpm" and "ddim"')
+            ts = schedule.step_timesteps(n_train, n_steps, schedule.SAMPLER_DDPM if sampler == "ddpm" else schedule.SAMPLER_DDIM)
+        else:
+            ts = np.zeros(n_steps, np.int64)                   # (a constant or explicit table does not read the timesteps)
+        return self._step_sizes(ts, n_train)
+
+    def step_sizes_on(self, timesteps, n_train: Optional[int] = None) -> np.ndarray:
+        """step_sizes at the entries of a timestep table (first executed step first), for loops that do not run on the uniform grid
+        (sampler "dpmpp" through LDPAgent.plan): "sigma2" -> scale (1 - abar_ts[i]), "constant" and explicit tables as in step_sizes,
+        with the same descent-bound refusal."""
+        n_train = int(self.cfg.get("planner_n_diffusion_steps", 100) if n_train is None else n_train)
+        ts = np.asarray(_host(timesteps), dtype=np.int64).reshape(-1)
+        if len(ts) and (ts.min() < 0 or ts.max() >= n_train):
+            raise ValueError(f"timesteps must lie in 0..{n_train - 1}, got {ts.tolist()}")
+        return self._step_sizes(ts, n_train)
+
+    def _step_sizes(self, ts: np.ndarray, n_train: int) -> np.ndarray:
+        """rho at the timesteps ts of the executed steps (step_sizes / step_sizes_on)."""
+        n_steps = len(ts)
         L = self.lipschitz
         if self.scale is None:                                 # the largest float32 with scale * L <= 1
             scale = np.float32(1.0 / L if L > 0 else 0.0)
@@ -78,9 +99,6 @@ class Guide:
             if self.schedule == "constant":
                 rho = np.full(n_steps, scale, np.float64)
             elif self.schedule == "sigma2":
-                if sampler not in ("ddpm", "ddim"):
-                    raise NotImplementedError(f'guidance under sampler="{sampler}" is not built: it runs under "ddpm" and "ddim"')
-                ts = schedule.step_timesteps(n_train, n_steps, schedule.SAMPLER_DDPM if sampler == "ddpm" else schedule.SAMPLER_DDIM)
                 acp = schedule.make_schedule(n_train).alphas_cumprod.astype(np.float64)
                 rho = scale * (1.0 - acp[ts])
             else:

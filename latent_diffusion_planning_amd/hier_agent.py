@@ -155,6 +155,12 @@ class LDPHierAgent(LDPAgent):
     def build_guide(self, *a, **k):
         raise NotImplementedError("build_guide is built for LDPAgent only (the hierarchical plan has a stride and a U-Net IDM)")
 
+    def plan(self, *a, **k):
+        raise NotImplementedError("plan is built for LDPAgent only (the hierarchical plan has a stride and a U-Net IDM)")
+
+    def controller(self, *a, **k):
+        raise NotImplementedError("controller is built for LDPAgent only (the hierarchical plan has a stride and a U-Net IDM)")
+
     # ---- agent/ldp_hier_agent.py:385-461 -----------------------------------------------------------
     def sample(self, batch, eval_rng, **kw):
         kw.setdefault("decode", False)

@@ -101,9 +101,18 @@ class Replanner:
             t = self._slot_cache[key] = torch.as_tensor(list(slots), dtype=dtype).to(self.agent._device)
         return t
 
-    def _run(self, batch, seed, slots, order, n_warm, keep=None):
+    def _warm_call(self, eng, emb, table, slot_t, rows, extras, kw):
+        """The engine call of the warm group: emb its rows (reordered), slot_t their slots on the device, rows their indices in the
+        caller's batch -> (x, plan, action).  Controller overrides this."""
+        return eng.agent_resample(emb, self.agent.config["obs_horizon"], table, self.step_begin, slot=slot_t, shift=self.shift, row_offset=0, **kw)
+
+    def _cold_call(self, eng, emb, rows, row_offset, extras, kw):
+        """The engine call of the cold group -> (x, plan, action).  Controller overrides this."""
+        return eng.agent_sample(emb, self.agent.config["obs_horizon"], row_offset=row_offset, **kw)
+
+    def _run(self, batch, seed, slots, order, n_warm, keep=None, extras=None):
         """The engine calls of one act() -> [action, plan, x] in the caller's row order (device tensors).  keep: per reordered cold row,
-        whether its x is stored (None: all)."""
+        whether its x is stored (None: all).  extras: what a subclass hands its group calls (Replanner: nothing)."""
         ag = self.agent
         eng, cfg = ag._engine, ag.config
         ag._sync_weights()
@@ -120,12 +129,11 @@ class Replanner:
                   action_mode=mode)
         parts = []
         if n_warm:
-            parts.append(eng.agent_resample(emb[:n_warm], cfg["obs_horizon"], table, self.step_begin,
-                                            slot=self._dev_slots([slots[i] for i in order[:n_warm]], torch.int32), shift=self.shift,
-                                            row_offset=0, **kw))
+            parts.append(self._warm_call(eng, emb[:n_warm], table, self._dev_slots([slots[i] for i in order[:n_warm]], torch.int32),
+                                         list(order[:n_warm]), extras, kw))
             self.calls["warm"] += 1
         if n_warm < len(order):
-            x, plan, act = eng.agent_sample(emb[n_warm:], cfg["obs_horizon"], row_offset=n_warm, **kw)
+            x, plan, act = self._cold_call(eng, emb[n_warm:], list(order[n_warm:]), n_warm, extras, kw)
             cold = [slots[i] for i in order[n_warm:]]
             if keep is None:
                 table.index_copy_(0, self._dev_slots(cold, torch.long), x)
@@ -143,9 +151,12 @@ class Replanner:
 
     def act(self, batch, eval_rng, slots, decode: bool = False):
         """-> (action (B, ah, A), metrics) like LDPAgent.sample_viz, plus metrics['x'] (B, T, D), in the caller's row order."""
+        return self._act(batch, eval_rng, self._slots(slots), decode, None)
+
+    def _act(self, batch, eval_rng, slots, decode, extras):
+        """act() on validated slots; extras: what a subclass hands its group calls, the same in the first attempt, the retry and a late recompute."""
         from .agent import _seed_of
         ag = self.agent
-        slots = self._slots(slots)
         seed = _seed_of(eval_rng)
         order, n_warm = group_rows(self.valid, slots)
 
@@ -156,14 +167,16 @@ class Replanner:
             # the first attempt follows the grouping rule.  If the engine refuses one of its calls because of an earlier, unread fault,
             # the warm rows of this attempt may already have overwritten their slots: the retry runs every row cold
             attempts[0] += 1
-            return self._run(batch, seed, slots, order, n_warm) if attempts[0] == 1 else self._run(batch, seed, slots, straight, 0)
+            if attempts[0] == 1:
+                return self._run(batch, seed, slots, order, n_warm, extras=extras)
+            return self._run(batch, seed, slots, straight, 0, extras=extras)
 
         def recompute():
             # a fault invalidated this call AFTER its warm rows overwrote their slots: the previous states are gone, so the recompute
             # runs every row cold, in the caller's order (a valid plan; the handle has changed its launch mode by then anyway).  It runs
             # when the call's results are first read, possibly after later act() calls: only slots no later call has written are stored
             # (those later calls are suspect too -- a fault marks every call enqueued before its poll -- and recompute cold themselves).
-            return self._run(batch, seed, slots, straight, 0, keep=[self.gen[s] == mine[s] for s in slots]) + [None]
+            return self._run(batch, seed, slots, straight, 0, keep=[self.gen[s] == mine[s] for s in slots], extras=extras) + [None]
         res, rec = ag._call(run, recompute)
         for s in slots:
             self.valid[s] = True
@@ -175,3 +188,65 @@ class Replanner:
         if decode:
             viz.tensor
         return action, {"plan": plan, "x": x, "plan_viz": viz}
+
+
+class Controller(Replanner):
+    """A Replanner whose rows can also be steered (`LDPAgent.controller`): act() takes a guide and / or a constraint, and
+    runs under any sampler, "dpmpp" included.  The grouping rule, the slot table, the fault retry and the recompute are Replanner's; its
+    warm and cold group calls go through `agent_sample_composed`, which hands each group its rows of the guide and the constraint.  With
+    neither, and under DDPM / DDIM, the results are Replanner's bit for bit.
+
+    Whether such plans control well has NOT been evaluated: there is no checkpoint and no simulator here."""
+
+    def act(self, batch, eval_rng, slots, guide=None, decode: bool = False, **constraint_kw):
+        """Replanner.act with `guide` (a guide.Guide for the B rows of this call, in the caller's row order; anchor=True: each row's own
+        last observation embedding) and a constraint in constrain.build_constraint's keywords (target, mask, goal, t_goal, goal_dims)
+        plus mode ('repaint' / 'clamp').  Every refusal is raised before any engine call."""
+        from .constrain import MODES, build_constraint
+        from .guide import Guide
+        ag = self.agent
+        slots = self._slots(slots)
+        B = len(slots)
+        mode = constraint_kw.pop("mode", "repaint")
+        unknown = sorted(set(constraint_kw) - {"target", "mask", "goal", "t_goal", "goal_dims"})
+        if unknown:
+            raise TypeError(f"act() got unexpected keyword arguments {unknown}")
+        if mode not in MODES:
+            raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+        extras = dict(guide=None, rho=None, target=None, mask=None, mode=mode)
+        if guide is not None:
+            if not isinstance(guide, Guide):
+                raise ValueError(f"guide must be a guide.Guide (guide.build_guide / LDPAgent.build_guide), got {type(guide).__name__}")
+            if guide.B != B:
+                raise ValueError(f"the guide was built for B = {guide.B} plans, the call holds {B} rows")
+            extras["guide"], extras["rho"] = guide, ag._guide_step_sizes(guide, self.sampler, self.n_steps)
+        if any(v is not None for v in constraint_kw.values()):
+            goal = constraint_kw.get("goal")
+            kw = dict(constraint_kw, goal=None if goal is None else ag._goal_embedding(goal, B))
+            if kw.get("target") is not None:
+                kw["target"] = ag._t(kw["target"])
+            tg, mk = build_constraint(ag.config, B, **kw)
+            extras["target"], extras["mask"] = ag._t(tg), torch.as_tensor(mk)
+        return self._act(batch, eval_rng, slots, decode, extras)
+
+    def _parts(self, emb, rows, extras):
+        """The rows of the guide and the constraint that belong to one group call, as agent_sample_composed's keywords."""
+        from .guide import Guide
+        kw = dict(mode=extras["mode"])
+        gd = extras["guide"]
+        if gd is not None:
+            oh = self.agent.config["obs_horizon"]
+            anchor = emb[:, oh - 1].contiguous() if gd.anchor is True else None if gd.anchor is None else self.agent._t(gd.anchor)[rows]
+            kw["guide"] = Guide(gd.cfg, len(rows), gd.target[rows], gd.weight[rows], anchor, gd.lam, gd.beta, gd.lo, gd.hi, gd.scale,
+                                gd.schedule, gd.engine, gd.wmax)
+            kw["rho"] = extras["rho"]
+        if extras["target"] is not None:
+            kw["target"], kw["mask"] = extras["target"][rows], extras["mask"][rows]
+        return kw
+
+    def _warm_call(self, eng, emb, table, slot_t, rows, extras, kw):
+        return eng.agent_sample_composed(emb, self.agent.config["obs_horizon"], x_store=table, slot=slot_t, shift=self.shift,
+                                         step_begin=self.step_begin, row_offset=0, **self._parts(emb, rows, extras), **kw)
+
+    def _cold_call(self, eng, emb, rows, row_offset, extras, kw):
+        return eng.agent_sample_composed(emb, self.agent.config["obs_horizon"], row_offset=row_offset, **self._parts(emb, rows, extras), **kw)
