@@ -943,7 +943,7 @@ class LDPAgent(_EngineCalls):
         action_horizon - 1) into the columns `goal_dims` (None / 'all', 'latent', 'lowdim', an index list, a bool (D,) array).  Values
         are in the normalised embedding units of the plan; they belong in [-1, 1], where the scheduler clips its own estimate.  With
         nothing given the call is sample()'s.  noise: optional dict(x_init, x_noise, a_init, a_noise) as in sample_viz.
-        The control quality of inpainted plans has not been evaluated."""
+        The control quality of inpainted plans has not been evaluated (the toy task of DESIGN.md 4.21 has no inpainting arm)."""
         from .constrain import MODES, build_constraint
         if sampler == "dpmpp":
             raise NotImplementedError('a constraint under sampler="dpmpp" is not built: its noise levels assume the uniform timestep grid')
@@ -1008,7 +1008,7 @@ class LDPAgent(_EngineCalls):
         'plan') and box bounds (lo, hi, bound_weight).  scale / schedule: the step sizes (guide.Guide.step_sizes); a step size beyond the
         descent bound is a ValueError before the planner loop is enqueued.  The planner loop has one launch more per step than sample()'s; the IDM
         loop, the plan assembly and the un-normalisation are sample()'s.  noise: optional dict(x_init, x_noise, a_init, a_noise) as in
-        sample_viz.  Not built (NotImplementedError): sampler="dpmpp".  The control quality of guided plans has not been evaluated."""
+        sample_viz.  Not built (NotImplementedError): sampler="dpmpp".  The control quality of guided plans has been measured on a toy task only."""
         from .guide import Guide, build_guide
         if sampler == "dpmpp":
             raise NotImplementedError('guidance under sampler="dpmpp" is not built: the guided step is the DDPM / DDIM scheduler step')
@@ -1093,7 +1093,7 @@ class LDPAgent(_EngineCalls):
         Where a guide meets a constraint, or either meets "dpmpp", every denoising step is the U-Net evaluation plus one composed launch
         (csrc/compose.hip): data prediction, guide, scheduler or solver update, constraint, in that order.  Every other combination runs
         the loop of the dedicated method and returns its bits.  Every refusal is raised before any GPU work.
-        The control quality of such plans has not been evaluated."""
+        The control quality of such plans has been measured on a toy task only."""
         from .constrain import MODES, build_constraint
         from .guide import Guide
         from .replan import check_warm_steps

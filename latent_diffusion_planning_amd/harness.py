@@ -402,6 +402,68 @@ def fit(agent, data_iter, n_steps: int, rng, log_every: int = 100, on_log: Optio
     return agent, metrics
 
 
+def _to_host(x) -> np.ndarray:
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+def run_device_eval(env, act, n_rollout: int, seed: int, eval_rng: int, on_reset: Optional[Callable] = None, episode0: int = 0) -> dict:
+    """Closed-loop evaluation on a device-resident task (toyenv.Reach2DEnv): the env's N environments run whole episodes
+    in lockstep, n_rollout / N rounds of them; round r holds the global episodes episode0 + r * N .. + N - 1 of `seed`.  A round is
+        env.reset -> on_reset() -> { batch = env.observe(); action = act(batch, rng, cycle); env.step(action) } until episode_len steps
+    where `act` is any callable that returns the actions (B, action_horizon, A) or a tuple that starts with them -- `agent.sample`'s
+    (action, metrics), a Replanner's / Controller's `.act` wrapped with its slots 0..N-1, `sample_best_of` -- as a device tensor or a
+    DeviceArray, whose tensor goes to env.step as it is: nothing reads the device inside an episode.  Call n (counted from 1 over all
+    rounds) gets rng = eval_rng * 1000003 + n, as in run_eval; `cycle` counts from 0 within the episode; on_reset stands for the
+    `reset()` of a Replanner / Controller.  The last cycle executes only the actions that fit into the episode.
+    After a round the state is read ONCE; then the fault protocol of the calls is honoured (every DeviceArray of the round completes): a
+    round in which a call faulted and was recomputed executed suspect actions and is run again, at most twice.
+    -> dict(success_rate, mean_first_success (steps, over the successes; nan without one), blocked_share (refused moves / moves),
+    ms_per_call (host wall time of a round / its control calls, the round's final wait included), n_rollout, n_calls, cycles_per_episode).
+    Runs on the host with a NumPy environment of the same interface (tests/toyenv_oracle.NumpyReach2DEnv)."""
+    N, H = int(env.n_envs), int(env.episode_len)
+    if int(n_rollout) < N or int(n_rollout) % N:
+        raise ValueError(f"n_rollout = {n_rollout} must be a positive multiple of the environment's {N} episodes per round")
+    first, blocked, wall = [], [], 0.0
+    n_calls = cycles = 0
+    for r in range(int(n_rollout) // N):
+        for attempt in range(3):
+            env.reset(seed, int(episode0) + r * N)
+            if on_reset is not None:
+                on_reset()
+            held, t, cycles = [], 0, 0
+            t0 = time.perf_counter()
+            while t < H:
+                batch = env.observe()
+                n_calls += 1
+                out = act(batch, (int(eval_rng) * 1000003 + n_calls) & 0x7FFFFFFFFFFFFFFF, cycles)
+                action = out[0] if isinstance(out, (tuple, list)) else out
+                a = action.tensor if hasattr(action, "complete") else action
+                if a.shape[1] > H - t:
+                    a = a[:, :H - t]
+                env.step(a)
+                if hasattr(action, "complete"):
+                    held.append((action, a))
+                t += int(a.shape[1])
+                cycles += 1
+            f, b = _to_host(env.first_success()), _to_host(env.blocked())         # the one read of the round: waits for the device
+            wall += time.perf_counter() - t0
+            suspect = False
+            for action, a in held:
+                action.complete()
+                suspect = suspect or action.tensor.data_ptr() != a.data_ptr()
+            if not suspect:
+                break
+        else:
+            raise RuntimeError("run_device_eval: a policy call faulted in three attempts at the same round")
+        first.append(f.astype(np.int64))
+        blocked.append(b.astype(np.int64))
+    first, blocked = np.concatenate(first), np.concatenate(blocked)
+    ok = first != 0
+    return dict(success_rate=float(ok.mean()), mean_first_success=float(first[ok].mean()) if ok.any() else float("nan"),
+                blocked_share=float(blocked.sum() / (blocked.size * H)), ms_per_call=1e3 * wall / max(n_calls, 1),
+                n_rollout=int(n_rollout), n_calls=n_calls, cycles_per_episode=cycles)
+
+
 def eval_vae_metrics(model, batches, rng, max_batches: int = 11) -> dict:
     """The evaluation loop of train_vae.py:146-157 on a StableVAEModel: `get_metrics` on up to `max_batches` held-out batches, the mean of
     every key over the batches, prefixed `evaldata/`.  `rng` seeds batch i with rng + i (the reference splits its key once per batch)."""

@@ -6,7 +6,8 @@ to an intermediate level, starts a loop that runs only the last `warm_steps` of 
 with Diffusion", 5.4).  `Replanner` keeps the previous full planner state of every environment in a device table and decides per row whether
 a call can be warm (`LDPAgent.replanner`); `LDPAgent.sample_warm` is the same computation for a caller who carries the state itself.
 
-Whether warm-started plans control as well as cold ones has NOT been evaluated: this module defines and tests the computation.
+Whether warm-started plans control as well as cold ones has been measured on a toy task only (tools/toy_reach.py): this
+module defines and tests the computation.
 """
 from __future__ import annotations
 
@@ -196,7 +197,7 @@ class Controller(Replanner):
     warm and cold group calls go through `agent_sample_composed`, which hands each group its rows of the guide and the constraint.  With
     neither, and under DDPM / DDIM, the results are Replanner's bit for bit.
 
-    Whether such plans control well has NOT been evaluated: there is no checkpoint and no simulator here."""
+    Whether such plans control well has been measured on a toy task only: there is no robot checkpoint and no robot simulator here."""
 
     def act(self, batch, eval_rng, slots, guide=None, decode: bool = False, **constraint_kw):
         """Replanner.act with `guide` (a guide.Guide for the B rows of this call, in the caller's row order; anchor=True: each row's own

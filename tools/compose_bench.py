@@ -10,7 +10,7 @@ For each batch size B it times, on one GPU and in ONE process,
 The calls are ALTERNATED: every repeat times one window of `--steps` calls of each, in turn, so drift of the clocks or of the box hits
 all alike.  Every call is waited for (host clock around enqueue + completion point); all shapes are warmed up (graphs captured) before the
 first window.  A figure is [median, min, max] ms per call over the `--repeats` windows.
-Prints ONE JSON line.  Not the driver's bench line (bench.py is).  Control quality is not evaluated: there is no checkpoint and no simulator.
+Prints ONE JSON line.  Not the driver's bench line (bench.py is).  Control quality is not evaluated here (tools/toy_reach.py measures it on a toy task).
 
   python tools/compose_bench.py"""
 import argparse
