@@ -367,7 +367,8 @@ LDP_API int ldp_agent_sample_constrained(ldp_handle* h, const float* obs_emb, in
  * not strictly decreasing, a last entry that is not 0.  Registering the same table again does nothing; a different table for an
  * n_steps that already has one replaces it and drops the captured graphs.
  *
- * The update of executed step i, ONE elementwise launch (csrc/solver.hip plan_solver_kernel), each operation rounded to fp32 once:
+ * The update of executed step i, ONE elementwise launch (csrc/compose.hip plan_compose_step_kernel<1, false, false>), each operation
+ * rounded to fp32 once:
  *   x0     = clamp(fma(-sg, eps, x) * inv_a, -1, 1)             (the scheduler's clip_sample)
  *   Dv     = second ? fma(w, x0 - x0_prev, x0) : x0
  *   x_out  = fma(c_x, x, c_D * Dv);    x0_out = x0
@@ -402,11 +403,11 @@ LDP_API int ldp_plan_solver_step(ldp_handle* h, const float* x, const float* eps
  *   x <- c_x0 y' + c_x x + c_eps eps + sigma z
  * eps is used as the network wrote it; z is the fused step's draw (LDP_PHILOX_STREAM_STEP, step i, element (row_offset * T + r) * padded
  * width + c) or the explicit step noise, so with rho = 0 the guided loop is the free loop up to rounding.  Every operation is rounded to
- * fp32 once, in the order csrc/guide.hip states.  With L = max wg + 4 max lam + max beta, rho[i] L <= 1 guarantees J(y') <= J(y); the
+ * fp32 once, in the order csrc/compose.hip states.  With L = max wg + 4 max lam + max beta, rho[i] L <= 1 guarantees J(y') <= J(y); the
  * library does not check this bound (guide.build_guide does).
  *
- * ldp_plan_guide_step: that step on caller memory, ONE launch (csrc/guide.hip plan_guide_step_kernel: a work-group owns whole samples,
- * the stencil goes through LDS).  All pointers are device memory: x, x_out (B, T, ldx) with ldx >= D (x_out may be x; columns beyond D
+ * ldp_plan_guide_step: that step on caller memory, ONE launch (csrc/compose.hip plan_compose_step_kernel<0, true, false>: a work-group
+ * owns whole samples, the stencil goes through LDS).  All pointers are device memory: x, x_out (B, T, ldx) with ldx >= D (x_out may be x; columns beyond D
  * are neither read nor written), eps and noise (B, T, D; noise NULL: the Philox draw of (seed, row_offset)), target, wg (B, T, ldg) and
  * anchor (B, ldg) or NULL with ldg >= D, lam, beta, lo, hi (D), rho (n_steps; entry `step` is read).  pred_horizon <= 16, obs_dim <= 128.
  * ldp_plan_guide_cost: out[r] = J of row r of x (rows, T, D) under guide row r / n_per (rows = B * n_per: n_per candidates per

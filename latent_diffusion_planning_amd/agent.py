@@ -203,6 +203,11 @@ def _Elem(vec, i):
     return _HostScalar(lambda: vec.numpy()[i])
 
 
+def _need_nets(agent, what: str) -> None:
+    if not (agent.use_planner and agent.use_idm):
+        raise NotImplementedError(f"{what}() needs both the planner and the IDM (use_planner / use_idm)")
+
+
 def _seed_of(rng) -> int:
     if rng is None:
         return 0
@@ -793,21 +798,55 @@ class LDPAgent(_EngineCalls):
         for e in self._engines():
             e.set_solver_timesteps(ts)
 
-    def _sample_core(self, batch, seed, noise, row_offset, sampler, n_steps, idm_steps):
-        """normalize -> vae_encode -> get_obs_cond -> ONE ldp_agent_sample (planner loop, plan assembly,
-        IDM loop, action un-normalisation as one captured graph).  -> (action, plan, x, obs_emb) tensors."""
-        self._sync_weights()
-        cfg = self.config
-        nb = self._postprocess(batch)
-        obs = self._vae_encode_t(nb["obs"])
-        obs_emb = self.get_obs_cond(obs).contiguous()
-        lo, hi, mode = self._action_bounds()
+    # ---- what sample_viz, sample_warm, sample_constrained, sample_guided and plan share -----------------------------------------
+    def _sample_setup(self, eval_rng, sampler, n_steps, idm_steps, noise):
+        """-> (idm_steps, kw): idm_steps with its default, and the keywords every engine call of these methods takes as they are --
+        the seed of eval_rng, sampler, idm_steps and the explicit-noise tensors of `noise` (None where it has none)."""
+        seed = _seed_of(eval_rng)
+        if idm_steps is None and n_steps is not None and sampler != "ddpm":
+            idm_steps = n_steps                                # one schedule for both loops unless told otherwise
         nz = noise or {}
-        x, plan, action = self._engine.agent_sample(
-            obs_emb, cfg["obs_horizon"], x_init=nz.get("x_init"), x_noise=nz.get("x_noise"),
-            a_init=nz.get("a_init"), a_noise=nz.get("a_noise"), seed=seed, row_offset=row_offset, sampler=sampler,
-            planner_steps=n_steps, idm_steps=idm_steps, action_bounds=(lo, hi), action_mode=mode)
-        return action, plan, x, obs_emb
+        kw = dict(seed=seed, sampler=sampler, idm_steps=idm_steps, x_init=nz.get("x_init"), x_noise=nz.get("x_noise"), a_init=nz.get("a_init"),
+                  a_noise=nz.get("a_noise"))
+        return idm_steps, kw
+
+    def _sample_call(self, batch, call, keys=(), prev=None, decode=False):
+        """One sampling call under the fault protocol -> (action, metrics): normalize -> vae_encode -> get_obs_cond -> ONE engine call
+        (planner loop, plan assembly, IDM loop, action un-normalisation as one captured graph) -> _plan_metrics.
+        call(obs_emb, bounds) makes the engine call -- bounds: its action_bounds / action_mode keywords -- and returns (x, plan, action)
+        and, behind them, the tensors of keys[1:].  keys: what metrics holds between 'plan' and 'plan_mse' ('x' first, when at all).
+        prev: a warm call's previous state (it may belong to the call that faulted: a recompute completes it first)."""
+        oh = self.config["obs_horizon"]
+
+        def run():
+            self._sync_weights()
+            obs_emb = self.get_obs_cond(self._vae_encode_t(self._postprocess(batch)["obs"])).contiguous()
+            lo, hi, mode = self._action_bounds()
+            x, plan, action, *more = call(obs_emb, dict(action_bounds=(lo, hi), action_mode=mode))
+            out = [action, plan] + ([x] if keys else []) + more
+            if obs_emb.shape[1] > oh:                          # from a training batch, not inference (:447-448)
+                out.append(self._engine.mean_sq_diff(x, obs_emb[:, oh:]))
+            return out
+
+        def recompute():
+            if isinstance(prev, DeviceArray):
+                prev.complete()                                # the previous call may be the one that faulted: its x first
+            return run() + [None]                              # plan_viz re-decodes itself from the new plan
+        res, rec = self._call(run, recompute)
+        return self._plan_metrics(res, rec, keys, decode)
+
+    def _plan_metrics(self, res, rec, keys, decode):
+        """res: the tensors [action, plan, *those named by keys, plan_mse when the batch has future frames] of a call recorded in rec
+        -> (action, metrics) as DeviceArrays (created in that order: a recompute swaps them by position), with metrics['plan_viz']
+        decoding itself from the plan when it is read (decode: enqueued now, no host sync)."""
+        action, plan, *rest = (DeviceArray(t, record=rec) for t in res)
+        metrics = {"plan": plan, **dict(zip(tuple(keys) + ("plan_mse",), rest))}
+        S = self._engine.image_size
+        viz = DeviceArray(thunk=lambda: self._vae_decode_t(plan.tensor), shape=tuple(plan.shape[:2]) + (3, S, S), record=rec)
+        if decode:
+            viz.tensor
+        metrics["plan_viz"] = viz
+        return action, metrics
 
     def sample_viz(self, batch, eval_rng, noise=None, decode=True, row_offset=0,
                    sampler="ddpm", n_steps=None, idm_steps=None, timesteps=None):
@@ -821,33 +860,14 @@ class LDPAgent(_EngineCalls):
         candidates are sharded over GPUs).  n_steps / idm_steps: denoising steps (DDIM and DPM-Solver++; DDPM
         visits every training timestep).  sampler="dpmpp": the planner loop is DPM-Solver++(2M) over the timestep
         table `timesteps` (None / "logsnr" / "uniform" / n_steps integers: _solver_setup), the IDM loop DDIM."""
-        if not (self.use_planner and self.use_idm):
-            raise NotImplementedError("sample() needs both the planner and the IDM (use_planner / use_idm)")
-        seed = _seed_of(eval_rng)
-        oh = self.config["obs_horizon"]
-        if idm_steps is None and n_steps is not None and sampler != "ddpm":
-            idm_steps = n_steps                                # one schedule for both loops unless told otherwise
+        _need_nets(self, "sample")
+        idm_steps, kw = self._sample_setup(eval_rng, sampler, n_steps, idm_steps, noise)
         self._solver_setup(sampler, n_steps, idm_steps, timesteps)
+        oh = self.config["obs_horizon"]
 
-        def run():
-            action, plan, x, obs_emb = self._sample_core(batch, seed, noise, row_offset, sampler, n_steps, idm_steps)
-            out = [action, plan]
-            if obs_emb.shape[1] > oh:                          # from a training batch, not inference (:447-448)
-                out.append(self._engine.mean_sq_diff(x, obs_emb[:, oh:]))
-            return out
-        res, rec = self._call(run, lambda: run() + [None])             # plan_viz re-decodes itself from the new plan
-        action = DeviceArray(res[0], record=rec)
-        plan = DeviceArray(res[1], record=rec)
-        metrics = {"plan": plan}
-        if len(res) > 2:
-            metrics["plan_mse"] = DeviceArray(res[2], record=rec)
-        S = self._engine.image_size
-        viz = DeviceArray(thunk=lambda: self._vae_decode_t(plan.tensor), shape=tuple(plan.shape[:2]) + (3, S, S),
-                          record=rec)
-        if decode:
-            viz.tensor                                         # enqueue the decode now (no host sync)
-        metrics["plan_viz"] = viz
-        return action, metrics
+        def call(obs_emb, bounds):
+            return self._engine.agent_sample(obs_emb, oh, row_offset=row_offset, planner_steps=n_steps, **kw, **bounds)
+        return self._sample_call(batch, call, decode=decode)
 
     # ---- warm-started replanning (defined by this repository: DESIGN.md 4.16; csrc/replan.hip, replan.py) ---------------------
     def sample_warm(self, batch, eval_rng, prev, warm_steps, shift=None, sampler="ddim", n_steps=None, idm_steps=None, noise=None,
@@ -863,63 +883,32 @@ class LDPAgent(_EngineCalls):
         from .replan import check_warm_steps
         if sampler == "dpmpp":
             raise NotImplementedError('a warm start under sampler="dpmpp" is not built: its noise levels assume the uniform timestep grid')
-        if not (self.use_planner and self.use_idm):
-            raise NotImplementedError("sample_warm() needs both the planner and the IDM (use_planner / use_idm)")
+        _need_nets(self, "sample_warm")
         if (prev is None) != (warm_steps is None):
             raise ValueError("prev and warm_steps go together: both None (a cold call that returns 'x') or both given")
-        seed = _seed_of(eval_rng)
+        idm_steps, kw = self._sample_setup(eval_rng, sampler, n_steps, idm_steps, noise)
         cfg = self.config
         oh = cfg["obs_horizon"]
         ns = int(cfg["planner_n_diffusion_steps"] if n_steps is None else n_steps)
-        if idm_steps is None and n_steps is not None and sampler != "ddpm":
-            idm_steps = n_steps                                # one schedule for both loops unless told otherwise
-        nz = dict(noise or {})
         if prev is None:
-            def core():
-                return self._sample_core(batch, seed, noise, row_offset, sampler, n_steps, idm_steps)
+            def call(obs_emb, bounds):
+                return self._engine.agent_sample(obs_emb, oh, row_offset=row_offset, planner_steps=n_steps, **kw, **bounds)
         else:
             step_begin = check_warm_steps(warm_steps, ns)
-            if "x_init" in nz:
+            if "x_init" in (noise or {}):
                 raise ValueError("a warm call has no x_init: its initial state is the shifted, noised previous plan")
             sh = int(cfg["action_horizon"] if shift is None else shift)
             if sh < 0:
                 raise ValueError(f"shift must be >= 0, got {shift}")
+            del kw["x_init"]                                   # (agent_resample takes none)
 
-            def core():
-                self._sync_weights()
-                obs_emb = self.get_obs_cond(self._vae_encode_t(self._postprocess(batch)["obs"])).contiguous()
-                lo, hi, mode = self._action_bounds()
+            def call(obs_emb, bounds):
                 store = self._t(prev).clone()                  # the engine writes the new state back in place: not into the caller's prev
                 if tuple(store.shape) != (obs_emb.shape[0], cfg["pred_horizon"], cfg["obs_dim"]):
                     raise ValueError(f"prev must have shape {(obs_emb.shape[0], cfg['pred_horizon'], cfg['obs_dim'])}, got {tuple(store.shape)}")
-                x, plan, action = self._engine.agent_resample(
-                    obs_emb, oh, store, step_begin, shift=sh, x_noise=nz.get("x_noise"), a_init=nz.get("a_init"),
-                    a_noise=nz.get("a_noise"), seed=seed, row_offset=row_offset, sampler=sampler, planner_steps=ns,
-                    idm_steps=idm_steps, action_bounds=(lo, hi), action_mode=mode)
-                return action, plan, x, obs_emb
-
-        def run():
-            action, plan, x, obs_emb = core()
-            out = [action, plan, x]
-            if obs_emb.shape[1] > oh:                          # from a training batch, not inference (:447-448)
-                out.append(self._engine.mean_sq_diff(x, obs_emb[:, oh:]))
-            return out
-
-        def recompute():
-            if isinstance(prev, DeviceArray):
-                prev.complete()                                # the previous call may be the one that faulted: its x first
-            return run() + [None]                              # plan_viz re-decodes itself from the new plan
-        res, rec = self._call(run, recompute)
-        action, plan, x = (DeviceArray(t, record=rec) for t in res[:3])
-        metrics = {"plan": plan, "x": x}
-        if len(res) > 3:
-            metrics["plan_mse"] = DeviceArray(res[3], record=rec)
-        S = self._engine.image_size
-        viz = DeviceArray(thunk=lambda: self._vae_decode_t(plan.tensor), shape=tuple(plan.shape[:2]) + (3, S, S), record=rec)
-        if decode:
-            viz.tensor
-        metrics["plan_viz"] = viz
-        return action, metrics
+                return self._engine.agent_resample(obs_emb, oh, store, step_begin, shift=sh, row_offset=row_offset, planner_steps=ns,
+                                                   **kw, **bounds)
+        return self._sample_call(batch, call, ("x",), prev=prev, decode=decode)
 
     def replanner(self, n_slots, warm_steps, sampler="ddim", n_steps=None, shift=None):
         """A Replanner (replan.py) for closed-loop control of up to n_slots environments: it keeps every environment's previous planner
@@ -947,44 +936,20 @@ class LDPAgent(_EngineCalls):
         from .constrain import MODES, build_constraint
         if sampler == "dpmpp":
             raise NotImplementedError('a constraint under sampler="dpmpp" is not built: its noise levels assume the uniform timestep grid')
-        if not (self.use_planner and self.use_idm):
-            raise NotImplementedError("sample_constrained() needs both the planner and the IDM (use_planner / use_idm)")
+        _need_nets(self, "sample_constrained")
         if mode not in MODES:
             raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
-        seed = _seed_of(eval_rng)
+        idm_steps, kw = self._sample_setup(eval_rng, sampler, n_steps, idm_steps, noise)
         cfg = self.config
-        oh = cfg["obs_horizon"]
-        if idm_steps is None and n_steps is not None and sampler != "ddpm":
-            idm_steps = n_steps                                # one schedule for both loops unless told otherwise
-        nz = dict(noise or {})
 
-        def run():
-            self._sync_weights()
-            obs_emb = self.get_obs_cond(self._vae_encode_t(self._postprocess(batch)["obs"])).contiguous()
+        def call(obs_emb, bounds):
             B = obs_emb.shape[0]
             g = None if goal is None else self._goal_embedding(goal, B)
             tg, mk = build_constraint(cfg, B, target=None if target is None else self._t(target), mask=mask, goal=g, t_goal=t_goal,
                                       goal_dims=goal_dims)
-            lo, hi, amode = self._action_bounds()
-            x, plan, action = self._engine.agent_sample_constrained(
-                obs_emb, oh, tg, mk, mode=mode, x_init=nz.get("x_init"), x_noise=nz.get("x_noise"), a_init=nz.get("a_init"),
-                a_noise=nz.get("a_noise"), seed=seed, row_offset=row_offset, sampler=sampler, planner_steps=n_steps, idm_steps=idm_steps,
-                action_bounds=(lo, hi), action_mode=amode)
-            out = [action, plan, x]
-            if obs_emb.shape[1] > oh:                          # from a training batch, not inference (:447-448)
-                out.append(self._engine.mean_sq_diff(x, obs_emb[:, oh:]))
-            return out
-        res, rec = self._call(run, lambda: run() + [None])             # plan_viz re-decodes itself from the new plan
-        action, plan, x = (DeviceArray(t, record=rec) for t in res[:3])
-        metrics = {"plan": plan, "x": x}
-        if len(res) > 3:
-            metrics["plan_mse"] = DeviceArray(res[3], record=rec)
-        S = self._engine.image_size
-        viz = DeviceArray(thunk=lambda: self._vae_decode_t(plan.tensor), shape=tuple(plan.shape[:2]) + (3, S, S), record=rec)
-        if decode:
-            viz.tensor
-        metrics["plan_viz"] = viz
-        return action, metrics
+            return self._engine.agent_sample_constrained(obs_emb, cfg["obs_horizon"], tg, mk, mode=mode, row_offset=row_offset,
+                                                         planner_steps=n_steps, **kw, **bounds)
+        return self._sample_call(batch, call, ("x",), decode=decode)
 
     # ---- guided planning (defined by this repository: DESIGN.md 4.19; csrc/guide.hip, guide.py) --------------------------------
     def build_guide(self, B, **kw):
@@ -1012,8 +977,7 @@ class LDPAgent(_EngineCalls):
         from .guide import Guide, build_guide
         if sampler == "dpmpp":
             raise NotImplementedError('guidance under sampler="dpmpp" is not built: the guided step is the DDPM / DDIM scheduler step')
-        if not (self.use_planner and self.use_idm):
-            raise NotImplementedError("sample_guided() needs both the planner and the IDM (use_planner / use_idm)")
+        _need_nets(self, "sample_guided")
         built = dict(target=target, weight=weight, goal=goal, t_goal=t_goal, goal_dims=goal_dims, goal_weight=goal_weight, smooth=smooth,
                      anchor=anchor, lo=lo, hi=hi, bound_weight=bound_weight, scale=scale)
         if guide is not None:
@@ -1022,18 +986,13 @@ class LDPAgent(_EngineCalls):
                 raise ValueError(f"guide= already holds the cost and its step sizes: {', '.join(given)} cannot be given with it")
             if not isinstance(guide, Guide):
                 raise ValueError(f"guide must be a guide.Guide (guide.build_guide / LDPAgent.build_guide), got {type(guide).__name__}")
-        seed = _seed_of(eval_rng)
+        idm_steps, kw = self._sample_setup(eval_rng, sampler, n_steps, idm_steps, noise)
         cfg = self.config
         oh = cfg["obs_horizon"]
         ns = int(cfg["planner_n_diffusion_steps"] if n_steps is None else n_steps)
-        if idm_steps is None and n_steps is not None and sampler != "ddpm":
-            idm_steps = n_steps                                # one schedule for both loops unless told otherwise
-        nz = dict(noise or {})
         rho = None if guide is None else guide.step_sizes(ns, sampler)      # (a given guide: every host check before any GPU work)
 
-        def run():
-            self._sync_weights()
-            obs_emb = self.get_obs_cond(self._vae_encode_t(self._postprocess(batch)["obs"])).contiguous()
+        def call(obs_emb, bounds):
             B = obs_emb.shape[0]
             gd, rh = guide, rho
             if gd is None:
@@ -1042,31 +1001,21 @@ class LDPAgent(_EngineCalls):
                                                 anchor=anchor if anchor is None or anchor is True else self._t(anchor)),
                                  schedule=schedule, engine=self._engine)
                 rh = gd.step_sizes(ns, sampler)
-            if gd.B != B:
-                raise ValueError(f"the guide was built for B = {gd.B} plans, the batch holds {B}")
-            if gd.anchor is True:                              # this batch's own current observation: a copy of the guide, not the caller's
-                gd = Guide(gd.cfg, gd.B, gd.target, gd.weight, obs_emb[:, oh - 1].contiguous(), gd.lam, gd.beta, gd.lo, gd.hi, gd.scale,
-                           gd.schedule, self._engine, gd.wmax)
-            lo_a, hi_a, amode = self._action_bounds()
-            x, plan, action = self._engine.agent_sample_guided(
-                obs_emb, oh, gd, rh, x_init=nz.get("x_init"), x_noise=nz.get("x_noise"), a_init=nz.get("a_init"), a_noise=nz.get("a_noise"),
-                seed=seed, row_offset=row_offset, sampler=sampler, planner_steps=n_steps, idm_steps=idm_steps, action_bounds=(lo_a, hi_a),
-                action_mode=amode)
-            out = [action, plan, x, self._engine.plan_guide_cost(x, gd)]
-            if obs_emb.shape[1] > oh:                          # from a training batch, not inference (:447-448)
-                out.append(self._engine.mean_sq_diff(x, obs_emb[:, oh:]))
-            return out
-        res, rec = self._call(run, lambda: run() + [None])             # plan_viz re-decodes itself from the new plan
-        action, plan, x, cost = (DeviceArray(t, record=rec) for t in res[:4])
-        metrics = {"plan": plan, "x": x, "guide_cost": cost}
-        if len(res) > 4:
-            metrics["plan_mse"] = DeviceArray(res[4], record=rec)
-        S = self._engine.image_size
-        viz = DeviceArray(thunk=lambda: self._vae_decode_t(plan.tensor), shape=tuple(plan.shape[:2]) + (3, S, S), record=rec)
-        if decode:
-            viz.tensor
-        metrics["plan_viz"] = viz
-        return action, metrics
+            gd = self._batch_guide(gd, obs_emb)
+            x, plan, action = self._engine.agent_sample_guided(obs_emb, oh, gd, rh, row_offset=row_offset, planner_steps=n_steps, **kw, **bounds)
+            return x, plan, action, self._engine.plan_guide_cost(x, gd)
+        return self._sample_call(batch, call, ("x", "guide_cost"), decode=decode)
+
+    def _batch_guide(self, gd, obs_emb):
+        """`gd` as the engine takes it for this batch: its B checked, anchor=True resolved to the batch's own current observation (in a
+        copy of the guide, not the caller's)."""
+        from .guide import Guide
+        if gd.B != obs_emb.shape[0]:
+            raise ValueError(f"the guide was built for B = {gd.B} plans, the batch holds {obs_emb.shape[0]}")
+        if gd.anchor is True:
+            gd = Guide(gd.cfg, gd.B, gd.target, gd.weight, obs_emb[:, self.config["obs_horizon"] - 1].contiguous(), gd.lam, gd.beta, gd.lo,
+                       gd.hi, gd.scale, gd.schedule, self._engine, gd.wmax)
+        return gd
 
     # ---- composed planning (defined by this repository: DESIGN.md 4.20; csrc/compose.hip) -----------------------------------
     def _guide_step_sizes(self, guide, sampler, n_steps):
@@ -1090,15 +1039,14 @@ class LDPAgent(_EngineCalls):
         guide: a guide.Guide (LDPAgent.build_guide).  target / mask / goal / t_goal / goal_dims / mode: sample_constrained's constraint.
         prev / warm_steps / shift: sample_warm's warm start.  sampler "dpmpp" runs over the timestep table `timesteps` (sample_viz); the
         guide's "sigma2" step sizes and the constraint's noise levels are then taken at the entries of that table.
-        Where a guide meets a constraint, or either meets "dpmpp", every denoising step is the U-Net evaluation plus one composed launch
-        (csrc/compose.hip): data prediction, guide, scheduler or solver update, constraint, in that order.  Every other combination runs
-        the loop of the dedicated method and returns its bits.  Every refusal is raised before any GPU work.
+        With a guide, or under "dpmpp", every denoising step is the U-Net evaluation plus one launch of the step kernel
+        (csrc/compose.hip): data prediction, guide, scheduler or solver update, constraint, in that order.  A combination that a
+        dedicated method also serves runs that method's loop and returns its bits.  Every refusal is raised before any GPU work.
         The control quality of such plans has been measured on a toy task only."""
         from .constrain import MODES, build_constraint
         from .guide import Guide
         from .replan import check_warm_steps
-        if not (self.use_planner and self.use_idm):
-            raise NotImplementedError("plan() needs both the planner and the IDM (use_planner / use_idm)")
+        _need_nets(self, "plan")
         if mode not in MODES:
             raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
         if guide is not None and not isinstance(guide, Guide):
@@ -1109,17 +1057,13 @@ class LDPAgent(_EngineCalls):
             raise ValueError("target and mask go together: give both or neither")
         if goal is None and (t_goal is not None or goal_dims is not None):
             raise ValueError("t_goal and goal_dims describe `goal`: give goal too")
-        seed = _seed_of(eval_rng)
+        idm_steps, kw = self._sample_setup(eval_rng, sampler, n_steps, idm_steps, noise)
         cfg = self.config
-        oh = cfg["obs_horizon"]
         ns = int(cfg["planner_n_diffusion_steps"] if n_steps is None else n_steps)
-        if idm_steps is None and n_steps is not None and sampler != "ddpm":
-            idm_steps = n_steps                                # one schedule for both loops unless told otherwise
-        nz = dict(noise or {})
         step_begin, sh = 0, None
         if prev is not None:
             step_begin = check_warm_steps(warm_steps, ns)
-            if "x_init" in nz:
+            if "x_init" in (noise or {}):
                 raise ValueError("a warm call has no x_init: its initial state is the shifted, noised previous plan")
             sh = int(cfg["action_horizon"] if shift is None else shift)
             if sh < 0:
@@ -1130,17 +1074,9 @@ class LDPAgent(_EngineCalls):
         rho = None if guide is None else self._guide_step_sizes(guide, sampler, ns)
         constrained = target is not None or goal is not None
 
-        def run():
-            self._sync_weights()
-            obs_emb = self.get_obs_cond(self._vae_encode_t(self._postprocess(batch)["obs"])).contiguous()
+        def call(obs_emb, bounds):
             B = obs_emb.shape[0]
-            gd = guide
-            if gd is not None:
-                if gd.B != B:
-                    raise ValueError(f"the guide was built for B = {gd.B} plans, the batch holds {B}")
-                if gd.anchor is True:                          # this batch's own current observation: a copy of the guide, not the caller's
-                    gd = Guide(gd.cfg, gd.B, gd.target, gd.weight, obs_emb[:, oh - 1].contiguous(), gd.lam, gd.beta, gd.lo, gd.hi, gd.scale,
-                               gd.schedule, self._engine, gd.wmax)
+            gd = None if guide is None else self._batch_guide(guide, obs_emb)
             tg = mk = None
             if constrained:
                 g = None if goal is None else self._goal_embedding(goal, B)
@@ -1151,36 +1087,11 @@ class LDPAgent(_EngineCalls):
                 store = self._t(prev).clone()                  # the engine writes the new state back in place: not into the caller's prev
                 if tuple(store.shape) != (B, cfg["pred_horizon"], cfg["obs_dim"]):
                     raise ValueError(f"prev must have shape {(B, cfg['pred_horizon'], cfg['obs_dim'])}, got {tuple(store.shape)}")
-            lo_a, hi_a, amode = self._action_bounds()
-            x, plan, action = self._engine.agent_sample_composed(
-                obs_emb, oh, guide=gd, rho=rho, target=tg, mask=mk, mode=mode, x_store=store, shift=sh, step_begin=step_begin,
-                x_init=nz.get("x_init"), x_noise=nz.get("x_noise"), a_init=nz.get("a_init"), a_noise=nz.get("a_noise"), seed=seed,
-                row_offset=row_offset, sampler=sampler, planner_steps=ns, idm_steps=idm_steps, action_bounds=(lo_a, hi_a), action_mode=amode)
-            out = [action, plan, x]
-            if gd is not None:
-                out.append(self._engine.plan_guide_cost(x, gd))
-            if obs_emb.shape[1] > oh:                          # from a training batch, not inference (:447-448)
-                out.append(self._engine.mean_sq_diff(x, obs_emb[:, oh:]))
-            return out
-
-        def recompute():
-            if isinstance(prev, DeviceArray):
-                prev.complete()                                # the previous call may be the one that faulted: its x first
-            return run() + [None]                              # plan_viz re-decodes itself from the new plan
-        res, rec = self._call(run, recompute)
-        action, plan, x = (DeviceArray(t, record=rec) for t in res[:3])
-        metrics = {"plan": plan, "x": x}
-        rest = list(res[3:])
-        if guide is not None:
-            metrics["guide_cost"] = DeviceArray(rest.pop(0), record=rec)
-        if rest:
-            metrics["plan_mse"] = DeviceArray(rest[0], record=rec)
-        S = self._engine.image_size
-        viz = DeviceArray(thunk=lambda: self._vae_decode_t(plan.tensor), shape=tuple(plan.shape[:2]) + (3, S, S), record=rec)
-        if decode:
-            viz.tensor
-        metrics["plan_viz"] = viz
-        return action, metrics
+            res = self._engine.agent_sample_composed(
+                obs_emb, cfg["obs_horizon"], guide=gd, rho=rho, target=tg, mask=mk, mode=mode, x_store=store, shift=sh, step_begin=step_begin,
+                row_offset=row_offset, planner_steps=ns, **kw, **bounds)
+            return res if gd is None else (*res, self._engine.plan_guide_cost(res[0], gd))
+        return self._sample_call(batch, call, ("x",) if guide is None else ("x", "guide_cost"), prev=prev, decode=decode)
 
     def controller(self, n_slots, warm_steps, sampler="ddim", n_steps=None, timesteps=None, shift=None):
         """A Controller (replan.py) for closed-loop control of up to n_slots environments: a Replanner whose act() also takes a guide and

@@ -1,7 +1,8 @@
-// compose.hip -- the composed planner step (include/ldp_hip.h "composed planning"): ONE launch behind every U-Net
-// evaluation that does what guide.hip, solver.hip and constrain.hip do in a launch each -- the clipped data prediction, the guide's
-// projected gradient step on it, the scheduler (DDPM / DDIM) or solver (DPM-Solver++(2M)) update, and the constraint overwrite at the
-// next level.  Here: the kernel, its launch on the loop state from the buffers guide_stage / constrain_stage filled, the table-level
+// compose.hip -- the planner's step kernel (include/ldp_hip.h "composed planning"): ONE launch behind every U-Net
+// evaluation of a stepped loop (a guide, or sampler 2) -- the clipped data prediction, the guide's projected gradient step on it, the
+// scheduler (DDPM / DDIM) or solver (DPM-Solver++(2M)) update, and the constraint overwrite at the next level; each part a template
+// switch.  The guided step of guide.hip's entry point is <0, true, false>, the solver update of solver.hip's is <1, false, false>.
+// Here: the kernel, its launch on the loop state from the buffers guide_stage / constrain_stage filled, the table-level
 // constraint in front of a solver loop, and the stand-alone entry point.  The sampling entry points are engine.hip's.
 // Exact fp32 on the VALU; with a guide a work-group owns whole samples (the stencil along T goes through LDS), without one the launch is
 // plain elementwise; no atomics, vector stores only.
@@ -17,24 +18,7 @@ namespace ldp {
 namespace {
 
 constexpr unsigned COMPOSE_MAX_BLOCKS = 2048;     // 8 work-groups of 256 threads per CU on 256 CUs: the rest is strided
-constexpr int COMPOSE_MAX_T = 16, COMPOSE_MAX_D = 128;      // (guide.hip's limits: P.gcol is laid out in 128-float columns)
-constexpr int COMPOSE_LDS_FLOATS = COMPOSE_MAX_T * COMPOSE_MAX_D;      // 8 KB: one sample's clipped data prediction
-
-// Everything one composed step reads, by value.  Pointers are device memory.
-//   x / x_out (B, T, ldx), h_prev / h_out (B, T, ldx: the solver's history, SAMPLER 1 only), eps / noise (B, T, D),
-//   g_target / g_wg (B, T, ldg), g_anchor (B, ldg) or nullptr, lam / beta / lo / hi (D), rho (entry `step` is read),
-//   c_target (B, T, ldc) float, c_mask (B, T, ldc) bytes.
-// Coefficients: s / inv_a of the data prediction; SAMPLER 0: c_y = c_x0, c_x, c_eps, sigma; SAMPLER 1: c_y = c_D, c_x, w.
-// (ca, cs): the constraint's level coefficients of level step + 1; c_noise: repaint and that level is not the last.
-struct ComposeArgs {
-  const float* x; float* x_out; const float* eps; const float* noise; const float* h_prev; float* h_out;
-  const float* g_target; const float* g_wg; const float* g_anchor; const float* lam; const float* beta; const float* lo; const float* hi;
-  const float* rho;
-  const float* c_target; const uint8_t* c_mask;
-  const uint64_t* ctl; uint64_t seed, row0;
-  int ldx, ldg, ldc, B, T, D, DP, step, second, c_noise;
-  float s, inv_a, c_y, c_x, c_eps, sigma, w, ca, cs;
-};
+constexpr int COMPOSE_LDS_FLOATS = PLAN_MAX_T * PLAN_MAX_D;      // 8 KB: one sample's clipped data prediction
 
 __device__ __forceinline__ void load4(const float* p, size_t base, int c0, int D, bool vec, float (&v)[4]) {
   if (vec) {
@@ -100,7 +84,7 @@ __device__ __forceinline__ float compose_update(const ComposeArgs& A, float yg, 
 //              dn = t < T-1 ? rn(y - y_next) : 0;   dp = t > 0 ? rn(y - y_prev) : anchor ? rn(y - anchor) : 0
 //              g  = rn(fma(lam, rn(dn + dp), g))
 //              g  = rn(fma(beta, rn(max(rn(y - hi), 0) - max(rn(lo - y), 0)), g))
-//              y' = clamp(rn(fma(-r, g, y)), -1, 1)                    (plan_guide_step_kernel's g);    else y' = y
+//              y' = clamp(rn(fma(-r, g, y)), -1, 1);    else y' = y
 //   3  SAMPLER 0 (DDPM / DDIM):      x' = rn(fma(c_eps, eps, rn(fma(c_x, x, rn(c_y * y')))));   sigma != 0:  x' = rn(fma(sigma, z, x'))
 //      SAMPLER 1 (DPM-Solver++ 2M):  Dv = second ? rn(fma(w, rn(y' - h_prev), y')) : y';   x' = rn(fma(c_x, x, rn(c_y * Dv)));   h_out = y'
 //   4  CONSTRAIN, where mask != 0:   x' = c_noise ? fma(ca, target, rn(cs * z_c)) : target
@@ -231,10 +215,10 @@ void compose_launch_v(const ComposeArgs& A, bool vx, bool vg, bool ve, dim3 grid
   else hipLaunchKernelGGL((plan_compose_step_kernel<SAMPLER, GUIDE, CONSTRAIN, false, false, false>), grid, block, 0, st, A);
 }
 
-// solver: SAMPLER 1; guide / constrain: which parts A carries
+}  // namespace
+
 int plan_compose_launch(const ComposeArgs& A, bool solver, bool guide, bool constrain, hipStream_t st) {
-  if (guide && (A.T < 1 || A.T > COMPOSE_MAX_T || A.D < 1 || A.D > COMPOSE_MAX_D))
-    return fail(LDP_EINVAL, "the guide kernels serve pred_horizon <= %d and obs_dim <= %d, got %d and %d", COMPOSE_MAX_T, COMPOSE_MAX_D, A.T, A.D);
+  if (guide) LDP_TRY(check_guide_shape(A.T, A.D));
   const int64_t groups = (int64_t)A.B * A.T * ((A.D + 3) / 4);
   const dim3 grid(guide ? (unsigned)std::min<int64_t>(A.B, COMPOSE_MAX_BLOCKS)
                         : (unsigned)std::min<int64_t>((groups + 255) / 256, COMPOSE_MAX_BLOCKS));
@@ -265,8 +249,6 @@ void set_solver_coefs(ComposeArgs& A, const SolverCoef& k) {
   A.s = k.sg; A.inv_a = k.inv_a; A.c_y = k.c_D; A.c_x = k.c_x; A.c_eps = 0.0f; A.sigma = 0.0f; A.w = k.w;
 }
 
-}  // namespace
-
 int compose_level_coefs(const ldp_handle* h, int sampler, int n_steps, int level, float* a, float* s) {
   if (sampler != LDP_SAMPLER_DPMPP) return level_coefs(h->cfg.planner_train_steps, n_steps, level, a, s);
   const SolverTable* tab = solver_table(h, n_steps);
@@ -295,7 +277,7 @@ int planner_compose_step(ldp_handle* h, int Bg, const LoopSpec& L, const StepCoe
   if (L.guide) {
     const float* col = P.gcol.f();
     A.g_target = P.gtarget.f(); A.g_wg = P.gwg.f(); A.g_anchor = L.guide == LDP_GUIDE_ANCHOR ? P.ganchor.f() : nullptr;
-    A.lam = col; A.beta = col + COMPOSE_MAX_D; A.lo = col + 2 * COMPOSE_MAX_D; A.hi = col + 3 * COMPOSE_MAX_D; A.rho = col + 4 * COMPOSE_MAX_D;
+    A.lam = col; A.beta = col + PLAN_MAX_D; A.lo = col + 2 * PLAN_MAX_D; A.hi = col + 3 * PLAN_MAX_D; A.rho = col + 4 * PLAN_MAX_D;
   }
   if (L.constrain) {
     A.c_target = P.ctarget.f(); A.c_mask = P.cmask.as<uint8_t>();

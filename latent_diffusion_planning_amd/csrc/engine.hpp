@@ -87,8 +87,7 @@ struct GraphKey {
   int n_steps2 = 0, noise_mode2 = 0;              // joint graph: the IDM loop's step count / noise mode
   int begin = 0, end = -1;                        // planner loops (kind 0, 2): the executed steps [begin, end) of n_steps; (0, -1) = no planner range (the IDM loop, kind 1)
   int constrain = 0;                              // planner loops: 0 = the free loop, else the LDP_CONSTRAIN_* mode whose launches the graph carries (constrain.hip)
-  int guide = 0;                                  // planner loops: 0 = no guide, else LDP_GUIDE_ON / LDP_GUIDE_ANCHOR: the guided loop's launches (guide.hip)
-  int composed = 0;                               // planner loops: 1 = the composed loop (compose.hip): one composed step behind every U-Net evaluation
+  int guide = 0;                                  // planner loops: 0 = no guide, else LDP_GUIDE_ON / LDP_GUIDE_ANCHOR: the guide the stepped loop's launches carry
   bool operator<(const GraphKey& o) const {
     if (kind != o.kind) return kind < o.kind;
     if (B != o.B) return B < o.B;
@@ -100,8 +99,7 @@ struct GraphKey {
     if (begin != o.begin) return begin < o.begin;
     if (end != o.end) return end < o.end;
     if (constrain != o.constrain) return constrain < o.constrain;
-    if (guide != o.guide) return guide < o.guide;
-    return composed < o.composed;
+    return guide < o.guide;
   }
 };
 
@@ -283,13 +281,15 @@ inline int bucket_rows(int B, bool explicit_noise) { return explicit_noise ? B :
 // loop is (0, n_steps)).  Step i is the same step whatever the range: coefficients, timestep, noise row, Philox key and exchange tag
 // all carry i itself.  idm_loop always runs all n_steps and does not read them.  The default end = -1 is no range: planner_loop refuses
 // it (LDP_EINVAL), so a planner caller that forgets the two fields fails loudly instead of running zero steps.
-// constrain: 0, or the LDP_CONSTRAIN_* mode of a constrained loop (constrain.hip): C_begin in front of the first step and C_{i+1} behind
-// step i, on the target / mask staged into P.ctarget / P.cmask.
-// guide: 0, or LDP_GUIDE_ON / LDP_GUIDE_ANCHOR for a guided loop (guide.hip): the U-Net writes eps only and the guided step behind it
-// updates the state, on the guide staged into P.gtarget / P.gwg / P.ganchor / P.gcol (ANCHOR: with the continuity term).
-// composed: the composed loop (compose.hip): `constrain` and `guide` keep their meaning, C_begin runs once in front and ONE composed step
-// behind every U-Net evaluation does the rest.  Set by the composed entry points where a guide meets a constraint, or either meets sampler 2.
-struct LoopSpec { int n_steps = 0, sampler = 0; bool explicit_noise = false; int begin = 0, end = -1; int constrain = 0; int guide = 0; bool composed = false; };
+// constrain: 0, or the LDP_CONSTRAIN_* mode: C_begin in front of the first step and C_{i+1} behind step i, on the target / mask staged
+// into P.ctarget / P.cmask.
+// guide: 0, or LDP_GUIDE_ON / LDP_GUIDE_ANCHOR: the guide staged into P.gtarget / P.gwg / P.ganchor / P.gcol (ANCHOR: with the continuity term).
+// planner_loop has two shapes, chosen by (sampler, guide) alone (stepped_loop):
+//   fused    DDPM / DDIM without a guide: the U-Net's last launch does the scheduler step; a constraint is a launch of its own (constrain.hip)
+//   stepped  a guide, or sampler 2: the U-Net writes eps only and ONE plan_compose_step_kernel launch behind it (compose.hip) does the guided
+//            data prediction, the scheduler or solver update and C_{i+1}; C_begin runs once in front
+struct LoopSpec { int n_steps = 0, sampler = 0; bool explicit_noise = false; int begin = 0, end = -1; int constrain = 0; int guide = 0; };
+inline bool stepped_loop(const LoopSpec& L) { return L.guide != 0 || L.sampler == LDP_SAMPLER_DPMPP; }
 constexpr int LDP_GUIDE_ON = 1, LDP_GUIDE_ANCHOR = 2;
 int check_step_range(int begin, int end, int n_steps, const char* what);
 struct WarmSpec;                                 // a warm start of the planner state (below)
@@ -357,14 +357,8 @@ int planner_constrain_level(ldp_handle* h, int Bg, const LoopSpec& L, int level,
 // ---- DPM-Solver++(2M) sampler (solver.hip) -------------------------------------------------------------------
 const SolverTable* solver_table(const ldp_handle* h, int n_steps);      // the table registered for n_steps, or nullptr
 void make_solver_coefs(int n_train, const std::vector<int32_t>& ts, std::vector<SolverCoef>& out);
-// x0 = clamp(fma(-sg, eps, x) * inv_a, -1, 1); Dv = second ? fma(w, x0 - x0_prev, x0) : x0; x_out = fma(c_x, x, c_D * Dv); x0_out = x0 over the
-// columns c < D of `rows` rows; row strides ldx (x, x_out), ldh (x0_prev, x0_out), lde (eps).  x_out may be x, x0_out may be x0_prev.
-int plan_solver_launch(const float* x, const float* eps, const float* x0_prev, float* x_out, float* x0_out, int ldx, int ldh, int lde,
-                       int64_t rows, int D, const SolverCoef& k, bool second, hipStream_t st);
 // P.solver_eps / P.solver_x0 for Bg rows (they grow with the workspace and drop the captured graphs when they move)
 int solver_workspace(ldp_handle* h, int Bg);
-// the update of step i on the loop state, eps read from P.solver_eps, history in P.solver_x0: one launch, counted in last_total_launches
-int planner_solver_step(ldp_handle* h, int Bg, const SolverTable& tab, int i, bool second, hipStream_t q);
 // ---- guided planning (guide.hip) ----------------------------------------------------------------------------
 // A call's guide as the sampling entry points receive it: target, wg (B, T, D) and anchor (B, D; nullptr: no continuity term) in device
 // memory, lam, beta, lo, hi (D) and rho (n_rho) on the host.
@@ -378,14 +372,35 @@ int check_guide(const GuideSpec* g, int D, int n_steps, int sampler);
 // the guide into the handle's buffers, padded like the loop state (eager: pad launches and one host copy; the buffers grow with the
 // workspace and drop the captured graphs when they move)
 int guide_stage(ldp_handle* h, const GuideSpec& g, int B, int Bg, hipStream_t st);
-// the guided step i on the loop state, eps read from P.solver_eps, explicit noise (B, T, D) or nullptr: one launch, counted
-int planner_guide_step(ldp_handle* h, int Bg, const LoopSpec& L, const StepCoef& k, const float* noise, int i, hipStream_t q);
+// what the guide kernels and the staged column block P.gcol are laid out for: one sample's data prediction in 8 KB of LDS, [lam | beta |
+// lo | hi] at PLAN_MAX_D floats each, then up to PLAN_MAX_STEPS step sizes (check_sampler: a loop has at most 4094 steps)
+constexpr int PLAN_MAX_T = 16, PLAN_MAX_D = 128, PLAN_MAX_STEPS = 4096;
+int check_guide_shape(int T, int D);            // LDP_EINVAL unless 1 <= T <= PLAN_MAX_T and 1 <= D <= PLAN_MAX_D
 // ---- composed planning (compose.hip) ------------------------------------------------------------------------
+// Everything one launch of plan_compose_step_kernel reads, by value.  Pointers are device memory.
+//   x / x_out (B, T, ldx), h_prev / h_out (B, T, ldx: the solver's history, SAMPLER 1 only), eps / noise (B, T, D),
+//   g_target / g_wg (B, T, ldg), g_anchor (B, ldg) or nullptr, lam / beta / lo / hi (D), rho (entry `step` is read),
+//   c_target (B, T, ldc) float, c_mask (B, T, ldc) bytes.
+// Coefficients: s / inv_a of the data prediction; SAMPLER 0: c_y = c_x0, c_x, c_eps, sigma; SAMPLER 1: c_y = c_D, c_x, w.
+// (ca, cs): the constraint's level coefficients of level step + 1; c_noise: repaint and that level is not the last.
+struct ComposeArgs {
+  const float* x; float* x_out; const float* eps; const float* noise; const float* h_prev; float* h_out;
+  const float* g_target; const float* g_wg; const float* g_anchor; const float* lam; const float* beta; const float* lo; const float* hi;
+  const float* rho;
+  const float* c_target; const uint8_t* c_mask;
+  const uint64_t* ctl; uint64_t seed, row0;
+  int ldx, ldg, ldc, B, T, D, DP, step, second, c_noise;
+  float s, inv_a, c_y, c_x, c_eps, sigma, w, ca, cs;
+};
+void set_scheduler_coefs(ComposeArgs& A, const StepCoef& k);      // a DDPM / DDIM step's row into A
+void set_solver_coefs(ComposeArgs& A, const SolverCoef& k);       // a sampler-2 step's row into A
+// one launch of the step kernel.  solver: SAMPLER 1; guide / constrain: which parts A carries (a guide: check_guide_shape first)
+int plan_compose_launch(const ComposeArgs& A, bool solver, bool guide, bool constrain, hipStream_t st);
 // (a, s) of constraint level `level` under `sampler`: level_coefs on the uniform grid, table_level_coefs of the registered table under sampler 2
 int compose_level_coefs(const ldp_handle* h, int sampler, int n_steps, int level, float* a, float* s);
-// C_level on the loop state in front of a composed loop: planner_constrain_level, or its table-level counterpart under sampler 2; one launch, counted
+// C_level on the loop state in front of a stepped loop: planner_constrain_level, or its table-level counterpart under sampler 2; one launch, counted
 int planner_constrain_begin(ldp_handle* h, int Bg, const LoopSpec& L, int level, hipStream_t q);
-// the composed step i on the loop state: eps from P.solver_eps, the guide / constraint from the staged buffers as L names them, the
+// step i of a stepped loop on the loop state: eps from P.solver_eps, the guide / constraint from the staged buffers as L names them, the
 // history in P.solver_x0; k (DDPM / DDIM) or ks (sampler 2) is the step's coefficient row; one launch, counted
 int planner_compose_step(ldp_handle* h, int Bg, const LoopSpec& L, const StepCoef* k, const SolverCoef* ks, const float* noise, int i,
                          bool second, hipStream_t q);

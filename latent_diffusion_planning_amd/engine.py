@@ -7,6 +7,7 @@ arithmetic of the hot path all happens inside the C-ABI calls.  Every method enq
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -29,6 +30,14 @@ def _f32(t, device) -> torch.Tensor:
     if not torch.is_tensor(t):
         t = torch.as_tensor(np.asarray(t, dtype=np.float32))
     return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _opt_f32(t, device) -> Optional[torch.Tensor]:
+    return None if t is None else _f32(t, device)
+
+
+def _u64(seed: int):
+    return C.c_uint64(seed & (2**64 - 1))
 
 
 def _want(name: str, t: Optional[torch.Tensor], shape) -> None:
@@ -331,23 +340,66 @@ class HipEngine:
                                             self._stream()))
         return x_out, x0_out
 
+    def _plan_io(self, cond, B, x_init, step_noise, n_steps, step_end=None):
+        """What every plan_sample* method marshals: cond (B, G), x_init (B, T, D) and step_noise (n_steps, B, T, D) as float32 device
+        tensors (None stays None) with their shapes checked, B inferred from cond or x_init, the n_steps / step_end defaults and the
+        (B, T, D) output -> (cond, x_init, step_noise, B, n_steps, step_end, out)."""
+        cond_t = _opt_f32(cond, self.device)
+        if B is None:
+            B = cond_t.shape[0] if cond_t is not None else x_init.shape[0]
+        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
+        step_end = n_steps if step_end is None else int(step_end)
+        xi, nz = _opt_f32(x_init, self.device), _opt_f32(step_noise, self.device)
+        _want("cond", cond_t, (B, self.G))
+        _want("x_init", xi, (B, self.T, self.D))
+        _want("step_noise", nz, (n_steps, B, self.T, self.D))
+        return cond_t, xi, nz, B, n_steps, step_end, torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
+
+    def _agent_io(self, obs_emb, x_init, x_noise, a_init, a_noise, planner_steps, idm_steps, action_bounds, action_mode, use_graph,
+                  parts=None):
+        """What every agent_* sampling method marshals: obs_emb (B, H, D), the four optional noise tensors, the step-count defaults, the
+        action bounds (length 1 or A) and the x / plan / action outputs.  parts(B), when given, runs right behind the obs_emb check (a
+        method's own parts: their errors come before the noise tensors').  -> a namespace: B, H, ps, is_, parts, ob, noise (the four
+        pointers x_init, x_noise, a_init, a_noise), out = (x, plan, act) and tail, the arguments every C call of the family ends with."""
+        ob = _f32(obs_emb, self.device)
+        B, H = ob.shape[0], ob.shape[1]
+        _want("obs_emb", ob, (B, H, self.D))
+        m = SimpleNamespace(ob=ob, B=B, H=H)
+        m.parts = None if parts is None else parts(B)
+        m.ps = self.planner_train_steps if planner_steps is None else int(planner_steps)
+        m.is_ = self.idm_train_steps if idm_steps is None else int(idm_steps)
+        R = B * self.ah
+        xi, xn, ai, an = (_opt_f32(t, self.device) for t in (x_init, x_noise, a_init, a_noise))
+        _want("x_init", xi, (B, self.T, self.D))
+        _want("x_noise", xn, (m.ps, B, self.T, self.D))
+        _want("a_init", ai, (R, self.A))
+        _want("a_noise", an, (m.is_, R, self.A))
+        lo, hi, adim = self._action_bounds(action_bounds, self.A)
+        m.keep = (xi, xn, ai, an, lo, hi)
+        m.noise = [_ptr(xi), _ptr(xn), _ptr(ai), _ptr(an)]
+        m.out = (torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32),
+                 torch.empty((B, self.ah + 1, self.D), device=self.device, dtype=torch.float32),
+                 torch.empty((B, self.ah, self.A), device=self.device, dtype=torch.float32))
+        m.tail = [m.ps, m.is_, *(_ptr(t) for t in m.out), _ptr(lo), _ptr(hi), adim, int(action_mode), B, 1 if use_graph else 0, self._stream()]
+        return m
+
+    def _action_bounds(self, action_bounds, n: int):
+        """(lo, hi) of length 1 or n, or None -> (lo, hi, length) as the C ABI takes them (None, None, 0: actions stay normalised)."""
+        if action_bounds is None:
+            return None, None, 0
+        lo, hi = self._bounds(*action_bounds)
+        adim = lo.numel()
+        if adim not in (1, n) or hi.numel() != adim:
+            raise ValueError(f"action bounds must have length 1 or {n}")
+        return lo, hi, adim
+
     def plan_sample(self, cond: Optional[torch.Tensor], B: Optional[int] = None,
                     x_init: Optional[torch.Tensor] = None, step_noise: Optional[torch.Tensor] = None,
                     seed: int = 0, row_offset: int = 0, sampler: str = "ddpm",
                     n_steps: Optional[int] = None, use_graph: bool = True) -> torch.Tensor:
-        cond_t = None if cond is None else _f32(cond, self.device)
-        if B is None:
-            B = cond_t.shape[0] if cond_t is not None else x_init.shape[0]
-        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
-        xi = None if x_init is None else _f32(x_init, self.device)
-        nz = None if step_noise is None else _f32(step_noise, self.device)
-        _want("cond", cond_t, (B, self.G))
-        _want("x_init", xi, (B, self.T, self.D))
-        _want("step_noise", nz, (n_steps, B, self.T, self.D))
-        out = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
-        check(self.lib.ldp_plan_sample(self._h, _ptr(cond_t), _ptr(xi), _ptr(nz), C.c_uint64(seed & (2**64 - 1)),
-                                       C.c_int64(row_offset), self._sampler(sampler, n_steps), n_steps, _ptr(out), B,
-                                       1 if use_graph else 0, self._stream()))
+        cond_t, xi, nz, B, n_steps, _, out = self._plan_io(cond, B, x_init, step_noise, n_steps)
+        check(self.lib.ldp_plan_sample(self._h, _ptr(cond_t), _ptr(xi), _ptr(nz), _u64(seed), C.c_int64(row_offset),
+                                       self._sampler(sampler, n_steps), n_steps, _ptr(out), B, 1 if use_graph else 0, self._stream()))
         self.call_seq += 1
         return out
 
@@ -356,19 +408,10 @@ class HipEngine:
                           x_init: Optional[torch.Tensor] = None, step_noise: Optional[torch.Tensor] = None, seed: int = 0,
                           row_offset: int = 0, sampler: str = "ddpm", n_steps: Optional[int] = None, use_graph: bool = True) -> torch.Tensor:
         """plan_sample restricted to the executed steps [step_begin, step_end) of n_steps; step_noise stays (n_steps, B, T, D)."""
-        cond_t = None if cond is None else _f32(cond, self.device)
-        if B is None:
-            B = cond_t.shape[0] if cond_t is not None else x_init.shape[0]
-        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
-        xi = None if x_init is None else _f32(x_init, self.device)
-        nz = None if step_noise is None else _f32(step_noise, self.device)
-        _want("cond", cond_t, (B, self.G))
-        _want("x_init", xi, (B, self.T, self.D))
-        _want("step_noise", nz, (n_steps, B, self.T, self.D))
-        out = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
-        check(self.lib.ldp_plan_sample_range(self._h, _ptr(cond_t), _ptr(xi), _ptr(nz), C.c_uint64(seed & (2**64 - 1)),
-                                             C.c_int64(row_offset), self._sampler(sampler, n_steps), n_steps, int(step_begin), int(step_end),
-                                             _ptr(out), B, 1 if use_graph else 0, self._stream()))
+        cond_t, xi, nz, B, n_steps, _, out = self._plan_io(cond, B, x_init, step_noise, n_steps)
+        check(self.lib.ldp_plan_sample_range(self._h, _ptr(cond_t), _ptr(xi), _ptr(nz), _u64(seed), C.c_int64(row_offset),
+                                             self._sampler(sampler, n_steps), n_steps, int(step_begin), int(step_end), _ptr(out), B,
+                                             1 if use_graph else 0, self._stream()))
         self.call_seq += 1
         return out
 
@@ -404,7 +447,7 @@ class HipEngine:
         n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
         out = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
         check(self.lib.ldp_plan_warm_init(self._h, _ptr(xp), sp, n_slots, self.ah if shift is None else int(shift),
-                                          C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _SAMPLERS[sampler], n_steps,
+                                          _u64(seed), C.c_int64(row_offset), _SAMPLERS[sampler], n_steps,
                                           int(step_begin), _ptr(out), B, self._stream()))
         del keep
         return out
@@ -416,38 +459,15 @@ class HipEngine:
         """agent_sample resumed from the previous plan: the planner state is the warm initial state of rows slot[b] (or b) of x_store
         (n_slots, T, D), the planner loop runs the steps [step_begin, planner_steps), and the new full state is written back IN PLACE to
         the same rows of x_store -> (x, plan, action) as agent_sample.  Slots must be distinct within a call."""
-        ob = _f32(obs_emb, self.device)
-        B, H = ob.shape[0], ob.shape[1]
-        _want("obs_emb", ob, (B, H, self.D))
-        xs = self._store(x_store)
-        sp, keep = self._slots(slot, B)
-        ps = self.planner_train_steps if planner_steps is None else int(planner_steps)
-        is_ = self.idm_train_steps if idm_steps is None else int(idm_steps)
-        R = B * self.ah
-        xn = None if x_noise is None else _f32(x_noise, self.device)
-        ai = None if a_init is None else _f32(a_init, self.device)
-        an = None if a_noise is None else _f32(a_noise, self.device)
-        _want("x_noise", xn, (ps, B, self.T, self.D))
-        _want("a_init", ai, (R, self.A))
-        _want("a_noise", an, (is_, R, self.A))
-        lo = hi = None
-        adim = 0
-        if action_bounds is not None:
-            lo, hi = self._bounds(*action_bounds)
-            adim = lo.numel()
-            if adim not in (1, self.A) or hi.numel() != adim:
-                raise ValueError(f"action bounds must have length 1 or {self.A}")
-        x = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
-        plan = torch.empty((B, self.ah + 1, self.D), device=self.device, dtype=torch.float32)
-        act = torch.empty((B, self.ah, self.A), device=self.device, dtype=torch.float32)
-        check(self.lib.ldp_agent_resample(self._h, _ptr(ob), H, int(obs_horizon), _ptr(xs), sp, int(xs.shape[0]),
-                                          self.ah if shift is None else int(shift), int(step_begin), _ptr(xn), _ptr(ai), _ptr(an),
-                                          C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _SAMPLERS[sampler], ps, is_,
-                                          _ptr(x), _ptr(plan), _ptr(act), _ptr(lo), _ptr(hi), adim, int(action_mode), B,
-                                          1 if use_graph else 0, self._stream()))
+        m = self._agent_io(obs_emb, None, x_noise, a_init, a_noise, planner_steps, idm_steps, action_bounds, action_mode, use_graph,
+                           parts=lambda B: (self._store(x_store), *self._slots(slot, B)))
+        xs, sp, keep = m.parts
+        check(self.lib.ldp_agent_resample(self._h, _ptr(m.ob), m.H, int(obs_horizon), _ptr(xs), sp, int(xs.shape[0]),
+                                          self.ah if shift is None else int(shift), int(step_begin), *m.noise[1:], _u64(seed),
+                                          C.c_int64(row_offset), _SAMPLERS[sampler], *m.tail))
         del keep
         self.call_seq += 1
-        return x, plan, act
+        return m.out
 
     # -- constrained planning (csrc/constrain.hip, DESIGN.md 4.17) ----------------------------------------------------
     def _constraint(self, target, mask, mode, B: int):
@@ -479,7 +499,7 @@ class HipEngine:
         n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
         out = torch.empty_like(xt)
         check(self.lib.ldp_plan_constrain(self._h, _ptr(xt), _ptr(tg), _ptr(mk), md, _SAMPLERS[sampler], n_steps, int(level),
-                                          C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _ptr(out), B, self._stream()))
+                                          _u64(seed), C.c_int64(row_offset), _ptr(out), B, self._stream()))
         return out
 
     def plan_sample_constrained(self, cond: Optional[torch.Tensor], target, mask, *, mode="repaint", step_begin: int = 0,
@@ -488,20 +508,10 @@ class HipEngine:
                                 n_steps: Optional[int] = None, use_graph: bool = True) -> torch.Tensor:
         """plan_sample_range with the constraint applied in the loop: C_begin in front of the first executed step and C_{i+1} behind
         step i, inside the captured graph (default range: the whole loop).  An empty range returns C_begin of the initial state."""
-        cond_t = None if cond is None else _f32(cond, self.device)
-        if B is None:
-            B = cond_t.shape[0] if cond_t is not None else x_init.shape[0]
-        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
-        step_end = n_steps if step_end is None else int(step_end)
-        xi = None if x_init is None else _f32(x_init, self.device)
-        nz = None if step_noise is None else _f32(step_noise, self.device)
-        _want("cond", cond_t, (B, self.G))
-        _want("x_init", xi, (B, self.T, self.D))
-        _want("step_noise", nz, (n_steps, B, self.T, self.D))
+        cond_t, xi, nz, B, n_steps, step_end, out = self._plan_io(cond, B, x_init, step_noise, n_steps, step_end)
         tg, mk, md = self._constraint(target, mask, mode, B)
-        out = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
         check(self.lib.ldp_plan_sample_constrained(self._h, _ptr(cond_t), _ptr(xi), _ptr(nz), _ptr(tg), _ptr(mk), md,
-                                                   C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _SAMPLERS[sampler], n_steps,
+                                                   _u64(seed), C.c_int64(row_offset), _SAMPLERS[sampler], n_steps,
                                                    int(step_begin), step_end, _ptr(out), B, 1 if use_graph else 0, self._stream()))
         self.call_seq += 1
         return out
@@ -514,37 +524,13 @@ class HipEngine:
         agent_resample) is refused: a constraint together with a warm start is not built."""
         if x_store is not None:
             raise ValueError("a constraint (target / mask) together with a warm start (x_store) is not built")
-        ob = _f32(obs_emb, self.device)
-        B, H = ob.shape[0], ob.shape[1]
-        _want("obs_emb", ob, (B, H, self.D))
-        tg, mk, md = self._constraint(target, mask, mode, B)
-        ps = self.planner_train_steps if planner_steps is None else int(planner_steps)
-        is_ = self.idm_train_steps if idm_steps is None else int(idm_steps)
-        R = B * self.ah
-        xi = None if x_init is None else _f32(x_init, self.device)
-        xn = None if x_noise is None else _f32(x_noise, self.device)
-        ai = None if a_init is None else _f32(a_init, self.device)
-        an = None if a_noise is None else _f32(a_noise, self.device)
-        _want("x_init", xi, (B, self.T, self.D))
-        _want("x_noise", xn, (ps, B, self.T, self.D))
-        _want("a_init", ai, (R, self.A))
-        _want("a_noise", an, (is_, R, self.A))
-        lo = hi = None
-        adim = 0
-        if action_bounds is not None:
-            lo, hi = self._bounds(*action_bounds)
-            adim = lo.numel()
-            if adim not in (1, self.A) or hi.numel() != adim:
-                raise ValueError(f"action bounds must have length 1 or {self.A}")
-        x = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
-        plan = torch.empty((B, self.ah + 1, self.D), device=self.device, dtype=torch.float32)
-        act = torch.empty((B, self.ah, self.A), device=self.device, dtype=torch.float32)
-        check(self.lib.ldp_agent_sample_constrained(self._h, _ptr(ob), H, int(obs_horizon), _ptr(xi), _ptr(xn), _ptr(ai), _ptr(an),
-                                                    _ptr(tg), _ptr(mk), md, C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset),
-                                                    _SAMPLERS[sampler], ps, is_, _ptr(x), _ptr(plan), _ptr(act), _ptr(lo), _ptr(hi), adim,
-                                                    int(action_mode), B, 1 if use_graph else 0, self._stream()))
+        m = self._agent_io(obs_emb, x_init, x_noise, a_init, a_noise, planner_steps, idm_steps, action_bounds, action_mode, use_graph,
+                           parts=lambda B: self._constraint(target, mask, mode, B))
+        tg, mk, md = m.parts
+        check(self.lib.ldp_agent_sample_constrained(self._h, _ptr(m.ob), m.H, int(obs_horizon), *m.noise, _ptr(tg), _ptr(mk), md, _u64(seed),
+                                                    C.c_int64(row_offset), _SAMPLERS[sampler], *m.tail))
         self.call_seq += 1
-        return x, plan, act
+        return m.out
 
     # -- guided planning (csrc/guide.hip, DESIGN.md 4.19) --------------------------------------------------------------
     def _guide(self, guide, B: int, ld: Optional[int] = None):
@@ -596,7 +582,7 @@ class HipEngine:
         _want("rho", rh, (n_steps,))
         check(self.lib.ldp_plan_guide_step(self._h, _ptr(xt), _ptr(ep), _ptr(nz), _ptr(tg), _ptr(wg), _ptr(an), _ptr(dev[0]), _ptr(dev[1]),
                                            _ptr(dev[2]), _ptr(dev[3]), _ptr(rh), _SAMPLERS[sampler], n_steps, int(step),
-                                           C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _ptr(xt), ldx, ldg, B, self._stream()))
+                                           _u64(seed), C.c_int64(row_offset), _ptr(xt), ldx, ldg, B, self._stream()))
         return xt
 
     def plan_guide_cost(self, x: torch.Tensor, guide, n_per: int = 1) -> torch.Tensor:
@@ -619,22 +605,12 @@ class HipEngine:
                            use_graph: bool = True) -> torch.Tensor:
         """plan_sample_range with the guided loop: per executed step the U-Net's eps, then one guided step with the step size rho[i]
         (default range: the whole loop).  rho: n_steps step sizes (the library checks the count)."""
-        cond_t = None if cond is None else _f32(cond, self.device)
-        if B is None:
-            B = cond_t.shape[0] if cond_t is not None else x_init.shape[0]
-        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
-        step_end = n_steps if step_end is None else int(step_end)
-        xi = None if x_init is None else _f32(x_init, self.device)
-        nz = None if step_noise is None else _f32(step_noise, self.device)
-        _want("cond", cond_t, (B, self.G))
-        _want("x_init", xi, (B, self.T, self.D))
-        _want("step_noise", nz, (n_steps, B, self.T, self.D))
+        cond_t, xi, nz, B, n_steps, step_end, out = self._plan_io(cond, B, x_init, step_noise, n_steps, step_end)
         tg, wg, an, cols = self._guide(guide, B)
         rh = np.ascontiguousarray(np.asarray(rho, dtype=np.float32).reshape(-1))
-        out = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
         check(self.lib.ldp_plan_sample_guided(self._h, _ptr(cond_t), _ptr(xi), _ptr(nz), _ptr(tg), _ptr(wg), _ptr(an),
                                               *(self._host_ptr(a) for a in cols), self._host_ptr(rh), int(rh.size),
-                                              C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _SAMPLERS[sampler], n_steps,
+                                              _u64(seed), C.c_int64(row_offset), _SAMPLERS[sampler], n_steps,
                                               int(step_begin), step_end, _ptr(out), B, 1 if use_graph else 0, self._stream()))
         self.call_seq += 1
         return out
@@ -643,39 +619,15 @@ class HipEngine:
                             a_noise=None, seed: int = 0, row_offset: int = 0, sampler: str = "ddim", planner_steps: Optional[int] = None,
                             idm_steps: Optional[int] = None, action_bounds=None, action_mode: int = 0, use_graph: bool = True):
         """agent_sample whose planner loop is the guided one -> (x, plan, action) as agent_sample."""
-        ob = _f32(obs_emb, self.device)
-        B, H = ob.shape[0], ob.shape[1]
-        _want("obs_emb", ob, (B, H, self.D))
-        tg, wg, an, cols = self._guide(guide, B)
+        m = self._agent_io(obs_emb, x_init, x_noise, a_init, a_noise, planner_steps, idm_steps, action_bounds, action_mode, use_graph,
+                           parts=lambda B: self._guide(guide, B))
+        tg, wg, an, cols = m.parts
         rh = np.ascontiguousarray(np.asarray(rho, dtype=np.float32).reshape(-1))
-        ps = self.planner_train_steps if planner_steps is None else int(planner_steps)
-        is_ = self.idm_train_steps if idm_steps is None else int(idm_steps)
-        R = B * self.ah
-        xi = None if x_init is None else _f32(x_init, self.device)
-        xn = None if x_noise is None else _f32(x_noise, self.device)
-        ai = None if a_init is None else _f32(a_init, self.device)
-        an_ = None if a_noise is None else _f32(a_noise, self.device)
-        _want("x_init", xi, (B, self.T, self.D))
-        _want("x_noise", xn, (ps, B, self.T, self.D))
-        _want("a_init", ai, (R, self.A))
-        _want("a_noise", an_, (is_, R, self.A))
-        lo = hi = None
-        adim = 0
-        if action_bounds is not None:
-            lo, hi = self._bounds(*action_bounds)
-            adim = lo.numel()
-            if adim not in (1, self.A) or hi.numel() != adim:
-                raise ValueError(f"action bounds must have length 1 or {self.A}")
-        x = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
-        plan = torch.empty((B, self.ah + 1, self.D), device=self.device, dtype=torch.float32)
-        act = torch.empty((B, self.ah, self.A), device=self.device, dtype=torch.float32)
-        check(self.lib.ldp_agent_sample_guided(self._h, _ptr(ob), H, int(obs_horizon), _ptr(xi), _ptr(xn), _ptr(ai), _ptr(an_), _ptr(tg),
-                                               _ptr(wg), _ptr(an), *(self._host_ptr(a) for a in cols), self._host_ptr(rh), int(rh.size),
-                                               C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _SAMPLERS[sampler], ps, is_,
-                                               _ptr(x), _ptr(plan), _ptr(act), _ptr(lo), _ptr(hi), adim, int(action_mode), B,
-                                               1 if use_graph else 0, self._stream()))
+        check(self.lib.ldp_agent_sample_guided(self._h, _ptr(m.ob), m.H, int(obs_horizon), *m.noise, _ptr(tg), _ptr(wg), _ptr(an),
+                                               *(self._host_ptr(a) for a in cols), self._host_ptr(rh), int(rh.size), _u64(seed),
+                                               C.c_int64(row_offset), _SAMPLERS[sampler], *m.tail))
         self.call_seq += 1
-        return x, plan, act
+        return m.out
 
     # -- composed planning (csrc/compose.hip, DESIGN.md 4.20) ----------------------------------------------------------
     def _compose(self, B: int, n_steps: int, *, guide=None, rho=None, target=None, mask=None, mode="repaint", x_store=None, slot=None,
@@ -749,7 +701,7 @@ class HipEngine:
             h_out = hp if hp is not None else torch.zeros_like(xt)
         pc, keep = self._compose(B, n_steps, guide=guide, rho=rho, target=target, mask=mask, mode=mode, ldg=ldg, ldc=ldc, device_cols=True)
         check(self.lib.ldp_plan_compose_step(self._h, _ptr(xt), _ptr(ep), _ptr(nz), _ptr(hp), C.byref(pc), sid, n_steps, int(step),
-                                             1 if second else 0, C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), _ptr(xt), _ptr(h_out),
+                                             1 if second else 0, _u64(seed), C.c_int64(row_offset), _ptr(xt), _ptr(h_out),
                                              ldx, self.D if ldg is None else int(ldg), self.D if ldc is None else int(ldc), B, self._stream()))
         del keep
         return (xt, h_out) if sid == SAMPLER_DPMPP else xt
@@ -760,22 +712,12 @@ class HipEngine:
                              seed: int = 0, row_offset: int = 0, sampler: str = "ddim", n_steps: Optional[int] = None,
                              use_graph: bool = True) -> torch.Tensor:
         """plan_sample_range with any of a guide (with rho), a constraint (target, mask, mode) and a warm start (x_store, slot, shift: the
-        initial state is the warm one at the level of step_begin; x_store is not written), under any sampler.  A guide with a
-        constraint, and either under "dpmpp", run the composed loop (one composed launch behind every U-Net evaluation); every other
-        combination runs the dedicated loop."""
-        cond_t = None if cond is None else _f32(cond, self.device)
-        if B is None:
-            B = cond_t.shape[0] if cond_t is not None else x_init.shape[0]
-        n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
-        step_end = n_steps if step_end is None else int(step_end)
-        xi = None if x_init is None else _f32(x_init, self.device)
-        nz = None if step_noise is None else _f32(step_noise, self.device)
-        _want("cond", cond_t, (B, self.G))
-        _want("x_init", xi, (B, self.T, self.D))
-        _want("step_noise", nz, (n_steps, B, self.T, self.D))
+        initial state is the warm one at the level of step_begin; x_store is not written), under any sampler.  With a guide,
+        or under "dpmpp", the loop is the stepped one (one launch of the step kernel behind every U-Net evaluation does guide, update
+        and constraint); otherwise the U-Net's last launch does the scheduler step and a constraint is a launch of its own."""
+        cond_t, xi, nz, B, n_steps, step_end, out = self._plan_io(cond, B, x_init, step_noise, n_steps, step_end)
         pc, keep = self._compose(B, n_steps, guide=guide, rho=rho, target=target, mask=mask, mode=mode, x_store=x_store, slot=slot, shift=shift)
-        out = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
-        check(self.lib.ldp_plan_sample_composed(self._h, _ptr(cond_t), _ptr(xi), _ptr(nz), C.byref(pc), C.c_uint64(seed & (2**64 - 1)),
+        check(self.lib.ldp_plan_sample_composed(self._h, _ptr(cond_t), _ptr(xi), _ptr(nz), C.byref(pc), _u64(seed),
                                                 C.c_int64(row_offset), self._sampler(sampler, n_steps), n_steps, int(step_begin), step_end,
                                                 _ptr(out), B, 1 if use_graph else 0, self._stream()))
         del keep
@@ -790,38 +732,13 @@ class HipEngine:
         """agent_sample (no x_store) / agent_resample (x_store: the planner loop is [step_begin, planner_steps) from the warm state, and
         the new state is written back IN PLACE to the same rows of x_store) with any of a guide and a constraint, under any sampler
         -> (x, plan, action)."""
-        ob = _f32(obs_emb, self.device)
-        B, H = ob.shape[0], ob.shape[1]
-        _want("obs_emb", ob, (B, H, self.D))
-        ps = self.planner_train_steps if planner_steps is None else int(planner_steps)
-        is_ = self.idm_train_steps if idm_steps is None else int(idm_steps)
-        R = B * self.ah
-        xi = None if x_init is None else _f32(x_init, self.device)
-        xn = None if x_noise is None else _f32(x_noise, self.device)
-        ai = None if a_init is None else _f32(a_init, self.device)
-        an = None if a_noise is None else _f32(a_noise, self.device)
-        _want("x_init", xi, (B, self.T, self.D))
-        _want("x_noise", xn, (ps, B, self.T, self.D))
-        _want("a_init", ai, (R, self.A))
-        _want("a_noise", an, (is_, R, self.A))
-        pc, keep = self._compose(B, ps, guide=guide, rho=rho, target=target, mask=mask, mode=mode, x_store=x_store, slot=slot, shift=shift)
-        lo = hi = None
-        adim = 0
-        if action_bounds is not None:
-            lo, hi = self._bounds(*action_bounds)
-            adim = lo.numel()
-            if adim not in (1, self.A) or hi.numel() != adim:
-                raise ValueError(f"action bounds must have length 1 or {self.A}")
-        x = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
-        plan = torch.empty((B, self.ah + 1, self.D), device=self.device, dtype=torch.float32)
-        act = torch.empty((B, self.ah, self.A), device=self.device, dtype=torch.float32)
-        check(self.lib.ldp_agent_sample_composed(self._h, _ptr(ob), H, int(obs_horizon), _ptr(xi), _ptr(xn), _ptr(ai), _ptr(an), C.byref(pc),
-                                                 int(step_begin), C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset),
-                                                 self._sampler(sampler, ps), ps, is_, _ptr(x), _ptr(plan), _ptr(act), _ptr(lo), _ptr(hi), adim,
-                                                 int(action_mode), B, 1 if use_graph else 0, self._stream()))
+        m = self._agent_io(obs_emb, x_init, x_noise, a_init, a_noise, planner_steps, idm_steps, action_bounds, action_mode, use_graph)
+        pc, keep = self._compose(m.B, m.ps, guide=guide, rho=rho, target=target, mask=mask, mode=mode, x_store=x_store, slot=slot, shift=shift)
+        check(self.lib.ldp_agent_sample_composed(self._h, _ptr(m.ob), m.H, int(obs_horizon), *m.noise, C.byref(pc), int(step_begin), _u64(seed),
+                                                 C.c_int64(row_offset), self._sampler(sampler, m.ps), *m.tail))
         del keep
         self.call_seq += 1
-        return x, plan, act
+        return m.out
 
     # -- best-of-N planning (csrc/select.hip, DESIGN.md 4.14): candidate-major rows r = c * B + b ---------------------
     def plan_candidates(self, obs_emb: torch.Tensor, obs_horizon: int, n_candidates: int, *, c0: int = 0, n_loc: Optional[int] = None,
@@ -843,7 +760,7 @@ class HipEngine:
         _want("step_noise", nz, (n_steps, rows, self.T, self.D))
         out = torch.empty((rows, self.T, self.D), device=self.device, dtype=torch.float32)
         check(self.lib.ldp_plan_candidates(self._h, _ptr(ob), H, int(obs_horizon), B, int(c0), n_loc, _ptr(xi), _ptr(nz),
-                                           C.c_uint64(seed & (2**64 - 1)), self._sampler(sampler, n_steps), n_steps, _ptr(out),
+                                           _u64(seed), self._sampler(sampler, n_steps), n_steps, _ptr(out),
                                            1 if use_graph else 0, self._stream()))
         self.call_seq += 1
         return out
@@ -924,7 +841,7 @@ class HipEngine:
         _want("a_init", ai, (R, self.A))
         _want("step_noise", nz, (n_steps, R, self.A))
         out = torch.empty((R, self.A), device=self.device, dtype=torch.float32)
-        check(self.lib.ldp_idm_sample(self._h, _ptr(tr), _ptr(ai), _ptr(nz), C.c_uint64(seed & (2**64 - 1)),
+        check(self.lib.ldp_idm_sample(self._h, _ptr(tr), _ptr(ai), _ptr(nz), _u64(seed),
                                       C.c_int64(row_offset), _SAMPLERS[sampler], n_steps, _ptr(out), R,
                                       1 if use_graph else 0, self._stream()))
         self.call_seq += 1
@@ -938,36 +855,11 @@ class HipEngine:
         """sample_viz_step without the decode (agent/ldp_agent.py:452-505): -> (x, plan, action) with
         x (B,T,D), plan (B,ah+1,D), action (B,ah,A).  action_bounds = (lo, hi) device tensors of length
         1 or A (None: actions stay normalised); action_mode 0 = unnormalize + clip, 2 = clip."""
-        ob = _f32(obs_emb, self.device)
-        B, H = ob.shape[0], ob.shape[1]
-        _want("obs_emb", ob, (B, H, self.D))
-        ps = self.planner_train_steps if planner_steps is None else int(planner_steps)
-        is_ = self.idm_train_steps if idm_steps is None else int(idm_steps)
-        R = B * self.ah
-        xi = None if x_init is None else _f32(x_init, self.device)
-        xn = None if x_noise is None else _f32(x_noise, self.device)
-        ai = None if a_init is None else _f32(a_init, self.device)
-        an = None if a_noise is None else _f32(a_noise, self.device)
-        _want("x_init", xi, (B, self.T, self.D))
-        _want("x_noise", xn, (ps, B, self.T, self.D))
-        _want("a_init", ai, (R, self.A))
-        _want("a_noise", an, (is_, R, self.A))
-        lo = hi = None
-        adim = 0
-        if action_bounds is not None:
-            lo, hi = self._bounds(*action_bounds)
-            adim = lo.numel()
-            if adim not in (1, self.A) or hi.numel() != adim:
-                raise ValueError(f"action bounds must have length 1 or {self.A}")
-        x = torch.empty((B, self.T, self.D), device=self.device, dtype=torch.float32)
-        plan = torch.empty((B, self.ah + 1, self.D), device=self.device, dtype=torch.float32)
-        act = torch.empty((B, self.ah, self.A), device=self.device, dtype=torch.float32)
-        check(self.lib.ldp_agent_sample(self._h, _ptr(ob), H, int(obs_horizon), _ptr(xi), _ptr(xn), _ptr(ai), _ptr(an),
-                                        C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), self._sampler(sampler, ps), ps, is_,
-                                        _ptr(x), _ptr(plan), _ptr(act), _ptr(lo), _ptr(hi), adim, int(action_mode), B,
-                                        1 if use_graph else 0, self._stream()))
+        m = self._agent_io(obs_emb, x_init, x_noise, a_init, a_noise, planner_steps, idm_steps, action_bounds, action_mode, use_graph)
+        check(self.lib.ldp_agent_sample(self._h, _ptr(m.ob), m.H, int(obs_horizon), *m.noise, _u64(seed), C.c_int64(row_offset),
+                                        self._sampler(sampler, m.ps), *m.tail))
         self.call_seq += 1
-        return x, plan, act
+        return m.out
 
     # -- DP policy: condition gather + U-Net loop + action rows as one call / one captured graph ---------------------
     def policy_sample(self, obs_emb: torch.Tensor, obs_horizon: int, img_width: int, *, x_init=None, x_noise=None, seed: int = 0,
@@ -981,20 +873,13 @@ class HipEngine:
         E = self.G // int(obs_horizon)
         _want("obs_emb", ob, (B, H, E))
         n_steps = self.planner_train_steps if n_steps is None else int(n_steps)
-        xi = None if x_init is None else _f32(x_init, self.device)
-        xn = None if x_noise is None else _f32(x_noise, self.device)
+        xi, xn = _opt_f32(x_init, self.device), _opt_f32(x_noise, self.device)
         _want("x_init", xi, (B, self.T, self.D))
         _want("x_noise", xn, (n_steps, B, self.T, self.D))
-        lo = hi = None
-        adim = 0
-        if action_bounds is not None:
-            lo, hi = self._bounds(*action_bounds)
-            adim = lo.numel()
-            if adim not in (1, self.D) or hi.numel() != adim:
-                raise ValueError(f"action bounds must have length 1 or {self.D}")
+        lo, hi, adim = self._action_bounds(action_bounds, self.D)
         act = torch.empty((B, self.ah, self.D), device=self.device, dtype=torch.float32)
         check(self.lib.ldp_policy_sample(self._h, _ptr(ob), H, int(obs_horizon), int(img_width), _ptr(xi), _ptr(xn),
-                                         C.c_uint64(seed & (2**64 - 1)), C.c_int64(row_offset), self._sampler(sampler, n_steps), n_steps, _ptr(act),
+                                         _u64(seed), C.c_int64(row_offset), self._sampler(sampler, n_steps), n_steps, _ptr(act),
                                          _ptr(lo), _ptr(hi), adim, int(action_mode), B, 1 if use_graph else 0, self._stream()))
         self.call_seq += 1
         return act
@@ -1558,7 +1443,7 @@ def philox_raw(seed: int, elem0: int, step: int, stream_id: int, n: int, device=
     lib = _lib.load()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     out = torch.empty((n, 4), device=dev, dtype=torch.int32)
-    check(lib.ldp_philox_raw(C.c_uint64(seed & (2**64 - 1)), C.c_uint64(elem0 & (2**64 - 1)), C.c_uint32(step),
+    check(lib.ldp_philox_raw(_u64(seed), C.c_uint64(elem0 & (2**64 - 1)), C.c_uint32(step),
                              C.c_uint32(stream_id), _ptr(out), n, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return out
 
@@ -1567,6 +1452,6 @@ def philox_normal(seed: int, elem0: int, step: int, stream_id: int, n: int, devi
     lib = _lib.load()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     out = torch.empty((n,), device=dev, dtype=torch.float32)
-    check(lib.ldp_philox_normal(C.c_uint64(seed & (2**64 - 1)), C.c_uint64(elem0 & (2**64 - 1)), C.c_uint32(step),
+    check(lib.ldp_philox_normal(_u64(seed), C.c_uint64(elem0 & (2**64 - 1)), C.c_uint32(step),
                                 C.c_uint32(stream_id), _ptr(out), n, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return out

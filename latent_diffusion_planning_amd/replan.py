@@ -183,12 +183,7 @@ class Replanner:
             self.valid[s] = True
             self.gen[s] += 1
         mine = {s: self.gen[s] for s in slots}
-        action, plan, x = (DeviceArray(t, record=rec) for t in res)
-        S = ag._engine.image_size
-        viz = DeviceArray(thunk=lambda: ag._vae_decode_t(plan.tensor), shape=tuple(plan.shape[:2]) + (3, S, S), record=rec)
-        if decode:
-            viz.tensor
-        return action, {"plan": plan, "x": x, "plan_viz": viz}
+        return ag._plan_metrics(res, rec, ("x",), decode)
 
 
 class Controller(Replanner):

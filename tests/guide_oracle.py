@@ -121,7 +121,8 @@ def fma32(a, b, c):
 
 
 def emulate_step(x, eps, G, rho, k, z=None):
-    """plan_guide_step_kernel's result bit for bit: x, eps, z float32 (B, T, D); k: the float32 coefficient row; rho: the float32 step."""
+    """plan_compose_step_kernel<0, true, false>'s result (the guided step) bit for bit: x, eps, z float32 (B, T, D); k: the float32
+    coefficient row; rho: the float32 step."""
     x, eps = np.asarray(x, F32), np.asarray(eps, F32)
     _, inv_a, sg, c_x0, c_x, c_eps, sigma = (F32(v) for v in k)
     one = F32(1.0)

@@ -12,7 +12,8 @@ all alike.  Every call is waited for (host clock around enqueue + completion poi
 first window.  A figure is [median, min, max] ms per call over the `--repeats` windows.
 Prints ONE JSON line.  Not the driver's bench line (bench.py is).  Control quality is not evaluated here (tools/toy_reach.py measures it on a toy task).
 
-  python tools/compose_bench.py"""
+  python tools/compose_bench.py
+  python tools/compose_bench.py --lib /path/to/libldp_hip.so     (another build on the same box: A/B)"""
 import argparse
 import json
 import os
@@ -46,8 +47,11 @@ def main():
     p.add_argument("--steps", type=int, default=10, help="calls per timed window")
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--repeats", type=int, default=7, help="timed windows per figure")
+    p.add_argument("--lib", default=None, metavar="PATH", help="load this build of libldp_hip instead of the in-tree one (same-box A/B)")
     a = p.parse_args()
     from latent_diffusion_planning_amd import _lib
+    if a.lib:
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     from latent_diffusion_planning_amd.agent import LDPAgent
     from tests import cfgs
     torch.cuda.set_device(0)
@@ -89,7 +93,7 @@ def main():
         rows.append(row)
     eng.check_fault()
     print(json.dumps(dict(tool="compose_bench", config="rm_lift", figures="[median, min, max] ms per call", steps=a.steps,
-                          repeats=a.repeats, version=_lib.load().ldp_version().decode(), rows=rows)), flush=True)
+                          repeats=a.repeats, lib=a.lib or "in-tree", version=_lib.load().ldp_version().decode(), rows=rows)), flush=True)
 
 
 if __name__ == "__main__":

@@ -11,7 +11,8 @@ per-repeat differences to the free window of the same repeat (it holds the eager
 loop as well), `extra_us_per_step` that difference over the n guided steps.
 Prints ONE JSON line.  Not the driver's bench line (bench.py is).
 
-  python tools/guide_bench.py"""
+  python tools/guide_bench.py
+  python tools/guide_bench.py --lib /path/to/libldp_hip.so     (another build on the same box: A/B)"""
 import argparse
 import json
 import os
@@ -44,8 +45,11 @@ def main():
     p.add_argument("--steps", type=int, default=10, help="calls per timed window")
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--repeats", type=int, default=7, help="timed windows per figure")
+    p.add_argument("--lib", default=None, metavar="PATH", help="load this build of libldp_hip instead of the in-tree one (same-box A/B)")
     a = p.parse_args()
     from latent_diffusion_planning_amd import _lib
+    if a.lib:
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     from latent_diffusion_planning_amd.agent import LDPAgent
     from tests import cfgs
     torch.cuda.set_device(0)
@@ -83,7 +87,7 @@ def main():
             rows.append(row)
     eng.check_fault()
     print(json.dumps(dict(tool="guide_bench", config="rm_lift", figures="[median, min, max] ms per call", steps=a.steps,
-                          repeats=a.repeats, version=_lib.load().ldp_version().decode(), rows=rows)), flush=True)
+                          repeats=a.repeats, lib=a.lib or "in-tree", version=_lib.load().ldp_version().decode(), rows=rows)), flush=True)
 
 
 if __name__ == "__main__":

@@ -13,7 +13,8 @@ error     On the real U-Net with random weights (tests.util.planner_params) and 
           finest solution of the same ODE from the same starting level the engine has.  Each arm starts from x_T at ITS first timestep's
           level; x_T is one N(0, 1) draw, which is what every loop starts from.
 
-  python tools/solver_bench.py"""
+  python tools/solver_bench.py
+  python tools/solver_bench.py --lib /path/to/libldp_hip.so --skip error     (another build on the same box: A/B)"""
 import argparse
 import json
 import os
@@ -117,11 +118,14 @@ def main():
     p.add_argument("--error-dpmpp-steps", type=int, nargs="+", default=[10, 20])
     p.add_argument("--error-ddim-steps", type=int, nargs="+", default=[10, 20, 50])
     p.add_argument("--skip", choices=["latency", "error"], default=None)
+    p.add_argument("--lib", default=None, metavar="PATH", help="load this build of libldp_hip instead of the in-tree one (same-box A/B)")
     a = p.parse_args()
     from latent_diffusion_planning_amd import _lib
+    if a.lib:
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     torch.cuda.set_device(0)
     out = dict(tool="solver_bench", config="rm_lift", figures="[median, min, max] ms per call", steps=a.steps, repeats=a.repeats,
-               version=_lib.load().ldp_version().decode())
+               lib=a.lib or "in-tree", version=_lib.load().ldp_version().decode())
     if a.skip != "latency":
         out["latency"] = latency(a)
     if a.skip != "error":
