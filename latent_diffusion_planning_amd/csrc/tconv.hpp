@@ -1413,36 +1413,49 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
         return;
       }
     }
-    // the other parts' partial of element (sr, el), added in part order.  All granules of the element are requested
-    // together; the wave re-requests until every lane holds current tags (bounded: a peer that never publishes ends
-    // in the fault word like the statistics exchange's).
-    auto kw_add = [&](float x, int pass, int sr, int el) {
-      if (!(KW_OK && kw > 1)) return x;
-      unsigned long long pv[KW_MAX - 1];
-      int spin = 0;
-      for (;;) {
-        bool ok = true;
-        // kw - 1 polls (kw is uniform: the guards are scalar branches), not KW_MAX - 1
+    // The other parts' partials of the EPL elements of sample row sr, added in part order.  The granules of a batch --
+    // KW_EC elements x (kw - 1) parts -- are requested back to back and awaited ONCE: one fabric round trip per batch,
+    // where a request batch and a wait per element made EPL strictly sequential ones.  A batch costs 2 (KW_MAX - 1)
+    // VGPRs per element: the whole row where a lane holds one or two elements of it, two elements of the row in the
+    // 64-column tiles (EPL = 4, 8), which a whole row costs a wave per SIMD; for the same reason the rows of the wave's
+    // SPW samples stay batches of their own.  The wave re-requests a batch until every lane holds current tags
+    // (bounded: a peer that never publishes ends in the fault word like the statistics exchange's).
+    constexpr int KW_EC = EPL <= 2 ? EPL : 2;
+    auto kw_add_row = [&](float (&x)[EPL], int pass, int sr) {
+      if (!(KW_OK && kw > 1)) return;
 #pragma unroll
-        for (int q = 0; q < KW_MAX - 1; ++q) {
-          pv[q] = 0;
-          if (q + 1 < kw)
-            pv[q] = __hip_atomic_load(kw_tile + (size_t)(q + 1) * (2 * TILE) + pass * TILE + sr * (TO * BN) + el,
-                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // all polls landed before any is checked (see the statistics exchange)
+      for (int e0 = 0; e0 < EPL; e0 += KW_EC) {
+        unsigned long long pv[KW_EC][KW_MAX - 1];
+        int spin = 0;
+        for (;;) {
+          bool ok = true;
+          // kw - 1 polls per element (kw is uniform: the guards are scalar branches), not KW_MAX - 1
 #pragma unroll
-        for (int q = 0; q < KW_MAX - 1; ++q) ok = ok && (q + 1 >= kw || granule_ok(pv[q], ktag));
-        if (__all(ok)) break;
-        if (++spin > (1 << 18) || ((spin & 1023) == 0 && __hip_atomic_load(a.fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)) {
-          if (lane == 0) *a.fault = 1u;
-          break;
+          for (int e = 0; e < KW_EC; ++e)
+#pragma unroll
+            for (int q = 0; q < KW_MAX - 1; ++q) {
+              pv[e][q] = 0;
+              if (q + 1 < kw)
+                pv[e][q] = __hip_atomic_load(kw_tile + (size_t)(q + 1) * (2 * TILE) + pass * TILE + sr * (TO * BN) + lane + 64 * (e0 + e),
+                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // all polls landed before any is checked (see the statistics exchange)
+#pragma unroll
+          for (int e = 0; e < KW_EC; ++e)
+#pragma unroll
+            for (int q = 0; q < KW_MAX - 1; ++q) ok = ok && (q + 1 >= kw || granule_ok(pv[e][q], ktag));
+          if (__all(ok)) break;
+          if (++spin > (1 << 18) || ((spin & 1023) == 0 && __hip_atomic_load(a.fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)) {
+            if (lane == 0) *a.fault = 1u;
+            break;
+          }
+          __builtin_amdgcn_s_sleep(1);
         }
-        __builtin_amdgcn_s_sleep(1);
+#pragma unroll
+        for (int e = 0; e < KW_EC; ++e)
+#pragma unroll
+          for (int q = 0; q < KW_MAX - 1; ++q) x[e0 + e] += (q + 1 < kw) ? __uint_as_float((unsigned int)pv[e][q]) : 0.0f;
       }
-#pragma unroll
-      for (int q = 0; q < KW_MAX - 1; ++q) x += (q + 1 < kw) ? __uint_as_float((unsigned int)pv[q]) : 0.0f;
-      return x;
     };
 
     // phase A: K-split partial sums -> values, per-sample (sum, sum of squares); with a column-split
@@ -1459,6 +1472,7 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
       tag = ((unsigned int)a.ctl[2] << 12) + (unsigned int)a.step + 1u;     // unique per (call, step)
     }
     float vv[SPW][EPL];
+    float rv[SPW][EPL];                // RES_OUT: the projection's values, stored behind the poll wait
     float s1a[SPW], s2a[SPW];
     bool range_bad = false;            // fp16-plane tiles: a sum of squares that is not finite (the range guard below)
 #pragma unroll
@@ -1474,11 +1488,14 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
 #pragma unroll
           for (int k2 = 0; k2 < KS; ++k2)
             x += smem[((((sr >> 4) * KS + k2) * TO + to) * 16 + (sr & 15)) * BNP + col];
-          x = kw_add(x, 0, sr, el);
         }
         vv[si][e] = x;
-        s1 += x;
-        s2 += x * x;
+      }
+      if (FULL || sr < NS) kw_add_row(vv[si], 0, sr);
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) {
+        s1 += vv[si][e];
+        s2 += vv[si][e] * vv[si][e];
       }
       if (flags & EP_GN) {
         s1 = wave_sum(s1);
@@ -1528,6 +1545,152 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
         }
       }
       __syncthreads();
+      // The projection's values stay in registers (the accumulators are dead by now): their stores go out behind the
+      // poll wait below, which would otherwise also wait for every one of them to be acknowledged.
+#pragma unroll
+      for (int si = 0; si < SPW; ++si) {
+        const int sr = wave + si * C::NW;
+        const int b = b0 + sr;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) rv[si][e] = p_rb[e];
+        if ((!FULL && sr >= NS) || b >= a.B) continue;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+          const int el = lane + 64 * e;
+          const int to = el / BN, col = el % BN;
+#pragma unroll
+          for (int k2 = 0; k2 < KS; ++k2)
+            rv[si][e] += smem[((((sr >> 4) * KS + k2) * TO + to) * 16 + (sr & 15)) * BNP + col];
+        }
+        kw_add_row(rv[si], 1, sr);
+      }
+    }
+
+    LDP_TL(5);
+    // Statistics exchange, pipelined over the wave's samples.  Lane q requests peer q's record of one sample (16 bytes,
+    // sc1); the records reach the wave by readlane.  The poll of sample si + 1 is issued BEFORE the arithmetic of sample
+    // si and awaited behind it, so only the first of the wave's SPW round trips is exposed, and no output store of the
+    // wave is in flight at any poll wait: all stores go out behind the last sample's arithmetic (on gfx9 vmcnt counts
+    // stores too, so a wait placed behind the res_out stores or a previous sample's out stores also waited for their
+    // acknowledgements).  Measured and not kept: ONE batch for all SPW samples right behind phase A -- the peer publishes
+    // its second sample a slice pass later than its first, a tenth of the waves found it missing and paid a sleep and a
+    // second round trip, and a launch lasts as long as its slowest wave (HISTORY).
+    // Every poll has landed before it is looked at (agent-scope loads that miss -- peer on another XCD: two processes
+    // sharing the GPU -- were seen to be overtaken by later ones that hit, while the compiler's partial vmcnt(N) waits
+    // assume in-order returns), and it is re-requested until every record carries this call's tag; bounded: a peer that
+    // never publishes ends in the fault word.
+    const int pq_pp = lane < half ? lane : lane + 1;           // the part lane q polls
+    auto poll_issue = [&](int si, u32x4_t& pg) {
+      const int sr = wave + si * C::NW;
+      if (lane < cs - 1 && (FULL || sr < NS))
+        pg = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, xbase + (unsigned int)(((sr >> 4) * ngroups * 4 + pq_pp) * 256 + (sr & 15) * 16), 0, AUX_SC1);
+    };
+    auto poll_wait = [&](int si, u32x4_t& pg) {
+      const int sr = wave + si * C::NW;
+      const bool pact = lane < cs - 1 && (FULL || sr < NS);
+      int spin = 0;
+      for (;;) {
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(pg) :: "memory");
+        const bool ok = !pact || (((pg[0] ^ pg[1]) == tag) && ((pg[2] ^ pg[3]) == tag));
+        if (__all(ok)) break;
+        if (++spin > (1 << 20) || ((spin & 1023) == 0 && __hip_atomic_load(a.fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)) {
+          if (lane == 0) *a.fault = 1u;
+          break;
+        }
+        __builtin_amdgcn_s_sleep(1);
+        poll_issue(si, pg);
+      }
+#ifdef LDP_TIMELINE
+      if (a.tl && lane == 0) {      // exchanges and extra poll rounds of this launch (tools/timeline.py)
+        atomicAdd(&a.tl[120000], 1ull);
+        atomicAdd(&a.tl[120001], (unsigned long long)spin);
+      }
+#endif
+    };
+    u32x4_t pg_cur = {0u, 0u, 0u, 0u}, pg_nxt = {0u, 0u, 0u, 0u};
+    if (xch) {
+      poll_issue(0, pg_cur);
+      poll_wait(0, pg_cur);
+    }
+    LDP_TL(6);
+    // The operands fetched ahead of the epilogue sit behind uniform branches, so the compiler guards their first use in
+    // each sample's block with a full s_waitcnt vmcnt(0) (read off the ISA) -- which would also wait for the next
+    // sample's poll.  They have all landed by now: handed through an empty asm here, they are plain registers below.
+    // (Only where a wave holds few of them -- the tiles of the column-split launches: on the wide tiles the pinned
+    // registers cost a wave per SIMD, and those keep the compiler's waits.)
+    auto settle = [](float& x) { asm volatile("" : "+v"(x)); };
+    if constexpr (SPW > 1 && SPW * EPL <= 4) {
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) { settle(p_gs[e]); settle(p_gb[e]); }
+#pragma unroll
+      for (int si = 0; si < SPW; ++si)
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) { settle(p_fts[si][e]); settle(p_fgs[si][e]); settle(p_ftb[si][e]); settle(p_fgb[si][e]); settle(p_add[si][e]); }
+    }
+
+    // phase B: statistics (own half + peer half, always summed as half0 + half1), normalise; then store
+    float gs1 = 0.f, gs2 = 0.f;
+#pragma unroll
+    for (int si = 0; si < SPW; ++si) {
+      const int sr = wave + si * C::NW;
+      if (xch && si + 1 < SPW) poll_issue(si + 1, pg_nxt);
+      if (FULL || sr < NS) {
+        const int b = b0 + sr;
+        const bool live = b < a.B;
+        float* v = vv[si];
+        float mean = 0.f, rstd = 1.f;
+        if (flags & EP_GN) {
+          float s1 = s1a[si], s2 = s2a[si];
+          if (xch) {
+            // every part adds the cs partial sums in part order 0..cs-1 (its own from registers): all
+            // work-groups of the group obtain bit-identical statistics
+            float t1 = 0.f, t2 = 0.f;
+#pragma unroll
+            for (int pp = 0; pp < 4; ++pp) {
+              if (pp >= cs) continue;
+              const int q = pp < half ? pp : pp - 1;
+              float p1 = s1, p2 = s2;
+              if (pp != half) {
+                p1 = __uint_as_float(__builtin_amdgcn_readlane(pg_cur[0], q));
+                p2 = __uint_as_float(__builtin_amdgcn_readlane(pg_cur[2], q));
+              }
+              t1 = pp == 0 ? p1 : t1 + p1;
+              t2 = pp == 0 ? p2 : t2 + p2;
+            }
+            s1 = t1;
+            s2 = t2;
+          }
+          const float inv_n = 1.0f / (float)(TO * BN * cs);
+          mean = s1 * inv_n;
+          const float var = fmaxf(s2 * inv_n - mean * mean, 0.0f);
+#if LDP_EPILOGUE_IEEE
+          rstd = 1.0f / sqrtf(var + 1e-6f);
+#else
+          rstd = __builtin_amdgcn_rsqf(var + 1e-6f);
+#endif
+        }
+        if (live) {
+#pragma unroll
+          for (int e = 0; e < EPL; ++e) {
+            float y = v[e];
+            if (flags & EP_GN) {
+              y = (y - mean) * rstd * p_gs[e] + p_gb[e];
+              y = mish_f(y);
+            }
+            if (flags & EP_FILM) y = (p_fts[si][e] + p_fgs[si][e]) * y + (p_ftb[si][e] + p_fgb[si][e]);
+            if (flags & EP_RESIN) y += p_add[si][e];
+            if (flags & EP_RELU) y = fmaxf(y, 0.0f);
+            v[e] = y;
+          }
+        }
+      }
+      if (xch && si + 1 < SPW) {
+        poll_wait(si + 1, pg_nxt);
+        pg_cur = pg_nxt;
+      }
+    }
+    // every store of the wave goes out behind the arithmetic of ALL its samples (see above)
+    if (RES_OUT) {
 #pragma unroll
       for (int si = 0; si < SPW; ++si) {
         const int sr = wave + si * C::NW;
@@ -1535,109 +1698,23 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
         if ((!FULL && sr >= NS) || b >= a.B) continue;
 #pragma unroll
         for (int e = 0; e < EPL; ++e) {
-          const int el = lane + 64 * e;
-          const int to = el / BN, col = el % BN;
-          float x = p_rb[e];
-#pragma unroll
-          for (int k2 = 0; k2 < KS; ++k2)
-            x += smem[((((sr >> 4) * KS + k2) * TO + to) * 16 + (sr & 15)) * BNP + col];
-          x = kw_add(x, 1, sr, el);
+          const float x = rv[si][e];
           if (!LDP_ABL(128) || x == 12345.f) (a.res_out + ((size_t)b * TO + e_to(e)) * a.cout + e_col(e))[lane_eoff] = x;
         }
       }
     }
-
-    LDP_TL(5);
-    // phase B: statistics (own half + peer half, always summed as half0 + half1), normalise, store
-    float gs1 = 0.f, gs2 = 0.f;
 #pragma unroll
     for (int si = 0; si < SPW; ++si) {
       const int sr = wave + si * C::NW;
-      if (!FULL && sr >= NS) continue;
       const int b = b0 + sr;
-      const bool live = b < a.B;
-      float* v = vv[si];
-      float mean = 0.f, rstd = 1.f;
-      if (flags & EP_GN) {
-        float s1 = s1a[si], s2 = s2a[si];
-        if (xch) {
-          // every part adds the cs partial sums in part order 0..cs-1 (its own from registers): all
-          // work-groups of the group obtain bit-identical statistics
-          // the cs - 1 peers' records are requested together (one L2 round trip, not one per peer) and re-requested
-          // until every one carries this call's tag; bounded: a peer that never publishes ends in the fault word
-          u32x4_t pg[3];
-          int spin = 0;
-          for (;;) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-              pg[q] = u32x4_t{0u, 0u, 0u, 0u};
-              if (q < cs - 1) {
-                const int pp = q < half ? q : q + 1;
-                pg[q] = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, xbase + (unsigned int)(((sr >> 4) * ngroups * 4 + pp) * 256 + (sr & 15) * 16), 0, AUX_SC1);
-              }
-            }
-            // Every poll has landed before any is looked at, and none is left in flight into the next round: agent-scope
-            // loads that miss (peer on another XCD: two processes sharing the GPU) were seen to be overtaken by later
-            // ones that hit, while the compiler's partial vmcnt(N) waits assume in-order returns.
-            asm volatile("s_waitcnt vmcnt(0)" : "+v"(pg[0]), "+v"(pg[1]), "+v"(pg[2]) :: "memory");
-            bool ok = true;
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-              ok = ok && (q >= cs - 1 || (((pg[q][0] ^ pg[q][1]) == tag) && ((pg[q][2] ^ pg[q][3]) == tag)));
-            if (ok) break;
-            if (++spin > (1 << 20) || ((spin & 1023) == 0 && __hip_atomic_load(a.fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)) {
-              if (lane == 0) *a.fault = 1u;
-              break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-          }
-#ifdef LDP_TIMELINE
-          if (a.tl && lane == 0) {      // exchanges and extra poll rounds of this launch (tools/timeline.py)
-            atomicAdd(&a.tl[120000], 1ull);
-            atomicAdd(&a.tl[120001], (unsigned long long)spin);
-          }
-#endif
-          // every part adds the cs partial sums in part order 0..cs-1 (its own from registers)
-          float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-          for (int pp = 0; pp < 4; ++pp) {
-            if (pp >= cs) continue;
-            const int q = pp < half ? pp : pp - 1;
-            float p1 = s1, p2 = s2;
-            if (pp != half) {
-              p1 = __uint_as_float(q == 0 ? pg[0][0] : q == 1 ? pg[1][0] : pg[2][0]);
-              p2 = __uint_as_float(q == 0 ? pg[0][2] : q == 1 ? pg[1][2] : pg[2][2]);
-            }
-            t1 = pp == 0 ? p1 : t1 + p1;
-            t2 = pp == 0 ? p2 : t2 + p2;
-          }
-          s1 = t1;
-          s2 = t2;
-        }
-        const float inv_n = 1.0f / (float)(TO * BN * cs);
-        mean = s1 * inv_n;
-        const float var = fmaxf(s2 * inv_n - mean * mean, 0.0f);
-#if LDP_EPILOGUE_IEEE
-        rstd = 1.0f / sqrtf(var + 1e-6f);
-#else
-        rstd = __builtin_amdgcn_rsqf(var + 1e-6f);
-#endif
-      }
-      if (!live) continue;
+      if ((!FULL && sr >= NS) || b >= a.B) continue;
 #pragma unroll
       for (int e = 0; e < EPL; ++e) {
         const int el = lane + 64 * e;
         const int to = el / BN, col = el % BN;
         const int c = cbk * BN + col;
-        float y = v[e];
-        if (flags & EP_GN) {
-          y = (y - mean) * rstd * p_gs[e] + p_gb[e];
-          y = mish_f(y);
-        }
-        if (flags & EP_FILM) y = (p_fts[si][e] + p_fgs[si][e]) * y + (p_ftb[si][e] + p_fgb[si][e]);
+        const float y = vv[si][e];
         float* const optr = a.out + ((size_t)b * TO + e_to(e)) * a.cout + e_col(e);      // uniform; element at [lane_eoff]
-        if (flags & EP_RESIN) y += p_add[si][e];
-        if (flags & EP_RELU) y = fmaxf(y, 0.0f);
         if (flags & (EP_STEP | EP_EPSOUT)) {
           if (c < a.d_real && (b * TO + to) < a.rows_valid) {
             if (flags & EP_EPSOUT) (a.eps_out + ((size_t)b * TO + e_to(e)) * a.d_real + e_col(e))[lane_uoff] = y;
@@ -1665,9 +1742,19 @@ __global__ __launch_bounds__(64 * (((SPLIT == 1 || SPLIT == 4) && MB == 2) ? NWN
     if constexpr (C::F16) {
       if (LDP_RANGE_GUARD && range_bad && a.fault) a.fault[1] = 1u;
     }
-    LDP_TL(6);
 #ifdef LDP_TIMELINE
-    if (a.tl) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); LDP_TL(7); }
+    // a wave record holds eight stamps and the epilogue has one phase more than that leaves room for: stamp 7 is the
+    // time the stores have landed (low 48 bits) and, in its top 16 bits, how many ticks earlier the last of them was
+    // issued (the drain; saturating)
+    if (a.tl) {
+      const unsigned long long t_issued = __builtin_amdgcn_s_memtime();
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const unsigned long long t_landed = __builtin_amdgcn_s_memtime();
+      const unsigned long long drain = t_landed - t_issued < 0xffffull ? t_landed - t_issued : 0xffffull;
+      if (lane == 0)
+        a.tl[((size_t)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) * 16 + wave) * 8 + 7] =
+            (t_landed & 0xffffffffffffull) | (drain << 48);
+    }
 #endif
     if (C::STATS) {
       if (a.stats_part) {                                // uniform: every wave of the work-group takes this path

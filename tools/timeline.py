@@ -7,7 +7,8 @@ points of tconv_kernel; the product library carries none of this).  Runs the ben
 from its hipGraph, reads the stamps of the first two evaluations and prints, per launch of the second one:
 duration (last wave's end - first wave's entry, per XCD: s_memtime is a per-XCD counter; median over the XCDs), the gap to
 the previous launch and the median over waves of each phase.  Stamps: 0 entry, 1 first tile staged (prologue barrier), 2 main loop done, 3 accumulators in LDS,
-4 K-combine + statistics published, 5 projection pass done, 6 normalised + stores issued, 7 stores landed.
+4 K-combine + statistics published, 5 projection pass done (its values in registers), 6 the wave's poll batch has landed, 7 stores landed -- with, in its top 16
+bits, the ticks since the last store was issued (a wave record holds eight words; the tool unpacks it into 8 "normalised + stores issued" and 9 "stores landed").
 The instrumentation costs ~0.3 us per launch; the numbers are for comparing phases, not for the bench line.
 
     python tools/timeline.py [--batch 256] [--json out.json]
@@ -29,7 +30,8 @@ from latent_diffusion_planning_amd import weights as W  # noqa: E402
 from latent_diffusion_planning_amd.engine import HipEngine  # noqa: E402
 
 SLOT = 131072          # u64 per launch slot
-PHASES = ["prologue", "main", "acc->lds", "K+stats", "proj", "norm+store", "drain"]
+PHASES = ["prologue", "main", "acc->lds", "K+stats", "proj", "poll wait", "norm+store", "drain"]
+NP = len(PHASES)
 
 
 def main():
@@ -67,7 +69,10 @@ def main():
     flat[:, 120000:120002] = 0
     if os.environ.get("TL_DEBUG"):
         print("poll counters per slot:", polls[:, 0].tolist(), polls[:, 1].tolist())
-    st = flat.reshape(64, SLOT // 8, 8)                       # [slot][wave record][stamp]
+    raw = flat.reshape(64, SLOT // 8, 8).view(np.uint64)      # [slot][wave record][word]
+    t48 = raw & np.uint64((1 << 48) - 1)                      # the counter's low 48 bits; word 7 carries the drain above them
+    landed, drain = t48[..., 7], raw[..., 7] >> np.uint64(48)
+    st = np.concatenate([t48[..., :7], (landed - np.minimum(drain, landed))[..., None], landed[..., None]], axis=-1).astype(np.int64)      # [slot][wave record][stamp 0..8]
     P = a.period
     if a.raw:
         np.savez_compressed(a.raw, **{f"s{L}": st[L][(st[L] != 0).any(axis=1)] for L in range(2 * P)})
@@ -93,7 +98,7 @@ def main():
         phases, cur = [], []
         for r in domains(st[L]):
             n += len(r)
-            done = np.where(r[:, 7] != 0, r[:, 7], r[:, 2])        # waves that left early (K-partial parts) have no late stamps
+            done = np.where(r[:, NP] != 0, r[:, NP], r[:, 2])        # waves that left early (K-partial parts) have no late stamps
             t0, t1 = r[:, 0].min(), done.max()
             durs.append(us(t1 - t0))
             near = [e for (b0, e) in prev if abs(int(t0) - int(b0)) < 250000]
@@ -109,12 +114,12 @@ def main():
         if not durs:
             rows.append(None)
             continue
-        ph = np.concatenate(phases) if phases else np.zeros((1, 7))
+        ph = np.concatenate(phases) if phases else np.zeros((1, NP))
         rows.append(dict(layer=L % P, waves=n, domains=len(durs), dur_us=float(np.median(durs)),
                          gap_us=float(np.median(gaps)) if gaps else 0.0,
                          entry_skew_us=float(np.median(skin)), end_skew_us=float(np.median(skout)),
-                         phases_us=[us(np.median(ph[:, i])) for i in range(7)],
-                         phases_p90_us=[us(np.percentile(ph[:, i], 90)) for i in range(7)]))
+                         phases_us=[us(np.median(ph[:, i])) for i in range(NP)],
+                         phases_p90_us=[us(np.percentile(ph[:, i], 90)) for i in range(NP)]))
     print("layer waves   dur   gap  skewIn skewOut | " + " ".join(f"{p:>10s}" for p in PHASES))
     tot = 0.0
     for row in rows[P:]:
