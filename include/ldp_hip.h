@@ -712,14 +712,16 @@ LDP_API int ldp_train_grad_norm(ldp_handle* h, int32_t modules, float* out, void
 
 /* One TrainState.apply_gradients with tx = optax.adam(lr): mu = (1 - b1) g + b1 mu; nu = (1 - b2) g^2 + b2 nu; count += 1;
  * p += -lr * (mu / (1 - b1^count)) / (sqrt(nu / (1 - b2^count)) + eps)   (optax 0.2.2 scale_by_adam, eps_root = 0; one launch over the arena).
- * lr = schedule(count before the increment), evaluated by the caller. */
-LDP_API int ldp_train_apply(ldp_handle* h, int32_t module, float lr, float b1, float b2, float eps, void* stream);
+ * lr = schedule(count before the increment), evaluated by the caller.  b1 / b2 / eps are doubles, as optax receives them: 1 - b and
+ * 1 - b^count are formed in double and rounded to float32 once (1 - (float)0.999 is 1.3e-5 short of (float)0.001). */
+LDP_API int ldp_train_apply(ldp_handle* h, int32_t module, float lr, double b1, double b2, double eps, void* stream);
 
 /* TrainStateEMA(ema_decay = decay, ema_params = params) (agent/dp_repr_agent.py:290-296): allocates the module's EMA arena and copies the
  * current parameters into it.  From then on every ldp_train_apply of the module also writes
  *   ema = ema * decay + p_new * (1 - decay)        (TrainStateEMA.apply_ema, utils/flax_utils.py:22-27; :155)
- * in the same launch, and ldp_train_init re-seeds it from the parameters.  Synchronises `stream`. */
-LDP_API int ldp_train_ema(ldp_handle* h, int32_t module, float decay, void* stream);
+ * in the same launch (decay and 1 - decay each rounded to float32 once, 1 - decay formed in double), and ldp_train_init re-seeds it from
+ * the parameters.  Synchronises `stream`. */
+LDP_API int ldp_train_ema(ldp_handle* h, int32_t module, double decay, void* stream);
 
 /* TrainState.step of a module: *out = the count (number of ldp_train_apply calls since init); set_to >= 0 overwrites it first (checkpoint
  * restore). */

@@ -183,14 +183,14 @@ SIGNATURES: Dict[str, tuple] = {
     "ldp_train_vae_grad": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_float, _FP, C.c_uint64, C.c_int64, _FP, C.c_void_p]),
     "ldp_train_vae_grad_part": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _FP, C.c_uint64, C.c_int64, _FP, C.c_void_p]),
     "ldp_train_grad_norm": (C.c_int, [_H, C.c_int32, _FP, C.c_void_p]),
-    "ldp_train_apply": (C.c_int, [_H, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "ldp_train_apply": (C.c_int, [_H, C.c_int32, C.c_float, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "ldp_train_step_count": (C.c_int, [_H, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "ldp_train_read": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ldp_train_write": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ldp_train_arena": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "ldp_train_publish": (C.c_int, [_H, C.c_int32, C.c_void_p]),
     "ldp_train_publish_ema": (C.c_int, [_H, C.c_int32, C.c_void_p]),
-    "ldp_train_ema": (C.c_int, [_H, C.c_int32, C.c_float, C.c_void_p]),
+    "ldp_train_ema": (C.c_int, [_H, C.c_int32, C.c_double, C.c_void_p]),
     "ldp_policy_sample": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_uint64, C.c_int64, C.c_int32, C.c_int32,
                                     _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
 }

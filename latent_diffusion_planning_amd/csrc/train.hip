@@ -1010,11 +1010,14 @@ __global__ __launch_bounds__(256) void colsum_jobs2_kernel(const ColJobs js, con
 //   p += -lr * (mu / bc1) / (sqrt(nu / bc2) + eps),  bc = 1 - b^count   (oracle/train.py adam_apply)
 // One work-group per 1024-element stripe (sumsq1_kernel's stripes and reduction order): besides the update it leaves the stripe's sum of squared
 // gradients in part[block], so that the global norm of the step (a metric: agent/ldp_agent.py:253, nothing is clipped) costs no second pass over the arena.
-// kEma (a module with ldp_train_ema): TrainStateEMA.apply_ema (utils/flax_utils.py:22-27) in the same pass, e = e * d + p_new * (1 - d); the
-// kEma = false instantiation is the code every other caller has always run (same P / M / V / part[] bits).
+// kEma (a module with ldp_train_ema): TrainStateEMA.apply_ema (utils/flax_utils.py:22-27) in the same pass, e = e * d + p_new * (1 - d).  Both
+// instantiations leave the same P / M / V / part[] bits from the same state (tests/test_hip_optimizer.py holds them to it).
+// omb1 / omb2 / ema_1md are 1 - b1, 1 - b2, 1 - d formed by the host in DOUBLE from the doubles the caller passed and rounded once, as optax
+// and flax form them (a Python float meets a float32 array): 1.0f - 0.999f is exact in float32 and therefore 1 - (float)0.999 = 0.0009999871,
+// 1.3e-5 short of 0.001 -- every nu was that much too small, and against bias corrections formed from the double the step 6.5e-6 too long.
 template <bool kEma>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ mu, float* __restrict__ nu, long long n, float lr,
-                                                   float b1, float b2, float eps, float bc1, float bc2, float* __restrict__ part,
+                                                   float b1, float b2, float omb1, float omb2, float eps, float bc1, float bc2, float* __restrict__ part,
                                                    float* __restrict__ ema, float ema_d, float ema_1md) {
   __shared__ float red[4];
   const long long i0 = (long long)blockIdx.x * 1024 + threadIdx.x;
@@ -1025,8 +1028,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     if (i < n) {
       const float gi = g[i];
       s += gi * gi;
-      const float m = (1.0f - b1) * gi + b1 * mu[i];
-      const float v = (1.0f - b2) * (gi * gi) + b2 * nu[i];
+      const float m = omb1 * gi + b1 * mu[i];
+      const float v = omb2 * (gi * gi) + b2 * nu[i];
       mu[i] = m;
       nu[i] = v;
       const float pn = p[i] + (-lr) * ((m / bc1) / (sqrtf(v / bc2) + eps));
@@ -1098,7 +1101,7 @@ struct Module {
   DevBuf E;                       // EMA of the parameters (ldp_train_ema), same layout as P
   DevBuf Gpart;                   // the gradients of one part of a batch before they are added to G (allocated by the first accumulating call)
   bool ema_on = false;
-  float ema_decay = 0.0f;
+  double ema_decay = 0.0;         // as the caller gave it: 1 - decay is formed from the double (ldp_train_apply)
   bool gpart_fresh = false;       // gpart holds the stripes' sums of squares of the CURRENT gradients (left by ldp_train_apply)
   long long step = 0;
   bool ready = false;
@@ -2315,19 +2318,21 @@ int ldp_train_grad_norm(ldp_handle* h, int32_t modules, float* out, void* stream
   return LDP_OK;
 }
 
-int ldp_train_apply(ldp_handle* h, int32_t module, float lr, float b1, float b2, float eps, void* stream) {
+int ldp_train_apply(ldp_handle* h, int32_t module, float lr, double b1, double b2, double eps, void* stream) {
   Module* m = nullptr;
   LDP_TRY(need_module(h, module, &m));
   const long long count = m->step + 1;
-  const float bc1 = (float)(1.0 - std::pow((double)b1, (double)count)), bc2 = (float)(1.0 - std::pow((double)b2, (double)count));
+  // every scalar derived from b1 / b2 is formed in double and rounded once (see adam_kernel)
+  const float bc1 = (float)(1.0 - std::pow(b1, (double)count)), bc2 = (float)(1.0 - std::pow(b2, (double)count));
+  const float b1f = (float)b1, b2f = (float)b2, omb1 = (float)(1.0 - b1), omb2 = (float)(1.0 - b2), epsf = (float)eps;
   const dim3 grid((unsigned)((m->total + 1023) / 1024));
   if (m->ema_on) {
-    const float d = m->ema_decay, omd = (float)(1.0 - (double)m->ema_decay);
+    const float d = (float)m->ema_decay, omd = (float)(1.0 - m->ema_decay);
     hipLaunchKernelGGL(adam_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, m->P.f(), m->G.f(), m->M.f(), m->V.f(),
-                       (long long)m->total, lr, b1, b2, eps, bc1, bc2, m->gpart.f(), m->E.f(), d, omd);
+                       (long long)m->total, lr, b1f, b2f, omb1, omb2, epsf, bc1, bc2, m->gpart.f(), m->E.f(), d, omd);
   } else {
     hipLaunchKernelGGL(adam_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, m->P.f(), m->G.f(), m->M.f(), m->V.f(),
-                       (long long)m->total, lr, b1, b2, eps, bc1, bc2, m->gpart.f(), nullptr, 0.0f, 0.0f);
+                       (long long)m->total, lr, b1f, b2f, omb1, omb2, epsf, bc1, bc2, m->gpart.f(), nullptr, 0.0f, 0.0f);
   }
   LDP_HIP(hipGetLastError());
   m->gpart_fresh = true;
@@ -2435,10 +2440,10 @@ int ldp_train_publish(ldp_handle* h, int32_t modules, void* stream) { return pub
 
 int ldp_train_publish_ema(ldp_handle* h, int32_t modules, void* stream) { return publish(h, modules, true, stream); }
 
-int ldp_train_ema(ldp_handle* h, int32_t module, float decay, void* stream) {
+int ldp_train_ema(ldp_handle* h, int32_t module, double decay, void* stream) {
   Module* m = nullptr;
   LDP_TRY(need_module(h, module, &m));
-  if (!(decay >= 0.0f && decay <= 1.0f)) return fail(LDP_EINVAL, "ema decay must lie in [0, 1], got %g", (double)decay);
+  if (!(decay >= 0.0 && decay <= 1.0)) return fail(LDP_EINVAL, "ema decay must lie in [0, 1], got %g", decay);
   hipStream_t s = (hipStream_t)stream;
   LDP_HIP(hipSetDevice(h->cfg.device));
   LDP_TRY(m->E.alloc(m->total * 4));

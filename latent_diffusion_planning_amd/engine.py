@@ -1207,7 +1207,7 @@ class HipEngine:
         return out
 
     def train_apply(self, module: str, lr: float, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8) -> None:
-        check(self.lib.ldp_train_apply(self._h, self._MODS[module], C.c_float(lr), C.c_float(b1), C.c_float(b2), C.c_float(eps), self._stream()))
+        check(self.lib.ldp_train_apply(self._h, self._MODS[module], C.c_float(lr), C.c_double(b1), C.c_double(b2), C.c_double(eps), self._stream()))
 
     def train_step_count(self, module: str, set_to: Optional[int] = None) -> int:
         v = C.c_int64()
@@ -1220,7 +1220,7 @@ class HipEngine:
         """TrainStateEMA(ema_decay=decay, ema_params=params): the module's EMA arena starts as a copy of its parameters; every later
         train_apply updates it in the same launch, every train_init / train_load re-seeds it from the parameters."""
         with torch.cuda.device(self.device):
-            check(self.lib.ldp_train_ema(self._h, self._MODS[module], C.c_float(decay), self._stream()))
+            check(self.lib.ldp_train_ema(self._h, self._MODS[module], C.c_double(decay), self._stream()))
         self.ema_decay[module] = float(decay)
 
     def train_read(self, module: str, which: int, shapes) -> Dict[str, np.ndarray]:
