@@ -22,10 +22,11 @@ import numpy as np
 import torch
 
 
-def make_agent(args, decay_steps):
+def make_agent(args, decay_steps, config=None):
+    """config: the task's counterpart of toyenv.reach2d_config (default: reach2d's own)."""
     from latent_diffusion_planning_amd.agent import LDPAgent
     from latent_diffusion_planning_amd.toyenv import reach2d_config
-    cfg = reach2d_config(action_dim=args.action_dim, lr=args.lr, warmup_steps=min(500, max(decay_steps // 10, 1)), decay_steps=decay_steps)
+    cfg = (config or reach2d_config)(action_dim=args.action_dim, lr=args.lr, warmup_steps=min(500, max(decay_steps // 10, 1)), decay_steps=decay_steps)
     return LDPAgent.create(args.seed, None, cfg["shape_meta"], **cfg["agent_kwargs"]), cfg
 
 
@@ -70,6 +71,24 @@ def scripted_arm(env, policy, noise, rounds, seed, episode0):
                 n_calls=rounds, cycles_per_episode=1)
 
 
+def add_stderr(results):
+    """success_stderr = sqrt(p (1 - p) / n) for every arm, in place; a mean over no success becomes None (JSON has no NaN)."""
+    for res in results.values():
+        p, n = res["success_rate"], res["n_rollout"]
+        res["success_stderr"] = float(np.sqrt(p * (1 - p) / n))
+        if res["mean_first_success"] is not None and np.isnan(res["mean_first_success"]):
+            res["mean_first_success"] = None                   # no success at all (JSON has no NaN)
+
+
+def print_table(results, extra=()):
+    """One line per arm; extra: (heading, format, key) of further columns (default: none, reach2d's table)."""
+    print(f"{'arm':44s} success  +-se   first  blocked  ms/call" + "".join(f"  {h}" for h, _, _ in extra))
+    for name, r in results.items():
+        first = "    -" if r["mean_first_success"] is None else f"{r['mean_first_success']:5.1f}"
+        more = "".join("  " + ("-".rjust(len(h)) if r.get(k) is None else format(r[k], f).rjust(len(h))) for h, f, k in extra)
+        print(f"{name:44s} {r['success_rate']:.4f}  {r['success_stderr']:.4f}  {first}  {r['blocked_share']:.4f}  {r['ms_per_call']:8.2f}" + more)
+
+
 def evaluate(args):
     from latent_diffusion_planning_amd import _lib, harness, weights as W
     from latent_diffusion_planning_amd.toyenv import Reach2DEnv
@@ -106,11 +125,7 @@ def evaluate(args):
         harness.run_device_eval(env, act, N, tr["demo_seed"], args.eval_rng, on_reset=on_reset, episode0=args.eval_episode0)      # warm-up: graphs, tables
         results[name] = harness.run_device_eval(env, act, N * rounds, tr["demo_seed"], args.eval_rng, on_reset=on_reset, episode0=args.eval_episode0)
         print(name, json.dumps(results[name]), flush=True)
-    for res in results.values():
-        p, n = res["success_rate"], res["n_rollout"]
-        res["success_stderr"] = float(np.sqrt(p * (1 - p) / n))
-        if np.isnan(res["mean_first_success"]):
-            res["mean_first_success"] = None                   # no success at all (JSON has no NaN)
+    add_stderr(results)
     out = dict(task="reach2d", note="toy task: ranks the planning modes on reach2d, says nothing about a robot", ldp_version=_lib.load().ldp_version().decode(),
                device=torch.cuda.get_device_name(0), episodes_per_arm=N * rounds, envs=N, rounds=rounds, env_seed=tr["demo_seed"],
                eval_episode0=args.eval_episode0, eval_rng=args.eval_rng, scripted_noise=tr["demo_noise"],
@@ -118,10 +133,7 @@ def evaluate(args):
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
-    print(f"{'arm':44s} success  +-se   first  blocked  ms/call")
-    for name, r in results.items():
-        first = "    -" if r["mean_first_success"] is None else f"{r['mean_first_success']:5.1f}"
-        print(f"{name:44s} {r['success_rate']:.4f}  {r['success_stderr']:.4f}  {first}  {r['blocked_share']:.4f}  {r['ms_per_call']:8.2f}")
+    print_table(results)
     agent._engine.close()
 
 
