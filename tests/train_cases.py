@@ -363,14 +363,15 @@ def oracle_idm(ip, c, alpha=1.0):
 
 
 # ---- the per-entry rule ----------------------------------------------------------------------------------------------------------------------
-def every_entry(got, ref, factor=1e-4, scale=None):
+def every_entry(got, ref, factor=1e-4, scale=None, floor=None):
     """|got - ref| <= factor max|scale leaf| + 1e-12 on every entry of every leaf (scale = ref unless given) -> (report of the worst entry, the
-    leaves over the bound as text)."""
+    leaves over the bound as text).  floor = {leaf: figure}: the rule of DESIGN 4.11, max(factor max|scale leaf|, floor[leaf]) + 1e-12, whose
+    callers pass three times the leaf's float32-against-float64 error."""
     worst, bad = dict(err_over_bound=0.0, leaf=None, at=None), []
     for k, r in ref.items():
         g, r = np.asarray(got[k], np.float64), np.asarray(r, np.float64)
         assert g.shape == r.shape, (k, g.shape, r.shape)
-        bound = factor * float(np.abs(r if scale is None else scale[k]).max()) + 1e-12
+        bound = max(factor * float(np.abs(r if scale is None else scale[k]).max()), 0.0 if floor is None else float(floor[k])) + 1e-12
         err = np.abs(g - r)
         i = int(np.argmax(np.where(np.isnan(err), np.inf, err)))
         ratio = float(err.flat[i]) / bound
